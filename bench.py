@@ -2,13 +2,23 @@
 """Headline benchmark: Gauss-Newton / LM iterations of the reference's pose solvers on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--problem ndt6|ndt3|reproj] [--dtype f64|f32] [--repeats R]
+                    [--dump-outputs DIR] [--full]
 
 One "step" is one full LM iteration over the rank's resident correspondences: assemble kernel (residual +
 analytic Jacobian + robust weight + 28- / 10-scalar reduction) → in-launch final reduce → [N > 1: one all-reduce of the
 28 doubles] → damping + 6x6 (3x3) LDLT + pose update + lambda schedule.  The dataset is uploaded before the timed
-region (inputs resident in HBM).  W untimed warm-up steps, then R trains of EXACTLY K steps, every train bracketed by
-device synchronisation (+ a barrier for N > 1) on both sides, MAX over ranks; `value` comes from the MEDIAN train and
-min / median / max are reported beside it.
+region (inputs resident in HBM).  W untimed warm-up steps, then R trains of EXACTLY K steps (R = 1 unless --repeats
+says otherwise; 5 with --full), every train bracketed by device synchronisation (+ a barrier for N > 1) on both sides,
+MAX over ranks; `value` comes from the MEDIAN train and min / median / max are reported beside it.
+
+A plain run does only that and prints the line.  --full adds everything else the benchmark measures, as the default run
+did before the option existed: the host-loop placement, the other single-GPU configurations and the stages
+(bench_stages.py), the 80 M-correspondence strong-scaling baseline, cold / warm single launches, the CPU baselines
+and, for N > 1, every in-launch exchange beside RCCL.  --no-* switches trim it.
+
+--dump-outputs DIR writes what a caller of the timed solve receives after the last timed step (rank 0): pose_R (3x3),
+pose_t (3), lm_report [iterations, printed cost, last cost, final lambda] and, for the device loop, cost_history (one
+cost per iteration), all float64 .npy.  The inputs are seeded, so equal arguments give equal inputs in every run.
 
 Problems (BASELINE.json configs):
   ndt6    configs[1]  mahalanobis_distance_minimizer 6-DoF, 10 M correspondences / 200 k voxels per GPU, fp64,
@@ -46,7 +56,12 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="trains of --steps timed steps (min / median / max reported)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="trains of --steps timed steps (min / median / max reported); default 1, with --full 5")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other measurement of the benchmark (see the module docstring); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs of its last step as DIR/<name>.npy (rank 0)")
     ap.add_argument("--problem", default="ndt6", choices=["ndt6", "ndt3", "reproj"])
     ap.add_argument("--points", type=int, default=0, help="correspondences per GPU (0 = the config's size)")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
@@ -59,10 +74,10 @@ def parse_args():
     ap.add_argument("--prewarm-ms", type=float, default=400.0,
                     help="untimed GPU activity (the same iteration) before the warm-up steps: the part needs ≈ 0.1-0.3 s "
                          "of load to reach its steady clocks; reported as prewarm_ms")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=1.2,
                     help="time budget of the longest CPU baseline leg of the headline (its thread-count sweep takes ≈ 4.5x this; "
-                         "the other configurations and stages get one short leg each: ≤ 10 s of CPU baselines in the default run)")
+                         "the other configurations and stages get one short leg each: ≤ 10 s of CPU baselines in the --full run)")
     ap.add_argument("--no-stages", action="store_true",
                     help="skip the stage lines (pose graph, matcher, map build, ingestion, reference wrappers: bench_stages.py)")
     ap.add_argument("--no-strong-baseline", action="store_true",
@@ -71,7 +86,10 @@ def parse_args():
     ap.add_argument("--no-cold", action="store_true", help="skip the cold (evicted) / warm single-launch measurement")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short trains of the other single-GPU configurations (other_configs in the JSON line)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------- workloads
@@ -89,6 +107,7 @@ class Workload:
         self.pose_t = np.zeros(3)
         self.pose_R = np.eye(3).reshape(-1).copy()
         self.rep = np.zeros(5)
+        self.cost_history = None
 
     def reset_pose(self):
         self.pose_t[:] = 0.0
@@ -99,7 +118,15 @@ class Workload:
         if not r["ok"] or r["iterations"] != k or r["launches"] not in (1, k):  # 1: one-launch form at small sizes
             raise RuntimeError("device LM loop failed: %r" % (r,))
         self.rep[:4] = [r["iterations"], r["printed_cost"], r["last_cost"], r["final_lambda"]]
+        self.cost_history = r["cost_history"]
         self.launches_of_last_solve = int(r["launches"])
+
+    def outputs(self):
+        """What the caller of the last solve received (--dump-outputs)."""
+        out = {"pose_R": self.pose_R.reshape(3, 3).copy(), "pose_t": self.pose_t.copy(), "lm_report": self.rep[:4].copy()}
+        if self.cost_history is not None:
+            out["cost_history"] = np.asarray(self.cost_history, dtype=np.float64).copy()
+        return out
 
     def _host_check(self, ok, k, rep):
         if not ok or int(rep[0]) != k:
@@ -406,9 +433,9 @@ def check_runtime(api, need_rccl):
 
 
 def dist_free_default(args):
-    """True for the default headline run (ndt6 fp64 flat, configs[1] size, device loop): the run that also carries short
+    """True for the full headline run (ndt6 fp64 flat, configs[1] size, device loop): the run that also carries short
     trains of the other single-GPU configurations."""
-    return (args.problem == "ndt6" and args.dtype == "f64" and args.layout == "flat" and args.loop == "device"
+    return (args.full and args.problem == "ndt6" and args.dtype == "f64" and args.layout == "flat" and args.loop == "device"
             and args.points in (0, 10_000_000) and not args.no_other_configs
             and os.environ.get("NOS_BENCH_FORCE_DIST", "0") != "1")
 
@@ -495,7 +522,7 @@ def main():
     planes = work.planes(n_local, rank)
     ds = work.dataset(ctx, planes)
     other_wanted = (world == 1 and dist_free_default(args))
-    keep_planes = rank == 0 and world == 1 and (not args.no_cpu_baseline or other_wanted)
+    keep_planes = rank == 0 and world == 1 and args.full and (not args.no_cpu_baseline or other_wanted)
     if not keep_planes:
         del planes
         planes = None
@@ -531,6 +558,7 @@ def main():
         ms, kms, launches = [], [], 0
         for _ in range(max(1, repeats)):
             work.reset_pose()  # every train does the same work: K iterations from the initial pose
+            work.cost_history = None
             fence()
             if os.environ.get("NOS_BENCH_NO_EVENTS", "0") != "1":
                 ctx.profile_begin(steps + 8, sample_every=0 if bracket else 4)
@@ -544,7 +572,8 @@ def main():
                 kms.append(k_mean)
                 launches += n_timed
         return {"ms_per_step": summarize(ms), "kernel_ms": summarize(kms) if kms else None, "launches_timed": launches,
-                "prewarm_ms": prewarm_ms, "final_translation_error_m": work.pose_error(), "lm_last_cost": float(work.rep[2])}
+                "prewarm_ms": prewarm_ms, "final_translation_error_m": work.pose_error(), "lm_last_cost": float(work.rep[2]),
+                "outputs": work.outputs()}
 
     legs = {}
     comm_mode = "none"
@@ -599,6 +628,8 @@ def main():
 
         failed_legs = {}
         for candidate in order:
+            if "rccl-native" in legs and not args.full:
+                break  # the headline exchange is timed; the mailbox forms beside it are --full's
             up = bring_up(candidate)
             if up is None:
                 continue
@@ -680,7 +711,7 @@ def main():
 
     # ---- second placement of the loop at N = 1 (host loop beside the device loop), one train
     host_loop = None
-    if dist is None and args.loop == "device":
+    if args.full and dist is None and args.loop == "device":
         ht, hR, hrep = np.zeros(3), np.eye(3).reshape(-1).copy(), np.zeros(5)
         work.iterate_host(ds, max(args.warmup, 1), ht, hR, hrep)
         ht[:], hR[:] = 0.0, np.eye(3).reshape(-1)
@@ -696,7 +727,7 @@ def main():
 
     # ---- cold (evicted from the 256 MiB Infinity Cache) vs warm single launches, for datasets that fit the cache
     cold_warm = None
-    if dist is None and not args.no_cold and args.layout == "flat" and bytes_per_launch <= (200 << 20):
+    if args.full and dist is None and not args.no_cold and args.layout == "flat" and bytes_per_launch <= (200 << 20):
         evict_n = 4_500_000  # 540 MB of fp64 planes streamed through the cache between two timed launches
         evictor = NdtDataset.from_planes(ctx, synth.ndt_planes(evict_n, 10_000), "f64")
 
@@ -787,7 +818,7 @@ def main():
 
     # ---- the denominator of the strong-scaling claim: configs[3]'s 80 M correspondences on ONE GPU
     strong = None
-    if (dist is None and not args.no_strong_baseline and args.problem == "ndt6" and args.layout == "flat"
+    if (args.full and dist is None and not args.no_strong_baseline and args.problem == "ndt6" and args.layout == "flat"
             and args.dtype == "f64" and args.points in (0, 10_000_000)):
         ds.close()
         big_n = args.strong_points
@@ -985,6 +1016,10 @@ def main():
         summary["wrap_reproj"] = [sig(w["ms"]["median"]), int(w["cost_line_equals_the_captured_run"])]
     summary["_"] = "[ms, frac of the line's bound (hbm | pcie; wrappers: 1 = COST lines equal the captured run)]"
     result["summary"] = summary
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in main_leg["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     if rank == 0:
         print(json.dumps(result), flush=True)
     if dist is not None:

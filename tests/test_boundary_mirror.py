@@ -3,18 +3,33 @@ the reference's own headers — member names, types, default values, enumerators
 signatures, the loss functions' arithmetic — because the drop-in classes compile against either one
 (-DNOS_IN_REFERENCE_TREE) and the in-tree build cannot be exercised here (no Eigen).
 
-Runs in the build container only: the reference is not mounted on the GPU box (skipped there); nothing of the reference
-travels — the headers are parsed where they lie."""
+The reference's side is tests/golden/reference_public_surface.json: one SHA-256 fingerprint per fact that
+public_surface() below extracts from the reference's headers (tests/golden/make_boundary_golden.py); no header text is
+stored.  The same extraction runs on the mirror here, and every fact must have the stored fingerprint."""
+import hashlib
+import json
 import os
 import re
 
 import pytest
 
-REF = "/root/reference/nonlinear_optimizer"
-MIRROR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nonlinear_optimizer_for_slam_amd", "csrc",
-                      "host", "nos_reference_api.hpp")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MIRROR = os.path.join(ROOT, "nonlinear_optimizer_for_slam_amd", "csrc", "host", "nos_reference_api.hpp")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_public_surface.json")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
+# the reference headers public_surface() reads, relative to its nonlinear_optimizer/ directory
+REFERENCE_HEADERS = {
+    "options": "options.h",
+    "loss": "loss_function.h",
+    "mdm_types": os.path.join("mahalanobis_distance_minimizer", "types.h"),
+    "mdm_solver": os.path.join("mahalanobis_distance_minimizer", "mahalanobis_distance_minimizer.h"),
+    "rem_types": os.path.join("reprojection_error_minimizer", "types.h"),
+    "rem_solver": os.path.join("reprojection_error_minimizer", "reprojection_error_minimizer.h"),
+    "pgo_types": os.path.join("pose_graph_optimizer", "types.h"),
+    "pgo": os.path.join("pose_graph_optimizer", "pose_graph_optimizer.h"),
+}
+LOSS_CLASSES = ("ExponentialLossFunction", "HuberLossFunction")
+PURE_EVALUATE = "virtual void Evaluate(const double squared_residual, double* output) = 0;"
 
 
 def _clean(path):
@@ -39,19 +54,19 @@ def _block(text, header_regex):
 
 
 def _members(body):
-    """[(type, name, default)] of `type name{default};` members, nested anonymous structs flattened as name.member."""
+    """[[type, name, default]] of `type name{default};` members, nested anonymous structs flattened as name.member."""
     out = []
     rest = body
     for m in re.finditer(r"struct\s*\{", body):
         inner = _block(body[m.start():], r"struct\s*")
         tail = body[m.start() + body[m.start():].index(inner) + len(inner) + 1:]
         name = re.match(r"\s*(\w+)\s*;", tail).group(1)
-        out += [(t, name + "." + n, d) for t, n, d in _members(inner)]
+        out += [[t, name + "." + n, d] for t, n, d in _members(inner)]
         rest = rest.replace("struct {" + inner + "} " + name + ";", " ").replace("struct {" + inner + "}" + name + ";", " ")
     # drop member functions (anything with a parameter list before a body) before looking for data members
     rest = re.sub(r"[\w:<>~&\*\s]+\([^()]*\)\s*(const)?\s*(final|override)?\s*(:[^{]*)?\{[^{}]*(\{[^{}]*\}[^{}]*)*\}", " ", rest)
     for m in re.finditer(r"((?:const\s+)?[\w:]+(?:<[^<>]*>)?)\s+(\w+)\s*\{([^{}]*)\}\s*;", rest):
-        out.append((m.group(1).replace(" ", ""), m.group(2), m.group(3).replace(" ", "")))
+        out.append([m.group(1).replace(" ", ""), m.group(2), m.group(3).replace(" ", "")])
     return out
 
 
@@ -65,79 +80,111 @@ def _signature(text, pattern):
     return re.sub(r"\s+", " ", m.group(0)).replace("( ", "(").replace(" )", ")").strip()
 
 
+def fingerprints(surface):
+    """{fact: SHA-256 of its canonical JSON}: what the golden file stores of the reference's surface."""
+    return {k: hashlib.sha256(json.dumps(v, sort_keys=True).encode()).hexdigest() for k, v in surface.items()}
+
+
+def public_surface(src):
+    """The facts both sides must share, from cleaned header texts keyed as REFERENCE_HEADERS (for the mirror: the
+    namespace blocks that stand for those headers)."""
+    out = {"Options": _members(_block(src["options"], r"struct Options\s*"))}
+    for e in ("MinimizerType", "LinearSolverType"):
+        out[e] = _enum(src["options"], e)
+    out["mdm.NDT"] = _members(_block(src["mdm_types"], r"struct NDT\s*"))
+    # `NDT ndt;` has no initialiser: the whole member list, textually
+    out["mdm.Correspondence"] = re.sub(r"\s+", "", _block(src["mdm_types"], r"struct Correspondence\s*"))
+    out["rem.CameraIntrinsics"] = _members(_block(src["rem_types"], r"struct CameraIntrinsics\s*"))
+    out["rem.Correspondence"] = _members(_block(src["rem_types"], r"struct Correspondence\s*"))
+    for cls in LOSS_CLASSES:
+        body = _block(src["loss"], r"class " + cls + r"\s*:\s*public LossFunction\s*")
+        # constructor parameter list
+        out[cls + ".constructor"] = re.sub(r"\s+", " ", re.search(cls + r"\(([^()]*)\)", body).group(1))
+        # the scalar Evaluate body, statement for statement
+        out[cls + ".Evaluate"] = re.sub(
+            r"\s+", "", _block(body, r"void Evaluate\(const double squared_residual, double output\[\d\]\) final\s*"))
+        # argument checks: same conditions, same exception type and message
+        out[cls + ".checks"] = [list(c) for c in re.findall(r"if \(([^()]*)\)\s*throw (std::\w+)\(\"([^\"]*)\"\)", body)]
+        # private data members
+        out[cls + ".private"] = _members(body.split("private:")[1])
+    out["LossFunction.pure_virtual_Evaluate"] = PURE_EVALUATE in src["loss"]
+    solve = r"virtual bool Solve\([^()]*\) = 0;"
+    for ns in ("mdm", "rem"):
+        text = src[ns + "_solver"]
+        out[ns + ".Solve"] = _signature(text, solve)
+        out[ns + ".SetLossFunction"] = bool(
+            re.search(r"void SetLossFunction\(const std::shared_ptr<LossFunction>& loss_function\)", text))
+        out[ns + ".SetMultiThreadExecutor"] = bool(
+            re.search(r"void SetMultiThreadExecutor\( ?const std::shared_ptr<MultiThreadExecutor>& multi_thread_executor\)", text))
+        out[ns + ".mentions_SetMultiThreadExecutor"] = "SetMultiThreadExecutor" in text
+        out[ns + ".loss_function_"] = "std::shared_ptr<LossFunction> loss_function_{nullptr};" in text
+        out[ns + ".multi_thread_executor_"] = "std::shared_ptr<MultiThreadExecutor> multi_thread_executor_{nullptr};" in text
+    out["pgo.ConstraintType"] = _enum(src["pgo_types"], "ConstraintType")
+    out["pgo.Constraint"] = _members(_block(src["pgo_types"], r"struct Constraint\s*"))
+    out["pgo.PoseParameter"] = re.sub(r"\s+", "", _block(src["pgo"], r"struct PoseParameter\s*"))
+    return out
+
+
+def reference_surface(reference_dir):
+    """public_surface() of the reference's headers under reference_dir (its nonlinear_optimizer/ directory)."""
+    return public_surface({k: _clean(os.path.join(reference_dir, v)) for k, v in REFERENCE_HEADERS.items()})
+
+
+def mirror_surface():
+    text = _clean(MIRROR)
+    mdm = _block(text, r"namespace mahalanobis_distance_minimizer\s*")
+    rem = _block(text, r"namespace reprojection_error_minimizer\s*")
+    pgo = _block(text, r"namespace pose_graph_optimizer\s*")
+    return public_surface({"options": text, "loss": text, "mdm_types": mdm, "mdm_solver": mdm, "rem_types": rem,
+                           "rem_solver": rem, "pgo_types": pgo, "pgo": pgo})
+
+
+@pytest.fixture(scope="module")
+def ref():
+    return json.load(open(GOLDEN))["sha256"]
+
+
 @pytest.fixture(scope="module")
 def mirror():
-    return _clean(MIRROR)
+    return mirror_surface()
 
 
-def test_options_and_enums(mirror):
-    ref = _clean(os.path.join(REF, "options.h"))
-    assert _members(_block(ref, r"struct Options\s*")) == _members(_block(mirror, r"struct Options\s*"))
-    assert len(_members(_block(ref, r"struct Options\s*"))) == 8  # 3 + 3 + 2: the parser saw all of them
-    for e in ("MinimizerType", "LinearSolverType"):
-        assert _enum(ref, e) == _enum(mirror, e)
+def _same(ref, mirror, *keys):
+    got = fingerprints({k: mirror[k] for k in keys})
+    for k in keys:
+        assert got[k] == ref[k], (k, mirror[k])
 
 
-def test_ndt_and_correspondence_records(mirror):
-    mdm = _clean(os.path.join(REF, "mahalanobis_distance_minimizer", "types.h"))
-    rem = _clean(os.path.join(REF, "reprojection_error_minimizer", "types.h"))
-    mirror_mdm = _block(mirror, r"namespace mahalanobis_distance_minimizer\s*")
-    mirror_rem = _block(mirror, r"namespace reprojection_error_minimizer\s*")
-    want = _members(_block(mdm, r"struct NDT\s*"))
-    assert [n for _, n, _ in want] == ["count", "sum", "moment", "mean", "information", "sqrt_information", "is_valid", "is_planar"]
-    assert want == _members(_block(mirror_mdm, r"struct NDT\s*"))
-    # `NDT ndt;` has no initialiser: compare the whole member list textually
-    ref_c = re.sub(r"\s+", "", _block(mdm, r"struct Correspondence\s*"))
-    assert ref_c == re.sub(r"\s+", "", _block(mirror_mdm, r"struct Correspondence\s*")) == "Vec3point{Vec3::Zero()};NDTndt;"
-    assert _members(_block(rem, r"struct CameraIntrinsics\s*")) == _members(_block(mirror_rem, r"struct CameraIntrinsics\s*"))
-    assert len(_members(_block(rem, r"struct CameraIntrinsics\s*"))) == 8
-    assert _members(_block(rem, r"struct Correspondence\s*")) == _members(_block(mirror_rem, r"struct Correspondence\s*"))
+def test_options_and_enums(ref, mirror):
+    _same(ref, mirror, "Options", "MinimizerType", "LinearSolverType")
+    assert len(mirror["Options"]) == 8  # 3 + 3 + 2: the parser saw all of them
 
 
-def test_loss_functions(mirror):
-    ref = _clean(os.path.join(REF, "loss_function.h"))
-    for cls in ("ExponentialLossFunction", "HuberLossFunction"):
-        rb, mb = _block(ref, r"class " + cls + r"\s*:\s*public LossFunction\s*"), _block(mirror, r"class " + cls + r"\s*:\s*public LossFunction\s*")
-        # constructor parameter list
-        rc = re.search(cls + r"\(([^()]*)\)", rb).group(1)
-        mc = re.search(cls + r"\(([^()]*)\)", mb).group(1)
-        assert re.sub(r"\s+", " ", rc) == re.sub(r"\s+", " ", mc)
-        # the scalar Evaluate body, statement for statement
-        r_eval = _block(rb, r"void Evaluate\(const double squared_residual, double output\[\d\]\) final\s*")
-        m_eval = _block(mb, r"void Evaluate\(const double squared_residual, double output\[\d\]\) final\s*")
-        assert re.sub(r"\s+", "", r_eval) == re.sub(r"\s+", "", m_eval), cls
-        # argument checks: same conditions, same exception type and message
-        assert re.findall(r"if \(([^()]*)\)\s*throw (std::\w+)\(\"([^\"]*)\"\)", rb) == \
-            re.findall(r"if \(([^()]*)\)\s*throw (std::\w+)\(\"([^\"]*)\"\)", mb)
-        # private data members
-        assert _members(rb.split("private:")[1]) == _members(mb.split("private:")[1])
-    assert "virtual void Evaluate(const double squared_residual, double* output) = 0;" in ref
-    assert "virtual void Evaluate(const double squared_residual, double* output) = 0;" in mirror
+def test_ndt_and_correspondence_records(ref, mirror):
+    assert [n for _, n, _ in mirror["mdm.NDT"]] == ["count", "sum", "moment", "mean", "information", "sqrt_information",
+                                                    "is_valid", "is_planar"]
+    _same(ref, mirror, "mdm.NDT", "mdm.Correspondence", "rem.CameraIntrinsics", "rem.Correspondence")
+    assert mirror["mdm.Correspondence"] == "Vec3point{Vec3::Zero()};NDTndt;"
+    assert len(mirror["rem.CameraIntrinsics"]) == 8
 
 
-def test_solver_base_classes(mirror):
-    mdm = _clean(os.path.join(REF, "mahalanobis_distance_minimizer", "mahalanobis_distance_minimizer.h"))
-    rem = _clean(os.path.join(REF, "reprojection_error_minimizer", "reprojection_error_minimizer.h"))
-    mirror_mdm = _block(mirror, r"namespace mahalanobis_distance_minimizer\s*")
-    mirror_rem = _block(mirror, r"namespace reprojection_error_minimizer\s*")
-    solve = r"virtual bool Solve\([^()]*\) = 0;"
-    assert _signature(mdm, solve) == _signature(mirror_mdm, solve) == \
+def test_loss_functions(ref, mirror):
+    for cls in LOSS_CLASSES:
+        _same(ref, mirror, *(cls + s for s in (".constructor", ".Evaluate", ".checks", ".private")))
+    _same(ref, mirror, "LossFunction.pure_virtual_Evaluate")
+    assert mirror["LossFunction.pure_virtual_Evaluate"] is True
+
+
+def test_solver_base_classes(ref, mirror):
+    _same(ref, mirror, "mdm.Solve", "rem.Solve", "mdm.SetLossFunction", "rem.SetLossFunction", "mdm.SetMultiThreadExecutor",
+          "mdm.loss_function_", "mdm.multi_thread_executor_", "rem.mentions_SetMultiThreadExecutor")
+    assert mirror["mdm.Solve"] == \
         "virtual bool Solve(const Options& options, const std::vector<Correspondence>& correspondences, Pose* pose) = 0;"
-    assert _signature(rem, solve) == _signature(mirror_rem, solve)
-    assert "const CameraIntrinsics& camera_intrinsics, Pose* pose" in _signature(rem, solve)
-    for text in (mdm, mirror_mdm, rem, mirror_rem):
-        assert re.search(r"void SetLossFunction\(const std::shared_ptr<LossFunction>& loss_function\)", text)
-    for text in (mdm, mirror_mdm):
-        assert re.search(r"void SetMultiThreadExecutor\( ?const std::shared_ptr<MultiThreadExecutor>& multi_thread_executor\)", text)
-        assert "std::shared_ptr<LossFunction> loss_function_{nullptr};" in text
-        assert "std::shared_ptr<MultiThreadExecutor> multi_thread_executor_{nullptr};" in text
-    assert "SetMultiThreadExecutor" not in rem and "SetMultiThreadExecutor" not in mirror_rem  # the reference has none there
+    assert "const CameraIntrinsics& camera_intrinsics, Pose* pose" in mirror["rem.Solve"]
+    assert mirror["mdm.SetLossFunction"] and mirror["rem.SetLossFunction"]
+    assert mirror["mdm.SetMultiThreadExecutor"] and mirror["mdm.loss_function_"] and mirror["mdm.multi_thread_executor_"]
+    assert not mirror["rem.mentions_SetMultiThreadExecutor"]  # the reference has none there
 
 
-def test_pose_graph_records(mirror):
-    types = _clean(os.path.join(REF, "pose_graph_optimizer", "types.h"))
-    pgo = _clean(os.path.join(REF, "pose_graph_optimizer", "pose_graph_optimizer.h"))
-    mirror_pgo = _block(mirror, r"namespace pose_graph_optimizer\s*")
-    assert _enum(types, "ConstraintType") == _enum(mirror_pgo, "ConstraintType")
-    assert _members(_block(types, r"struct Constraint\s*")) == _members(_block(mirror_pgo, r"struct Constraint\s*"))
-    assert re.sub(r"\s+", "", _block(pgo, r"struct PoseParameter\s*")) == re.sub(r"\s+", "", _block(mirror_pgo, r"struct PoseParameter\s*"))
+def test_pose_graph_records(ref, mirror):
+    _same(ref, mirror, "pgo.ConstraintType", "pgo.Constraint", "pgo.PoseParameter")

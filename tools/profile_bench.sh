@@ -11,7 +11,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=gpurun_out
 CASES=${1:-"ndt6:f64 ndt6:f32 ndt3:f64 reproj:f64 ndt6:f64:stream ndt6:f32:stream reproj:f64:stream reproj:f32:stream"}
-COMMON="--no-cpu-baseline --no-strong-baseline --no-cold --no-other-configs"
+COMMON="--full --no-cpu-baseline --no-strong-baseline --no-cold --no-other-configs"
 SQ="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU"
 for c in $CASES; do
   # problem:dtype[:stream]  — "stream" = NOS_LM_CLUSTER=0: the launch-per-iteration (streaming) kernel instead of the resident solve

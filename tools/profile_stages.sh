@@ -23,7 +23,7 @@ for s in $STAGES; do
     pgo) CMD="tools/measure_pgo.py 1000000" ;;
     match) CMD="tools/measure_matcher.py 10000000" ;;
     mapbuild) CMD="tools/measure_mapbuild.py" ;;
-    indexed) CMD="bench.py --layout indexed --steps 40 --warmup 10 --repeats 3 --no-cpu-baseline --no-strong-baseline --no-cold --no-other-configs" ;;
+    indexed) CMD="bench.py --layout indexed --steps 40 --warmup 10 --repeats 3 --full --no-cpu-baseline --no-strong-baseline --no-cold --no-other-configs" ;;
     *) echo "unknown stage $s"; exit 2 ;;
   esac
   B=$OUT/prof_${TAG}_${s}
