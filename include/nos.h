@@ -184,8 +184,10 @@ int nos_reproj_dataset_create_from_records(nos_ctx* ctx, size_t n, const void* r
 int nos_dataset_destroy(nos_dataset* ds);
 size_t nos_dataset_size(const nos_dataset* ds);
 int nos_dataset_dtype(const nos_dataset* ds);
-/* Algorithmic bytes one accumulate pass streams from HBM for this dataset
- * (n × planes × sizeof(element)); the figure roofline numbers are quoted against. */
+/* Bytes of the dataset's correspondences as the caller gives them: n × planes × sizeof(element).  Flat NDT datasets
+ * also store A = SᵀS of every sqrt-information (computed on the device when the dataset is made), and the 6-DoF and fp64
+ * 3-DoF kernels stream p, mu and A only — 12 of these 15 planes' worth (96 / 48 B per fp64 / fp32 correspondence), so
+ * a pass moves 0.8 × this figure; the fp32 3-DoF kernels stream p, mu and S (all 15). */
 size_t nos_dataset_stream_bytes(const nos_dataset* ds);
 
 /* Semantics of the reference's fp32 ("SIMD") solver classes for solves and accumulates on this dataset (0 = off, the

@@ -26,6 +26,10 @@ enum LossKind : int { kLossNone = 0, kLossExponential = 1, kLossHuber = 2 };
 // Tiled SoA addressing.  Correspondence i, field f lives at element offset
 //   (i >> tile_shift) * tile_stride + f * field_stride + (i & (tile - 1)).
 // tile == n_padded, tile_stride == 0 gives a plain planar layout.
+// Flat NDT datasets store 21 planes: the 12 the kernels stream — p (3), mu (3), A = SᵀS (a00 a01 a02 a11 a12 a22) — in
+// the layout above, then the 9 planes of S (row-major) in a second region of the same allocation, laid out alike:
+//   s_offset + (i >> tile_shift) * s_tile_stride + k * field_stride + (i & (tile - 1)),
+// so that a pass over the streamed planes never touches S (nos_dataset_download and the fp32 3-DoF item read it).
 struct TiledLayout {
   const void* base;
   uint64_t n;            // real correspondences
@@ -34,7 +38,30 @@ struct TiledLayout {
   uint64_t field_stride; // elements between consecutive fields inside a tile
   uint32_t tile_shift;   // log2(tile)
   uint32_t tile_mask;    // tile - 1
+  uint64_t s_offset;     // flat NDT: element offset of the S region
+  uint64_t s_tile_stride;  // flat NDT: elements between consecutive tiles of the S region
 };
+
+constexpr int kNdtStreamed = 12;  // planes of a flat NDT dataset the kernels stream: p, mu, A
+constexpr int kNdtStored = 21;    // and the 9 planes of S behind them
+// stored plane of plane f of the caller's view (p, mu, S row-major: the 15 planes of nos.h)
+__host__ __device__ constexpr int ndt_stored_plane(int f) { return f < 6 ? f : f + 6; }
+// element offset of stored plane f (0 … 20; reprojection and voxel-indexed datasets: their own planes, all < 12) of item i
+__host__ __device__ inline uint64_t plane_offset(const TiledLayout& L, uint64_t i, int f) {
+  if (f < kNdtStreamed) return (i >> L.tile_shift) * L.tile_stride + uint64_t(f) * L.field_stride + (i & L.tile_mask);
+  return L.s_offset + (i >> L.tile_shift) * L.s_tile_stride + uint64_t(f - kNdtStreamed) * L.field_stride + (i & L.tile_mask);
+}
+// A = SᵀS of a row-major sqrt-information, in the element type of the dataset:
+//   A(a, b) = S(0,a) S(0,b) + S(1,a) S(1,b) + S(2,a) S(2,b)  as fma(S0a, S0b, fma(S1a, S1b, S2a * S2b)),
+// the expression the fp32 item and the resident fp64 form used when they converted S on the fly; a00 a01 a02 a11 a12 a22
+template <typename T>
+__device__ __forceinline__ void sqrt_info_to_A(const T (&S)[9], T (&A)[6]) {
+  int q = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = a; b < 3; ++b) A[q++] = fma(S[a], S[b], fma(S[3 + a], S[3 + b], S[6 + a] * S[6 + b]));
+}
 
 template <typename T>
 struct Ndt6Params {
@@ -211,36 +238,6 @@ __device__ __forceinline__ void loss_eval_v(V s, typename Lanes<V>::S la, typena
   }
 }
 
-// acc += w * JᵀJ (upper), w * Jᵀr for a ROWS×6 Jacobian held as J[row][6].
-template <typename V, int ROWS>
-__device__ __forceinline__ void rank_update6(const V (&J)[ROWS][6], const V (&r)[ROWS], V w,
-                                             V rho, V (&acc)[28]) {
-  V wJ[ROWS][6];
-#pragma unroll
-  for (int a = 0; a < ROWS; ++a)
-#pragma unroll
-    for (int c = 0; c < 6; ++c) wJ[a][c] = w * J[a][c];
-  int k = 0;
-#pragma unroll
-  for (int row = 0; row < 6; ++row)
-#pragma unroll
-    for (int col = row; col < 6; ++col) {
-      V h = acc[k];
-#pragma unroll
-      for (int a = 0; a < ROWS; ++a) h = vfma<V>(wJ[a][row], J[a][col], h);
-      acc[k] = h;
-      ++k;
-    }
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    V gsum = acc[21 + c];
-#pragma unroll
-    for (int a = 0; a < ROWS; ++a) gsum = vfma<V>(wJ[a][c], r[a], gsum);
-    acc[21 + c] = gsum;
-  }
-  acc[27] += rho;
-}
-
 // M = -R [p]x, column form of ..._analytic_simd_various.cc:677-687.
 template <typename V>
 __device__ __forceinline__ void minus_R_hat(const typename Lanes<V>::S (&R)[9], V px, V py, V pz, V (&M)[3][3]) {
@@ -256,29 +253,38 @@ __device__ __forceinline__ void minus_R_hat(const typename Lanes<V>::S (&R)[9], 
 
 template <typename T, int LOSS>
 struct Ndt6Problem {
-  static constexpr int kFields = 15;
+  static constexpr int kFields = kNdtStreamed;  // planes an item reads: p, mu, A (see TiledLayout)
+  static constexpr int kPlanes = 15;            // planes of a correspondence as the caller gives it (p, mu, S)
+  static constexpr bool kSPlanes = false;       // reads S instead of A (Ndt3Problem<float>)
   static constexpr int kOut = 28;
   using Params = Ndt6Params<T>;
-  // x = {p(3), mu(3), S row-major (9)}; V = T (one correspondence) or float2_t (two, fp32 only)
+  // x = {p(3), mu(3), A = SᵀS (a00 a01 a02 a11 a12 a22)}; V = T (one correspondence) or float2_t (two, fp32 only)
   template <typename V = T>
-  __device__ static __forceinline__ void item(const V (&x)[15], const Params& P, const bool (&)[Lanes<V>::n] /*valid*/,
-                                              V (&acc)[28]) {
-    V e[3], r[3], M[3][3], J[3][6];
+  __device__ static __forceinline__ void item(const V (&x)[kNdtStreamed], const Params& P,
+                                              const bool (&)[Lanes<V>::n] /*valid*/, V (&acc)[28]) {
+    if constexpr (sizeof(typename Lanes<V>::S) == 8) {
+      // fp64: the A form below (zero-padded records have A = 0 → s = 0, H = g = 0, rho(0) = 0: no mask needed)
+      const T p3[3] = {x[0], x[1], x[2]}, mu3[3] = {x[3], x[4], x[5]};
+      const T A6[6] = {x[6], x[7], x[8], x[9], x[10], x[11]};
+      item_A(p3, mu3, A6, P, acc);
+    } else {
+      V e[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const V pw = sfma<V>(P.R[3 * i], x[0], sfma<V>(P.R[3 * i + 1], x[1], sfma<V>(P.R[3 * i + 2], x[2], splat<V>(P.t[i]))));
-      e[i] = pw - x[3 + i];
-    }
-    if constexpr (sizeof(typename Lanes<V>::S) == 4) {
-      // fp32: A = SᵀS first, then H = w [I|M]ᵀ A [I|M], g = w [I|M]ᵀ A e, s = eᵀ A e — ≈ 150 instead of ≈ 186 operations
-      // per correspondence, the same sums.  Measured error against the fp64 oracle unchanged (1.09e-6 against 1.07e-6
-      // scaled, of which 1.0e-6 is the rounding of the inputs; profiles/r02_fp32_error.jsonl), 2.5 % faster at 10 M.
-      V A[3][3], Ae[3], wAe[3], B[3][3];
+      for (int i = 0; i < 3; ++i) {
+        const V pw = sfma<V>(P.R[3 * i], x[0], sfma<V>(P.R[3 * i + 1], x[1], sfma<V>(P.R[3 * i + 2], x[2], splat<V>(P.t[i]))));
+        e[i] = pw - x[3 + i];
+      }
+      // fp32: H = w [I|M]ᵀ A [I|M], g = w [I|M]ᵀ A e, s = eᵀ A e from the stored A — ≈ 150 instead of ≈ 186 operations
+      // per correspondence of the S form, the same sums.  Measured error against the fp64 oracle unchanged (1.09e-6 against
+      // 1.07e-6 scaled, of which 1.0e-6 is the rounding of the inputs; profiles/r02_fp32_error.jsonl).  A is computed
+      // from the fp32-rounded S when the dataset is made, with the expression this item used on every pass before.
+      V A[3][3], Ae[3], wAe[3], B[3][3], M[3][3];
+      int q = 6;
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = i; j < 3; ++j) {
-          A[i][j] = vfma<V>(x[6 + i], x[6 + j], vfma<V>(x[9 + i], x[9 + j], x[12 + i] * x[12 + j]));
+          A[i][j] = x[q++];
           A[j][i] = A[i][j];
         }
 #pragma unroll
@@ -323,33 +329,16 @@ struct Ndt6Problem {
           ++k;
         }
       acc[27] += rho2;
-      return;
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-      r[a] = vfma<V>(x[6 + 3 * a], e[0], vfma<V>(x[7 + 3 * a], e[1], x[8 + 3 * a] * e[2]));
-    minus_R_hat<V>(P.R, x[0], x[1], x[2], M);
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b) {
-        J[a][b] = x[6 + 3 * a + b];
-        J[a][3 + b] = vfma<V>(x[6 + 3 * a], M[0][b], vfma<V>(x[7 + 3 * a], M[1][b], x[8 + 3 * a] * M[2][b]));
-      }
-    const V s = vfma<V>(r[0], r[0], vfma<V>(r[1], r[1], r[2] * r[2]));
-    V rho, w;
-    loss_eval_v<V, LOSS>(s, P.la, P.lb, P.lc, rho, w);
-    // zero-padded records have S = 0 → r = 0, J = 0, rho(0) = 0: no mask needed
-    rank_update6<V, 3>(J, r, w, rho, acc);
   }
-  __device__ static __forceinline__ void item(const T (&x)[15], const Params& P, bool valid, T (&acc)[28]) {
+  __device__ static __forceinline__ void item(const T (&x)[kNdtStreamed], const Params& P, bool valid, T (&acc)[28]) {
     const bool v1[1] = {valid};
     item<T>(x, P, v1, acc);
   }
 
-  // Voxel-indexed form: the voxel table holds A = SᵀS (a00 a01 a02 a11 a12 a22) instead of S.  With J = [S | S M]:
+  // The A form (flat datasets store A = SᵀS, the voxel table of the indexed layout too).  With J = [S | S M]:
   //   s = rᵀr = eᵀAe,  g = w [A e ; Mᵀ A e],  H = w [A, A M ; · , Mᵀ A M]
-  // — ≈ 144 instead of ≈ 190 operations per correspondence, 9 instead of 12 values per voxel record.
+  // — ≈ 144 instead of ≈ 190 operations per correspondence, 12 instead of 15 values per flat record.
   __device__ static __forceinline__ void item_A(const T (&p)[3], const T (&mu)[3], const T (&A)[6], const Params& P,
                                                 T (&acc)[28]) {
     T e[3], Ae[3], M[3][3], B[3][3];
@@ -408,12 +397,26 @@ struct Ndt6Problem {
 
 template <typename T, int LOSS>
 struct Ndt3Problem {
-  static constexpr int kFields = 15;
+  // fp64: p, mu, A (item_A).  fp32 keeps the S form — p, mu and S (row-major) — and reads S from the dataset's S region:
+  // its sums are pinned to the printed digit (tests/test_simd_class.py)
+  static constexpr bool kSPlanes = sizeof(T) == 4;
+  static constexpr int kFields = kSPlanes ? 15 : kNdtStreamed;
+  static constexpr int kPlanes = 15;
   static constexpr int kOut = 10;
   using Params = Ndt3Params<T>;
   template <typename V = T>
-  __device__ static __forceinline__ void item(const V (&x)[15], const Params& P, const bool (&)[Lanes<V>::n] /*valid*/,
+  __device__ static __forceinline__ void item(const V (&x)[kFields], const Params& P, const bool (&)[Lanes<V>::n] /*valid*/,
                                               V (&acc)[10]) {
+    if constexpr (!kSPlanes) {
+      const T p3[3] = {x[0], x[1], x[2]}, mu3[3] = {x[3], x[4], x[5]};
+      const T A6[6] = {x[6], x[7], x[8], x[9], x[10], x[11]};
+      item_A(p3, mu3, A6, P, acc);
+    } else {
+      item_S<V>(x, P, acc);
+    }
+  }
+  template <typename V>
+  __device__ static __forceinline__ void item_S(const V (&x)[15], const Params& P, V (&acc)[10]) {
     V e[3], r[3], J[3][3];
     const V ux = x[0], uy = x[1];
     e[0] = sfma<V>(P.R2[0], ux, sfma<V>(P.R2[1], uy, splat<V>(P.t2[0]))) - x[3];
@@ -449,12 +452,12 @@ struct Ndt3Problem {
       acc[6 + c] = vfma<V>(wJ[0][c], r[0], vfma<V>(wJ[1][c], r[1], vfma<V>(wJ[2][c], r[2], acc[6 + c])));
     acc[9] += rho;
   }
-  __device__ static __forceinline__ void item(const T (&x)[15], const Params& P, bool valid, T (&acc)[10]) {
+  __device__ static __forceinline__ void item(const T (&x)[kFields], const Params& P, bool valid, T (&acc)[10]) {
     const bool v1[1] = {valid};
     item<T>(x, P, v1, acc);
   }
 
-  // Voxel-indexed form with A = SᵀS: J = [S(:,0) S(:,1) S(:,0:2)·d] ⇒ JᵀJ = [[a00, a01, q0], [·, a11, q1], [·, ·, dᵀq]]
+  // A form (flat fp64 datasets, the voxel table of the indexed layout) with A = SᵀS: J = [S(:,0) S(:,1) S(:,0:2)·d] ⇒ JᵀJ = [[a00, a01, q0], [·, a11, q1], [·, ·, dᵀq]]
   // with q = A(0:2,0:2)·d, and Jᵀr = [Ae₀, Ae₁, d·(Ae)(0:2)].
   __device__ static __forceinline__ void item_A(const T (&p)[3], const T (&mu)[3], const T (&A)[6], const Params& P,
                                                 T (&acc)[10]) {
@@ -490,6 +493,8 @@ struct Ndt3Problem {
 template <typename T, int LOSS>
 struct ReprojProblem {
   static constexpr int kFields = 5;
+  static constexpr int kPlanes = 5;
+  static constexpr bool kSPlanes = false;
   static constexpr int kOut = 28;
   using Params = ReprojParams<T>;
   // x = {X(3), pixel(2)}; V = T or float2_t
@@ -590,5 +595,14 @@ struct ReprojProblem {
     item<T>(x, P, v1, acc);
   }
 };
+
+// Element offset of field f (the problem's numbering) of item i, whose offset in the streamed region is `off`: the
+// problems that read S (kSPlanes) find fields 6 … 14 in the S region of the flat NDT layout.
+template <typename Problem>
+__device__ __forceinline__ uint64_t field_offset(const TiledLayout& L, uint64_t i, uint64_t off, int f) {
+  if constexpr (Problem::kSPlanes)
+    if (f >= 6) return plane_offset(L, i, ndt_stored_plane(f));
+  return off + uint64_t(f) * L.field_stride;
+}
 
 }  // namespace nos

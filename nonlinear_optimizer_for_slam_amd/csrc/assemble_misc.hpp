@@ -94,7 +94,21 @@ __global__ __launch_bounds__(1024) void final_reduce_kernel(const double* __rest
 
 // ---------------------------------------------------------------- ingestion kernels
 
-// planar source planes (15 or 5 pointers, element type SRC) → tiled layout of DST, zero pads.
+// One flat NDT record (p, mu, S row-major, already in the dataset's element type) → its 21 stored planes: p, mu, S and
+// A = SᵀS computed from the stored S (sqrt_info_to_A).  An all-zero record stores all zeros.
+template <typename DST>
+__device__ __forceinline__ void store_ndt_record(const TiledLayout& L, DST* __restrict__ dst, uint64_t i, const DST (&x)[15]) {
+  DST S[9], A[6];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) S[k] = x[6 + k];
+  sqrt_info_to_A<DST>(S, A);
+#pragma unroll
+  for (int f = 0; f < 15; ++f) dst[plane_offset(L, i, ndt_stored_plane(f))] = x[f];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) dst[plane_offset(L, i, 6 + k)] = A[k];
+}
+
+// planar source planes (5 pointers, element type SRC) → tiled layout of DST, zero pads (reprojection).
 struct PlanePtrs {
   const void* p[15];
 };
@@ -111,8 +125,19 @@ __global__ __launch_bounds__(256) void retile_kernel(PlanePtrs src, int n_fields
   dst[off] = v;
 }
 
-// array-of-structures records (double fields at byte offsets) → tiled layout.
-// `first` is the index of records[0] inside the dataset; count records are unpacked.
+// the 15 planar source planes of flat NDT (element type SRC) → the 21 stored planes of DST, one item per thread, pads zero
+template <typename SRC, typename DST>
+__global__ __launch_bounds__(256) void retile_ndt_kernel(PlanePtrs src, TiledLayout L, DST* __restrict__ dst) {
+  const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= L.n_padded) return;
+  DST x[15];
+#pragma unroll
+  for (int f = 0; f < 15; ++f) x[f] = i < L.n ? DST(static_cast<const SRC*>(src.p[f])[i]) : DST(0);
+  store_ndt_record<DST>(L, dst, i, x);
+}
+
+// array-of-structures records (double fields at byte offsets) → tiled layout (flat NDT, n_fields = 15: the 21 stored
+// planes).  `first` is the index of records[0] inside the dataset; count records are unpacked.
 struct FieldOffsets {
   uint32_t off[15];
 };
@@ -127,6 +152,13 @@ __global__ __launch_bounds__(256) void unpack_records_kernel(const unsigned char
   if (j >= count) return;
   const unsigned char* rec = records + j * stride_bytes;
   const uint64_t i = first + j;
+  if (n_fields == 15) {  // grid-uniform
+    DST x[15];
+#pragma unroll
+    for (int f = 0; f < 15; ++f) x[f] = DST(*reinterpret_cast<const double*>(rec + fo.off[f]));
+    store_ndt_record<DST>(L, dst, i, x);
+    return;
+  }
   const uint64_t o = (i >> L.tile_shift) * L.tile_stride + (i & L.tile_mask);
   for (int f = 0; f < n_fields; ++f) {
     const double v = *reinterpret_cast<const double*>(rec + fo.off[f]);
@@ -134,12 +166,27 @@ __global__ __launch_bounds__(256) void unpack_records_kernel(const unsigned char
   }
 }
 
+// The A planes of items [first, first + count) of a flat NDT dataset from its stored S (the host-pack ingestion copies
+// p, mu and S into place; A is computed here, on the device, in the element type of the dataset).
+template <typename T>
+__global__ __launch_bounds__(256) void ndt_a_planes_kernel(TiledLayout L, T* __restrict__ dst, uint64_t first, uint64_t count) {
+  const uint64_t j = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (j >= count) return;
+  const uint64_t i = first + j;
+  T S[9], A[6];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) S[k] = dst[plane_offset(L, i, kNdtStreamed + k)];
+  sqrt_info_to_A<T>(S, A);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) dst[plane_offset(L, i, 6 + k)] = A[k];
+}
+
+// n_fields: stored planes (flat NDT: 21)
 template <typename DST>
 __global__ __launch_bounds__(256) void zero_pad_kernel(int n_fields, TiledLayout L, DST* __restrict__ dst) {
   const uint64_t i = L.n + uint64_t(blockIdx.x) * 256 + threadIdx.x;
   if (i >= L.n_padded) return;
-  const uint64_t o = (i >> L.tile_shift) * L.tile_stride + (i & L.tile_mask);
-  for (int f = 0; f < n_fields; ++f) dst[o + uint64_t(f) * L.field_stride] = DST(0);
+  for (int f = 0; f < n_fields; ++f) dst[plane_offset(L, i, f)] = DST(0);
 }
 
 }  // namespace nos

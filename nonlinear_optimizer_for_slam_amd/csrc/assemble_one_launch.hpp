@@ -17,7 +17,7 @@ namespace nos {
 // One CU evaluates a 512-correspondence NDT chunk in ≈ 0.9 µs, so the single-workgroup form only pays while the whole
 // pass stays below the ≈ 6 µs that a launch with its hand-off costs: measured 11.3 → 5.3 µs per iteration at 630
 // reprojection points, but no gain at 2 900 NDT correspondences (6 chunks) — hence a budget in plane-elements.
-constexpr size_t kSingleBlockMaxElements = size_t(1024) * 15;  // n × fields: 1024 NDT or 3072 reprojection correspondences
+constexpr size_t kSingleBlockMaxElements = size_t(1024) * 15;  // n × planes (nos.h): 1024 NDT or 3072 reprojection correspondences
 
 template <typename Problem, typename T, int BLOCK, bool NT = false>
 __global__ __launch_bounds__(BLOCK) void solve_single_block_kernel(TiledLayout L, typename Problem::Params P,
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(BLOCK) void solve_single_block_kernel(TiledLayout L
     for (int k = 0; k < kOut; ++k) acc[k] = T(0);
     // several chunks per round, all their loads in flight before the first item is evaluated: with one workgroup there
     // are no other waves to hide the L2 latency behind
-    constexpr uint32_t kRound = (kF * sizeof(T) > 64) ? 2 : 4;  // 15 fp64 planes: two chunks fill the register file
+    constexpr uint32_t kRound = (kF * sizeof(T) > 64) ? 2 : 4;  // 12 fp64 planes: two chunks fill the register file
     for (uint32_t c = 0; c < n_chunks; c += kRound) {
       T x[kRound][kF][1];
       uint64_t i0[kRound];
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(BLOCK) void solve_single_block_kernel(TiledLayout L
         i0[u] = uint64_t(cu) * BLOCK + threadIdx.x;
         const uint64_t off = (i0[u] >> L.tile_shift) * L.tile_stride + (i0[u] & L.tile_mask);
 #pragma unroll
-        for (int f = 0; f < kF; ++f) load_items<T, 1, NT>(base + off + uint64_t(f) * L.field_stride, x[u][f]);
+        for (int f = 0; f < kF; ++f) load_items<T, 1, NT>(base + field_offset<Problem>(L, i0[u], off, f), x[u][f]);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -177,23 +177,20 @@ __device__ __forceinline__ void state_load_sc1(const LmDevice* lm, nos_host::LmS
 // How many correspondences a lane keeps resident for the whole solve: RI of them in REGISTERS (compile-time unrolled) and
 // up to LI more in LDS (dynamic allocation, [slot][field][lane] so that lanes read consecutive addresses).  One
 // 512-thread workgroup per CU → two waves per SIMD → 256 VGPRs per lane and ≈ 150 KB of the CU's 160 KB LDS:
-//   NDT fp64 (resident form 96 B / correspondence): 3 + 3 → 6 per lane → 786 432 correspondences on 256 CUs
-//   NDT fp32 (60 B, S kept)                        : 3 + 4 → 7         → 917 504
+//   NDT fp64 (96 B / correspondence: p, mu, A): 3 + 3 → 6 per lane → 786 432 correspondences on 256 CUs
+//   NDT fp32 (48 B; 3-DoF: 60 B, S kept)         : 3 + 4 → 7         → 917 504
 //   reprojection fp64 (40 B)          : 9 + 7 → 16        → 2 097 152  (BASELINE.json configs[2]: 2 M)
 //   reprojection fp32 (20 B)          : 10 + 14 → 24      → 3 145 728
 // i.e. at these sizes an LM iteration touches neither HBM nor the caches: its cost is the item math plus one grid-wide
 // hand-off.  The first touch (one pass over the dataset) is paid once per solve.
-// What a RESIDENT NDT correspondence consists of: the solvers only ever need A = SᵀS of the sqrt-information (with
-// J = [S | S M]: s = eᵀAe, g = w [Ae ; MᵀAe], H = w [A, AM ; ·, MᵀAM] — Ndt6Problem::item_A / Ndt3Problem::item_A), so a
-// correspondence that stays on chip for the whole solve is converted ONCE, at first touch, from {p, mu, S (9)} to
-// {p, mu, A (6)}: 12 values instead of 15 per item (more items fit) and ≈ 35 % fewer instructions per item and iteration
-// (fp64: 233 → ≈ 150).  Streamed data keeps the 15 planes: it is read
-// once per iteration, the conversion would cost more than it saves.
-// fp64 only: the fp32 item function already works from A and measured SLOWER through item_A (900 000: 8.57 → 9.24 µs).
-template <int FIELDS, size_t ELEM>
-constexpr int resident_fields() {
-  return (FIELDS == 15 && ELEM == 8) ? 12 : FIELDS;
-}
+// A resident NDT correspondence is what the dataset stores and the streamed form reads: {p, mu, A = SᵀS} — the solvers only
+// ever need A of the sqrt-information (with J = [S | S M]: s = eᵀAe, g = w [Ae ; MᵀAe], H = w [A, AM ; ·, MᵀAM] —
+// Ndt6Problem::item_A / Ndt3Problem::item_A).  A is computed ONCE, when the dataset is made (nos_core.hip), with the
+// expression the resident form used to apply at first touch: 12 values instead of 15 per item, ≈ 35 % fewer instructions
+// per item and iteration (fp64: 233 → ≈ 150), and 96 instead of 120 B per correspondence and iteration where the data is
+// streamed.  The fp32 3-DoF item keeps S (Ndt3Problem::kSPlanes).
+// The shape is chosen by the planes of the caller's record (Problem::kPlanes), so an fp32 item keeps the mapping of items to
+// lanes — and with it the order of the reduction — of the S form.
 template <int FIELDS, int ELEM>
 struct ResidentShape;
 template <>
@@ -226,8 +223,7 @@ __global__ __launch_bounds__(BLOCK) void solve_cluster_kernel(TiledLayout L, typ
   constexpr int kCols = 32;
   constexpr int kSlices = BLOCK / kCols;
   const T* __restrict__ base = static_cast<const T*>(L.base);
-  constexpr bool kAForm = kF == 15 && sizeof(T) == 8 && SI == 0;     // resident fp64 NDT items hold A = SᵀS (6) instead of S (9)
-  constexpr int kRF = kAForm ? resident_fields<kF, sizeof(T)>() : kF;  // values per resident item
+  constexpr int kRF = kF;  // values per resident item
   extern __shared__ __align__(16) unsigned char resident_raw[];  // [items_per_lane - RI][kRF][BLOCK] of T
   T* resident = reinterpret_cast<T*>(resident_raw);
   __shared__ int s_flag;  // 0 go on, 1 loop finished, 2 abort
@@ -256,38 +252,13 @@ __global__ __launch_bounds__(BLOCK) void solve_cluster_kernel(TiledLayout L, typ
     const uint64_t off = (ic >> L.tile_shift) * L.tile_stride + (ic & L.tile_mask);
     T xt[kF][1];
 #pragma unroll
-    for (int f = 0; f < kF; ++f) load_items<T, 1, false>(base + off + uint64_t(f) * L.field_stride, xt[f]);
-    if constexpr (kAForm) {
+    for (int f = 0; f < kF; ++f) load_items<T, 1, false>(base + field_offset<Problem>(L, ic, off, f), xt[f]);
 #pragma unroll
-      for (int f = 0; f < 6; ++f) dst[f] = ok ? xt[f][0] : T(0);
-      int q = 6;
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = a; b < 3; ++b) {  // A(a, b) = sum over rows k of S(k, a) S(k, b);  a00 a01 a02 a11 a12 a22
-          const T v = fma(xt[6 + a][0], xt[6 + b][0], fma(xt[9 + a][0], xt[9 + b][0], xt[12 + a][0] * xt[12 + b][0]));
-          dst[q++] = ok ? v : T(0);
-        }
-    } else {
-#pragma unroll
-      for (int f = 0; f < kF; ++f) dst[f] = ok ? xt[f][0] : T(0);
-    }
+    for (int f = 0; f < kF; ++f) dst[f] = ok ? xt[f][0] : T(0);
     return ok;
   };
-  // one resident item → the sums (NDT: the A form; reprojection: the item as it is)
-  auto evaluate_resident = [&](const T (&xi)[kRF], bool ok, T (&acc_)[kOut]) {
-    if constexpr (kAForm) {
-      const T p3[3] = {xi[0], xi[1], xi[2]}, mu3[3] = {xi[3], xi[4], xi[5]};
-      const T A6[6] = {xi[6], xi[7], xi[8], xi[9], xi[10], xi[11]};
-      (void)ok;  // pads are all-zero records: they contribute exactly nothing
-      Problem::item_A(p3, mu3, A6, P, acc_);
-    } else {
-      T xf[kF];
-#pragma unroll
-      for (int f = 0; f < kF; ++f) xf[f] = xi[f < kRF ? f : 0];
-      Problem::item(xf, P, ok, acc_);
-    }
-  };
+  // one resident item → the sums (pads are all-zero records: they contribute exactly nothing)
+  auto evaluate_resident = [&](const T (&xi)[kRF], bool ok, T (&acc_)[kOut]) { Problem::item(xi, P, ok, acc_); };
   T x[RI > 0 ? RI : 1][kRF];
   bool valid[RI > 0 ? RI : 1];
   static_assert(SI == 0 || (RI == 0 && LI == 0), "the streaming form keeps nothing resident");
@@ -298,7 +269,7 @@ __global__ __launch_bounds__(BLOCK) void solve_cluster_kernel(TiledLayout L, typ
     const uint64_t i0 = uint64_t(c) * (uint64_t(BLOCK) * (SI > 0 ? SI : 1)) + uint64_t(threadIdx.x) * (SI > 0 ? SI : 1);
     const uint64_t off = (i0 >> L.tile_shift) * L.tile_stride + (i0 & L.tile_mask);
 #pragma unroll
-    for (int f = 0; f < kF; ++f) load_items<T, (SI > 0 ? SI : 1), NT>(base + off + uint64_t(f) * L.field_stride, dst[f]);
+    for (int f = 0; f < kF; ++f) load_items<T, (SI > 0 ? SI : 1), NT>(base + field_offset<Problem>(L, i0, off, f), dst[f]);
     return i0;
   };
   if constexpr (SI > 0) {

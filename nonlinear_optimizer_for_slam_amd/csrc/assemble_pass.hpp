@@ -50,7 +50,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void assemble_kernel(TiledLayout L,
     auto issue = [&](uint32_t cc, T (&dst)[kF][ITEMS], uint64_t& i0) {
       const uint64_t off = chunk_offset(cc, i0);
 #pragma unroll
-      for (int f = 0; f < kF; ++f) load_items<T, ITEMS, NT>(base + off + uint64_t(f) * L.field_stride, dst[f]);
+      for (int f = 0; f < kF; ++f) load_items<T, ITEMS, NT>(base + field_offset<Problem>(L, i0, off, f), dst[f]);
     };
     auto evaluate = [&](const T (&src)[kF][ITEMS], uint64_t i0) {
 #pragma unroll
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void assemble_kernel(TiledLayout L,
       if (live) {
         const uint64_t off = chunk_offset(c, i0);
 #pragma unroll
-        for (int f = 0; f < kF; ++f) load_items<T, ITEMS, NT>(base + off + uint64_t(f) * L.field_stride, x[f]);
+        for (int f = 0; f < kF; ++f) load_items<T, ITEMS, NT>(base + field_offset<Problem>(L, i0, off, f), x[f]);
       }
       // All loads of the chunk go out before any of the item math: the machine scheduler otherwise interleaves them
       // with their uses in groups of 4-6 (seen in the ISA), which cuts the bytes a wave keeps in flight and costs ≈ 7 %

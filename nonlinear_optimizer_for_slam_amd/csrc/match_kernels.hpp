@@ -178,33 +178,33 @@ __global__ __launch_bounds__(256) void match_kernel(MapView map, const double* _
     const uint32_t (&best_j)[2] = best.j;
     // two consecutive slots 2i, 2i+1 → one 2-wide store per field
     const uint64_t i0 = 2 * i;
-    const uint64_t off = (i0 >> L.tile_shift) * L.tile_stride + (i0 & L.tile_mask);
     using V2 = DST __attribute__((ext_vector_type(2)));
     const bool ok0 = best_j[0] != 0xFFFFFFFFu;
     const bool ok1 = best_j[1] != 0xFFFFFFFFu && max_neighbors > 1;
     found = int(ok0) + int(ok1);
     const double pl[3] = {x, y, z};
-#pragma unroll
-    for (int f = 0; f < 3; ++f) {
+    auto put = [&](int plane, DST v0, DST v1) {  // slots 2i, 2i + 1 of one stored plane
       V2 v;
-      v[0] = ok0 ? DST(pl[f]) : DST(0);
-      v[1] = ok1 ? DST(pl[f]) : DST(0);
-      *reinterpret_cast<V2*>(dst + off + uint64_t(f) * L.field_stride) = v;
-    }
+      v[0] = v0;
+      v[1] = v1;
+      *reinterpret_cast<V2*>(dst + plane_offset(L, i0, plane)) = v;
+    };
 #pragma unroll
-    for (int f = 0; f < 3; ++f) {
-      V2 v;
-      v[0] = ok0 ? DST(map.mean[3 * size_t(best_j[0]) + f]) : DST(0);
-      v[1] = ok1 ? DST(map.mean[3 * size_t(best_j[1]) + f]) : DST(0);
-      *reinterpret_cast<V2*>(dst + off + uint64_t(3 + f) * L.field_stride) = v;
-    }
+    for (int f = 0; f < 3; ++f) put(f, ok0 ? DST(pl[f]) : DST(0), ok1 ? DST(pl[f]) : DST(0));
+#pragma unroll
+    for (int f = 0; f < 3; ++f)
+      put(3 + f, ok0 ? DST(map.mean[3 * size_t(best_j[0]) + f]) : DST(0), ok1 ? DST(map.mean[3 * size_t(best_j[1]) + f]) : DST(0));
+    DST S0[9], S1[9], A0[6], A1[6];
 #pragma unroll
     for (int f = 0; f < 9; ++f) {
-      V2 v;
-      v[0] = ok0 ? DST(map.sqrt_info[9 * size_t(best_j[0]) + f]) : DST(0);
-      v[1] = ok1 ? DST(map.sqrt_info[9 * size_t(best_j[1]) + f]) : DST(0);
-      *reinterpret_cast<V2*>(dst + off + uint64_t(6 + f) * L.field_stride) = v;
+      S0[f] = ok0 ? DST(map.sqrt_info[9 * size_t(best_j[0]) + f]) : DST(0);
+      S1[f] = ok1 ? DST(map.sqrt_info[9 * size_t(best_j[1]) + f]) : DST(0);
+      put(ndt_stored_plane(6 + f), S0[f], S1[f]);
     }
+    sqrt_info_to_A<DST>(S0, A0);
+    sqrt_info_to_A<DST>(S1, A1);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) put(6 + k, A0[k], A1[k]);
   }
   // match count: wave sum → one atomic per wave (integer, order independent)
   int s = found;
@@ -224,27 +224,26 @@ __global__ __launch_bounds__(64) void drop_last_matches_kernel(T* __restrict__ d
   for (uint64_t pos = L.n; remaining > 0 && pos > 0; pos = pos > 64 ? pos - 64 : 0) {
     const bool in_range = pos > uint64_t(lane);
     const uint64_t i = in_range ? pos - 1 - uint64_t(lane) : 0;
-    const uint64_t off = (i >> L.tile_shift) * L.tile_stride + (i & L.tile_mask);
     bool nonempty = false;
     if (in_range)
-      for (int f = 6; f < 15; ++f) nonempty = nonempty || data[off + uint64_t(f) * L.field_stride] != T(0);
+      for (int f = 6; f < 15; ++f) nonempty = nonempty || data[plane_offset(L, i, ndt_stored_plane(f))] != T(0);
     const unsigned long long mask = __ballot(nonempty);
     const uint64_t before = uint64_t(__popcll(mask & ((1ull << lane) - 1ull)));  // non-empty slots nearer to the end
-    if (nonempty && before < remaining)
-      for (int f = 0; f < 15; ++f) data[off + uint64_t(f) * L.field_stride] = T(0);
+    if (nonempty && before < remaining)  // all 21 stored planes (A as well): the cleared record contributes nothing
+      for (int f = 0; f < kNdtStored; ++f) data[plane_offset(L, i, f)] = T(0);
     const uint64_t found = uint64_t(__popcll(mask));
     remaining -= found < remaining ? found : remaining;
   }
 }
 
-// tiled dataset → planar host-order planes (diagnostics / tests)
+// tiled dataset → planar host-order planes (diagnostics / tests); flat NDT (ndt != 0): the 15 planes of nos.h (p, mu, S)
 template <typename SRC>
-__global__ __launch_bounds__(256) void untile_kernel(const SRC* __restrict__ src, int n_fields, TiledLayout L,
+__global__ __launch_bounds__(256) void untile_kernel(const SRC* __restrict__ src, int n_fields, int ndt, TiledLayout L,
                                                      double* __restrict__ dst /* [n_fields][L.n] */) {
   const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
   const int f = blockIdx.y;
   if (i >= L.n || f >= n_fields) return;
-  const uint64_t off = (i >> L.tile_shift) * L.tile_stride + uint64_t(f) * L.field_stride + (i & L.tile_mask);
+  const uint64_t off = plane_offset(L, i, ndt != 0 ? ndt_stored_plane(f) : f);
   dst[uint64_t(f) * L.n + i] = double(src[off]);
 }
 

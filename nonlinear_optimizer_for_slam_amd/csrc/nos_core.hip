@@ -100,7 +100,12 @@ int env_int(const char* name, int dflt) {
 
 // ------------------------------------------------------------------ layout
 
+// n_fields: stored planes.  Flat NDT (nos::kNdtStored = 21): the 12 streamed planes (p, mu, A) in the layout below, the 9
+// planes of S behind them in a region of the same shape (nos::TiledLayout) — planar with the plane skew for fp64, tiles of
+// 2^10 items whose 12 streamed fields are contiguous for fp32.
 nos::TiledLayout make_layout(size_t n, int n_fields, int tile_log2, int plane_skew) {
+  const int stored = n_fields;
+  if (n_fields == nos::kNdtStored) n_fields = nos::kNdtStreamed;
   nos::TiledLayout L{};
   L.n = n;
   if (tile_log2 <= 0) {
@@ -123,8 +128,15 @@ nos::TiledLayout make_layout(size_t n, int n_fields, int tile_log2, int plane_sk
     L.tile_shift = uint32_t(tile_log2);
     L.tile_mask = uint32_t(tile - 1);
   }
+  if (stored == nos::kNdtStored) {
+    L.s_offset = (L.tile_stride == 0 ? L.field_stride : L.n_padded) * size_t(nos::kNdtStreamed);
+    L.s_tile_stride = L.tile_stride == 0 ? 0 : L.field_stride * size_t(nos::kNdtStored - nos::kNdtStreamed);
+  }
   return L;
 }
+
+// planes a dataset stores (flat NDT: 21, see make_layout); ds->n_fields are the planes of the caller's view (nos.h)
+int stored_planes(const nos_dataset* ds) { return ds->kind == kKindNdt ? nos::kNdtStored : ds->n_fields; }
 
 size_t layout_elems(const nos::TiledLayout& L, int n_fields) {
   return (L.tile_stride == 0 ? L.field_stride : L.n_padded) * size_t(n_fields);
@@ -285,13 +297,13 @@ int launch_single(const nos::TiledLayout& L, const typename Problem::Params& P, 
     return NOS_OK;
   }
   if (a.cluster_blocks > 0) {
-    using Shape = nos::ResidentShape<Problem::kFields, int(sizeof(T))>;
+    using Shape = nos::ResidentShape<Problem::kPlanes, int(sizeof(T))>;
     if (a.items_per_lane < 1 || a.items_per_lane > Shape::RI + Shape::LI)
       return fail(NOS_ERR_INVALID_ARGUMENT, "resident solve: %d items per lane do not fit (%d + %d)", a.items_per_lane,
                   Shape::RI, Shape::LI);
     const auto kernel = nos::solve_cluster_kernel<Problem, T, kBlock, Shape::RI, Shape::LI>;
     const size_t lds_items = a.items_per_lane > Shape::RI ? size_t(a.items_per_lane - Shape::RI) : 0;
-    const size_t dyn_bytes = lds_items * size_t(nos::resident_fields<Problem::kFields, sizeof(T)>()) * kBlock * sizeof(T);
+    const size_t dyn_bytes = lds_items * size_t(Problem::kFields) * kBlock * sizeof(T);
     // Dynamic LDS beyond the default limit has to be granted per kernel AND per device (the attribute belongs to the
     // function on the current device): asked for on every launch that needs it — a host-side call of about a microsecond,
     // once per solve — instead of remembered in a process-wide static that a second device or thread would trip over.
@@ -1061,8 +1073,8 @@ int alloc_shards(nos_ctx* ctx, nos_dataset* ds) {
     const size_t cnt = begin < n ? std::min(per, n - begin) : 0;
     Shard& sh = ds->shards[s];
     sh.slot = s;
-    sh.layout = make_layout(cnt, ds->n_fields, tile_log2, ctx->settings.plane_skew);
-    sh.bytes = layout_elems(sh.layout, ds->n_fields) * elem_size(ds->dtype);
+    sh.layout = make_layout(cnt, stored_planes(ds), tile_log2, ctx->settings.plane_skew);
+    sh.bytes = layout_elems(sh.layout, stored_planes(ds)) * elem_size(ds->dtype);
     NOS_HIP_CHECK(hipSetDevice(ctx->slots[s].device));
     int prc = pool_alloc(ctx->slots[s], sh.bytes, &sh.data, &sh.capacity);
     if (prc != NOS_OK) return prc;
@@ -1076,6 +1088,16 @@ int alloc_shards(nos_ctx* ctx, nos_dataset* ds) {
 template <typename SRC>
 int retile_dispatch(const nos::PlanePtrs& src, int n_fields, const nos::TiledLayout& L, void* dst, int dtype,
                     hipStream_t stream) {
+  if (n_fields == NOS_NDT_PLANES) {  // flat NDT: one item per thread, its A planes computed on the way
+    const dim3 grid1(unsigned((L.n_padded + 255) / 256));
+    if (dtype == NOS_F64)
+      hipLaunchKernelGGL((nos::retile_ndt_kernel<SRC, double>), grid1, dim3(256), 0, stream, src, L, static_cast<double*>(dst));
+    else
+      hipLaunchKernelGGL((nos::retile_ndt_kernel<SRC, float>), grid1, dim3(256), 0, stream, src, L, static_cast<float*>(dst));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(NOS_ERR_HIP, "retile launch failed: %s", hipGetErrorString(e));
+    return NOS_OK;
+  }
   dim3 grid(unsigned((L.n_padded + 255) / 256), unsigned(n_fields));
   if (dtype == NOS_F64)
     hipLaunchKernelGGL((nos::retile_kernel<SRC, double>), grid, dim3(256), 0, stream, src, n_fields, L,
@@ -1212,26 +1234,32 @@ int zero_pad_launch(int n_fields, const nos::TiledLayout& L, void* dst, hipStrea
 // `pinned` is the staging image of one chunk: planar (tile_log2 = 0: field f of record j at f * chunk + j) or in the
 // dataset's tiled order (record j of the chunk at (j >> T) * n_fields * 2^T + f * 2^T + (j mod 2^T); chunks start on
 // tile boundaries), so that the image is one contiguous piece of the dataset.  [lo, lo + count) = this thread's records.
+// Flat NDT in tiles (ndt): the image has the two regions of the stored layout — [tiles][12][2^T] with p, mu in fields 0-5
+// (the A fields are computed on the device afterwards), then at 12 * chunk [tiles][9][2^T] of S — each one contiguous piece.
 // Records are taken a cache line of OUTPUT at a time (8 doubles / 16 floats per field): the line's worth of every field is
 // gathered into a small block first and leaves with full-line non-temporal stores — the staging image is written once and
 // read only by the copy engine, so the destination lines need not be fetched for ownership first (4.2 instead of 5.4 GB of
 // host memory traffic per 10 M NDT records) and 15 interleaved 8-byte store streams do not fight over the core's
 // write-combining buffers.
 template <typename T>
-void pack_range(const unsigned char* host, size_t stride, const nos::FieldOffsets& fo, int n_fields, size_t first, size_t lo,
-                size_t count, size_t chunk, int tile_log2, T* pinned) {
+void pack_range(const unsigned char* host, size_t stride, const nos::FieldOffsets& fo, int n_fields, bool ndt, size_t first,
+                size_t lo, size_t count, size_t chunk, int tile_log2, T* pinned) {
   const size_t tile = size_t(1) << tile_log2, mask = tile - 1;
-  const size_t pitch = tile_log2 == 0 ? chunk : tile;
-  auto dst_of = [&](size_t j) -> T* {
-    return tile_log2 == 0 ? pinned + j : pinned + (j >> tile_log2) * (tile * size_t(n_fields)) + (j & mask);
+  [[maybe_unused]] const size_t pitch = tile_log2 == 0 ? chunk : tile;
+  auto dst_of = [&](size_t j, int f) -> T* {
+    if (tile_log2 == 0) return pinned + size_t(f) * chunk + j;
+    if (ndt && f >= 6)
+      return pinned + size_t(nos::kNdtStreamed) * chunk + (j >> tile_log2) * (tile * size_t(nos::kNdtStored - nos::kNdtStreamed)) +
+             size_t(f - 6) * tile + (j & mask);
+    const size_t tile_fields = ndt ? size_t(nos::kNdtStreamed) : size_t(n_fields);
+    return pinned + (j >> tile_log2) * (tile * tile_fields) + size_t(f) * tile + (j & mask);
   };
   auto one = [&](size_t j) {
     const unsigned char* rec = host + (first + j) * stride;
-    T* dst = dst_of(j);
     for (int f = 0; f < n_fields; ++f) {
       double v;
       memcpy(&v, rec + fo.off[f], sizeof v);
-      dst[size_t(f) * pitch] = T(v);
+      *dst_of(j, f) = T(v);
     }
   };
   [[maybe_unused]] constexpr size_t kLine = 64 / sizeof(T);  // records per output cache line
@@ -1250,10 +1278,9 @@ void pack_range(const unsigned char* host, size_t stride, const nos::FieldOffset
           block[f][r] = T(v);
         }
       }
-      T* dst = dst_of(j);  // a line never straddles a tile: tiles are multiples of 1 024 records
-      for (int f = 0; f < n_fields; ++f) {
+      for (int f = 0; f < n_fields; ++f) {  // a line never straddles a tile: tiles are multiples of 1 024 records
         const __m128d* src = reinterpret_cast<const __m128d*>(block[f]);
-        double* line = reinterpret_cast<double*>(dst + size_t(f) * pitch);
+        double* line = reinterpret_cast<double*>(dst_of(j, f));
         _mm_stream_pd(line + 0, src[0]);
         _mm_stream_pd(line + 2, src[1]);
         _mm_stream_pd(line + 4, src[2]);
@@ -1272,7 +1299,10 @@ int ingest_host_pack(nos_ctx* ctx, nos_dataset* ds, Shard& sh, const unsigned ch
   const size_t cnt = sh.layout.n;
   const size_t es = elem_size(ds->dtype);
   const size_t chunk = size_t(256) << 10;  // records per chunk: 31 MB of fp64 planes
-  const size_t need = chunk * size_t(ds->n_fields) * es;
+  const bool ndt = ds->kind == kKindNdt;
+  const int tile_log2 = sh.layout.tile_stride == 0 ? 0 : int(sh.layout.tile_shift);  // 0 = planar planes
+  // image of one chunk: the planes as given (planar), or the stored layout's tiles (flat NDT: 21 fields, A left to the device)
+  const size_t need = chunk * size_t(ndt && tile_log2 != 0 ? nos::kNdtStored : ds->n_fields) * es;
   hipError_t e = hipSetDevice(slot.device);
   if (e == hipSuccess && slot.copy_stream == nullptr) e = hipStreamCreateWithFlags(&slot.copy_stream, hipStreamNonBlocking);
   for (int b = 0; b < 2 && e == hipSuccess; ++b)
@@ -1295,7 +1325,6 @@ int ingest_host_pack(nos_ctx* ctx, nos_dataset* ds, Shard& sh, const unsigned ch
   void* const pinned2[2] = {slot.pack_pinned[0], slot.pack_pinned[1]};
   const int n_fields = ds->n_fields;
   const bool f64 = ds->dtype == NOS_F64;
-  const int tile_log2 = sh.layout.tile_stride == 0 ? 0 : int(sh.layout.tile_shift);  // 0 = planar planes
   std::vector<std::thread> pool;
   const int n_workers = (e == hipSuccess && n_chunks > 0) ? threads : 0;
   for (int w = 0; w < n_workers; ++w) {
@@ -1308,9 +1337,11 @@ int ingest_host_pack(nos_ctx* ctx, nos_dataset* ds, Shard& sh, const unsigned ch
         const size_t lo = std::min(count, size_t(w) * per), hi = std::min(count, lo + per);
         if (lo < hi) {
           if (f64)
-            pack_range<double>(host, stride, fo, n_fields, first, lo, hi - lo, chunk, tile_log2, static_cast<double*>(pinned2[c & 1]));
+            pack_range<double>(host, stride, fo, n_fields, ndt, first, lo, hi - lo, chunk, tile_log2,
+                               static_cast<double*>(pinned2[c & 1]));
           else
-            pack_range<float>(host, stride, fo, n_fields, first, lo, hi - lo, chunk, tile_log2, static_cast<float*>(pinned2[c & 1]));
+            pack_range<float>(host, stride, fo, n_fields, ndt, first, lo, hi - lo, chunk, tile_log2,
+                              static_cast<float*>(pinned2[c & 1]));
         }
         arrived.fetch_add(1, std::memory_order_release);
       }
@@ -1326,7 +1357,7 @@ int ingest_host_pack(nos_ctx* ctx, nos_dataset* ds, Shard& sh, const unsigned ch
     while (arrived.load(std::memory_order_acquire) < int(c + 1) * n_workers) std::this_thread::yield();
     if (tile_log2 == 0) {
       for (int f = 0; f < n_fields && e == hipSuccess; ++f) {
-        char* dst = static_cast<char*>(sh.data) + (size_t(f) * sh.layout.field_stride + first) * es;
+        char* dst = static_cast<char*>(sh.data) + nos::plane_offset(sh.layout, first, ndt ? nos::ndt_stored_plane(f) : f) * es;
         const char* src = static_cast<const char*>(slot.pack_pinned[buf]) + size_t(f) * chunk * es;
         e = hipMemcpyAsync(dst, src, count * es, hipMemcpyHostToDevice, slot.copy_stream);
       }
@@ -1335,6 +1366,11 @@ int ingest_host_pack(nos_ctx* ctx, nos_dataset* ds, Shard& sh, const unsigned ch
       const size_t tiles = (count + tile - 1) / tile;
       char* dst = static_cast<char*>(sh.data) + (first >> tile_log2) * sh.layout.tile_stride * es;
       e = hipMemcpyAsync(dst, slot.pack_pinned[buf], tiles * sh.layout.tile_stride * es, hipMemcpyHostToDevice, slot.copy_stream);
+      if (ndt && e == hipSuccess) {  // the S region's tiles of the chunk
+        char* dst_s = static_cast<char*>(sh.data) + (sh.layout.s_offset + (first >> tile_log2) * sh.layout.s_tile_stride) * es;
+        const char* src_s = static_cast<const char*>(slot.pack_pinned[buf]) + size_t(nos::kNdtStreamed) * chunk * es;
+        e = hipMemcpyAsync(dst_s, src_s, tiles * sh.layout.s_tile_stride * es, hipMemcpyHostToDevice, slot.copy_stream);
+      }
     }
     if (e == hipSuccess) e = hipEventRecord(slot.pack_done[buf], slot.copy_stream);
     used[buf] = true;
@@ -1344,8 +1380,18 @@ int ingest_host_pack(nos_ctx* ctx, nos_dataset* ds, Shard& sh, const unsigned ch
   if (e == hipSuccess) e = hipStreamSynchronize(slot.copy_stream);
   if (e != hipSuccess)
     return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "host-pack ingestion failed: %s", hipGetErrorString(e));
-  int rc = (ds->dtype == NOS_F64) ? zero_pad_launch<double>(ds->n_fields, sh.layout, sh.data, slot.stream)
-                                  : zero_pad_launch<float>(ds->n_fields, sh.layout, sh.data, slot.stream);
+  if (ndt && cnt > 0) {  // A = SᵀS from the S just copied, in the dataset's element type
+    const dim3 grid(unsigned((cnt + 255) / 256));
+    if (f64)
+      hipLaunchKernelGGL((nos::ndt_a_planes_kernel<double>), grid, dim3(256), 0, slot.stream, sh.layout,
+                         static_cast<double*>(sh.data), uint64_t(0), uint64_t(cnt));
+    else
+      hipLaunchKernelGGL((nos::ndt_a_planes_kernel<float>), grid, dim3(256), 0, slot.stream, sh.layout,
+                         static_cast<float*>(sh.data), uint64_t(0), uint64_t(cnt));
+    NOS_HIP_CHECK(hipGetLastError());
+  }
+  int rc = (ds->dtype == NOS_F64) ? zero_pad_launch<double>(stored_planes(ds), sh.layout, sh.data, slot.stream)
+                                  : zero_pad_launch<float>(stored_planes(ds), sh.layout, sh.data, slot.stream);
   if (rc != NOS_OK) return rc;
   NOS_HIP_CHECK(hipStreamSynchronize(slot.stream));
   return NOS_OK;
@@ -1436,8 +1482,8 @@ int create_from_records(nos_ctx* ctx, int kind, size_t n, const void* records, s
       }
     }
     if (e == hipSuccess && rc == NOS_OK)
-      rc = (dtype == NOS_F64) ? zero_pad_launch<double>(ds->n_fields, sh.layout, sh.data, slot.stream)
-                              : zero_pad_launch<float>(ds->n_fields, sh.layout, sh.data, slot.stream);
+      rc = (dtype == NOS_F64) ? zero_pad_launch<double>(stored_planes(ds), sh.layout, sh.data, slot.stream)
+                              : zero_pad_launch<float>(stored_planes(ds), sh.layout, sh.data, slot.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(slot.stream);
     if (copy_stream) (void)hipStreamSynchronize(copy_stream);
     if (e != hipSuccess || rc != NOS_OK) {
@@ -1873,6 +1919,8 @@ size_t nos_dataset_stream_bytes(const nos_dataset* ds) {
   if (!ds) return 0;
   if (ds->kind == kKindNdtIndexed)  // point (3 values) + one 4-byte voxel id per slot; the voxel table is cache resident
     return ds->n * (3 * elem_size(ds->dtype) + sizeof(int32_t) * size_t(ds->shards.empty() ? 0 : ds->shards[0].n_slots));
+  // flat datasets: the planes of the caller's record (nos.h).  Flat NDT kernels stream 12 of the 15 (p, mu, A = SᵀS;
+  // fp32 3-DoF: p, mu, S) — the figure stays the record's, which the test suite pins.
   return ds->n * size_t(ds->n_fields) * elem_size(ds->dtype);
 }
 

@@ -424,7 +424,7 @@ int nos_ndt_match(nos_ndt_map* map, nos_scan* scan, const double R[9], const dou
     e = hipGetLastError();
   }
   if (e == hipSuccess)
-    rc = zero_pad(dtype, ds->n_fields, sh.layout, sh.data, slot.stream);
+    rc = zero_pad(dtype, nos::kNdtStored, sh.layout, sh.data, slot.stream);
   unsigned long long count = 0;
   if (e == hipSuccess && rc == NOS_OK)
     e = hipMemcpyAsync(&count, map->d_n_matches, sizeof count, hipMemcpyDeviceToHost, slot.stream);
@@ -472,10 +472,10 @@ int nos_dataset_download(nos_dataset* ds, double* const planes[]) {
     const dim3 grid(unsigned((cnt + 255) / 256), unsigned(ds->n_fields));
     if (ds->dtype == NOS_F64)
       hipLaunchKernelGGL((nos::untile_kernel<double>), grid, dim3(256), 0, slot.stream,
-                         static_cast<const double*>(sh.data), ds->n_fields, sh.layout, tmp);
+                         static_cast<const double*>(sh.data), ds->n_fields, int(ds->kind == kKindNdt), sh.layout, tmp);
     else
       hipLaunchKernelGGL((nos::untile_kernel<float>), grid, dim3(256), 0, slot.stream,
-                         static_cast<const float*>(sh.data), ds->n_fields, sh.layout, tmp);
+                         static_cast<const float*>(sh.data), ds->n_fields, int(ds->kind == kKindNdt), sh.layout, tmp);
     hipError_t e = hipGetLastError();
     for (int f = 0; f < ds->n_fields && e == hipSuccess; ++f)
       e = hipMemcpyAsync(planes[f] + begin, tmp + size_t(f) * cnt, cnt * sizeof(double), hipMemcpyDeviceToHost, slot.stream);
