@@ -185,8 +185,8 @@ int nos_dataset_destroy(nos_dataset* ds);
 size_t nos_dataset_size(const nos_dataset* ds);
 int nos_dataset_dtype(const nos_dataset* ds);
 /* Bytes of the dataset's correspondences as the caller gives them: n × planes × sizeof(element).  Flat NDT datasets
- * also store A = SᵀS of every sqrt-information (computed on the device when the dataset is made), and the 6-DoF and fp64
- * 3-DoF kernels stream p, mu and A only — 12 of these 15 planes' worth (96 / 48 B per fp64 / fp32 correspondence), so
+ * also store U of every sqrt-information S = QU (triangular, computed on the device when the dataset is made), and the 6-DoF and fp64
+ * 3-DoF kernels stream p, mu and U only — 12 of these 15 planes' worth (96 / 48 B per fp64 / fp32 correspondence), so
  * a pass moves 0.8 × this figure; the fp32 3-DoF kernels stream p, mu and S (all 15). */
 size_t nos_dataset_stream_bytes(const nos_dataset* ds);
 

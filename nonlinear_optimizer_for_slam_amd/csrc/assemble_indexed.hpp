@@ -12,7 +12,7 @@ namespace nos {
 // The reference's data model copies the whole NDT into every correspondence (MDM/types.h:23-26), which
 // is what the flat 120-byte layout above streams.  When many points share a voxel (10 M points over
 // 200 k voxels = 50 per voxel) the same sums can be formed from  point (3 values) + voxel id(s)  and a
-// table of voxel records {mean(3), A = SᵀS (6), pad}: 24 B + 4 B·K per point instead of
+// table of voxel records {mean(3), U (6: S = QU), pad}: 24 B + 4 B·K per point instead of
 // 120 B·K, with the table (≈ 25 MB at 200 k voxels) served from L2 / Infinity Cache.  Points are
 // stored sorted by voxel id (done once at dataset creation), so the lanes of a wave hit a handful
 // of table records that stay in L1.  The kernel is then fp64-ALU bound, not HBM bound; it is reported
@@ -20,7 +20,7 @@ namespace nos {
 struct IndexedLayout {
   const void* points;      // 3 planes of n_padded (element type T)
   const int32_t* index;    // K planes of n_padded voxel ids, -1 = no correspondence in that slot
-  const void* table;       // [n_voxels][16] of T: mean(3), A = SᵀS upper triangle (6), pad(7)
+  const void* table;       // [n_voxels][16] of T: mean(3), U (6, sqrt_info_to_U), pad(7)
   uint64_t n_padded;       // multiple of the kernel chunk; pads carry index -1
 };
 
@@ -35,7 +35,7 @@ __device__ __forceinline__ void load_voxel_record(const T* table, int32_t v, T (
     using V2 = double __attribute__((ext_vector_type(2)));
     const V2* q = reinterpret_cast<const V2*>(p);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {  // mean (3) + A = SᵀS (6) = 9 values
+    for (int k = 0; k < 4; ++k) {  // mean (3) + U (6) = 9 values
       const V2 t = q[k];
       rec[2 * k] = t[0];
       rec[2 * k + 1] = t[1];
@@ -107,8 +107,8 @@ __global__ __launch_bounds__(BLOCK, MINW) void assemble_indexed_kernel(IndexedLa
     for (int k = 0; k < K; ++k) {
       if (live && vid[k] >= 0) {
         const T mu[3] = {rec[k][0], rec[k][1], rec[k][2]};
-        const T A[6] = {rec[k][3], rec[k][4], rec[k][5], rec[k][6], rec[k][7], rec[k][8]};
-        Problem::item_A(p, mu, A, P, acc);
+        const T U[6] = {rec[k][3], rec[k][4], rec[k][5], rec[k][6], rec[k][7], rec[k][8]};
+        Problem::item_U(p, mu, U, P, acc);
       }
     }
   };
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void gather_plane_kernel(const SRC* __restrict
   dst[j] = j < n ? DST(src[perm ? perm[j] : j]) : pad_value;
 }
 
-// voxel table: [V][3] means + [V][9] sqrt-informations (double) → [V][16] records of T = {mean, SᵀS upper triangle}
+// voxel table: [V][3] means + [V][9] sqrt-informations (double) → [V][16] records of T = {mean, U of S = QU}
 template <typename T>
 __global__ __launch_bounds__(256) void build_voxel_table_kernel(const double* __restrict__ means,
                                                                 const double* __restrict__ sqrt_infos, uint64_t n_voxels,
@@ -156,11 +156,13 @@ __global__ __launch_bounds__(256) void build_voxel_table_kernel(const double* __
   T val = T(0);
   if (k < 3) {
     val = T(means[3 * v + k]);
-  } else if (k < 9) {  // A = SᵀS, upper triangle row-major: (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
-    const int ii[6] = {0, 0, 0, 1, 1, 2}, jj[6] = {0, 1, 2, 1, 2, 2};
-    const int i = ii[k - 3], j = jj[k - 3];
-    const double* S = sqrt_infos + 9 * v;
-    val = T(S[i] * S[j] + S[3 + i] * S[3 + j] + S[6 + i] * S[6 + j]);
+  } else if (k < 9) {  // U from the fp64 S, rounded once: u00 u01 u02 u11 u12 u22
+    double S[9], U[6];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) S[q] = sqrt_infos[9 * v + q];
+    sqrt_info_to_U<double>(S, U);
+    const int q = k - 3;  // selects, not an indexed private array (no scratch)
+    val = T(q == 0 ? U[0] : q == 1 ? U[1] : q == 2 ? U[2] : q == 3 ? U[3] : q == 4 ? U[4] : U[5]);
   }
   table[t] = val;
 }

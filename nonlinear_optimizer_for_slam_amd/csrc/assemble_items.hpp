@@ -26,7 +26,8 @@ enum LossKind : int { kLossNone = 0, kLossExponential = 1, kLossHuber = 2 };
 // Tiled SoA addressing.  Correspondence i, field f lives at element offset
 //   (i >> tile_shift) * tile_stride + f * field_stride + (i & (tile - 1)).
 // tile == n_padded, tile_stride == 0 gives a plain planar layout.
-// Flat NDT datasets store 21 planes: the 12 the kernels stream — p (3), mu (3), A = SᵀS (a00 a01 a02 a11 a12 a22) — in
+// Flat NDT datasets store 21 planes: the 12 the kernels stream — p (3), mu (3), U (u00 u01 u02 u11 u12 u22: S = QU,
+// sqrt_info_to_U) — in
 // the layout above, then the 9 planes of S (row-major) in a second region of the same allocation, laid out alike:
 //   s_offset + (i >> tile_shift) * s_tile_stride + k * field_stride + (i & (tile - 1)),
 // so that a pass over the streamed planes never touches S (nos_dataset_download and the fp32 3-DoF item read it).
@@ -42,7 +43,7 @@ struct TiledLayout {
   uint64_t s_tile_stride;  // flat NDT: elements between consecutive tiles of the S region
 };
 
-constexpr int kNdtStreamed = 12;  // planes of a flat NDT dataset the kernels stream: p, mu, A
+constexpr int kNdtStreamed = 12;  // planes of a flat NDT dataset the kernels stream: p, mu, U
 constexpr int kNdtStored = 21;    // and the 9 planes of S behind them
 // stored plane of plane f of the caller's view (p, mu, S row-major: the 15 planes of nos.h)
 __host__ __device__ constexpr int ndt_stored_plane(int f) { return f < 6 ? f : f + 6; }
@@ -51,16 +52,42 @@ __host__ __device__ inline uint64_t plane_offset(const TiledLayout& L, uint64_t 
   if (f < kNdtStreamed) return (i >> L.tile_shift) * L.tile_stride + uint64_t(f) * L.field_stride + (i & L.tile_mask);
   return L.s_offset + (i >> L.tile_shift) * L.s_tile_stride + uint64_t(f - kNdtStreamed) * L.field_stride + (i & L.tile_mask);
 }
-// A = SᵀS of a row-major sqrt-information, in the element type of the dataset:
-//   A(a, b) = S(0,a) S(0,b) + S(1,a) S(1,b) + S(2,a) S(2,b)  as fma(S0a, S0b, fma(S1a, S1b, S2a * S2b)),
-// the expression the fp32 item and the resident fp64 form used when they converted S on the fly; a00 a01 a02 a11 a12 a22
+// U = the upper-triangular factor of a QR of a row-major sqrt-information S (S = Q U, so UᵀU = SᵀS), in the element type
+// of the dataset: u00 u01 u02 u11 u12 u22.  Computed in fp64 from the stored S by three Givens rotations (backward stable:
+// Q̂U = S + ΔS, ‖ΔS‖ ≈ u‖S‖; a rank-deficient S gives a zero row of U), then rounded once.  The items evaluate
+// r' = U e = Qᵀ(S e), s = r'ᵀr' and J' = [U | U M] (Ndt6Problem::item_U): the error of s grows like u·κ(S), as in the
+// S form of the reference, not like u·κ(S)² as that of eᵀ(SᵀS)e does.
 template <typename T>
-__device__ __forceinline__ void sqrt_info_to_A(const T (&S)[9], T (&A)[6]) {
-  int q = 0;
+__device__ __forceinline__ void sqrt_info_to_U(const T (&S)[9], T (&U)[6]) {
+  double m[3][3];
 #pragma unroll
-  for (int a = 0; a < 3; ++a)
+  for (int k = 0; k < 9; ++k) m[k / 3][k % 3] = double(S[k]);
+  // zero (1,0) and (2,0) against row 0, then (2,1) against row 1
+  const int rot[3][3] = {{0, 1, 0}, {0, 2, 0}, {1, 2, 1}};  // pivot row, zeroed row, column
 #pragma unroll
-    for (int b = a; b < 3; ++b) A[q++] = fma(S[a], S[b], fma(S[3 + a], S[3 + b], S[6 + a] * S[6 + b]));
+  for (int q = 0; q < 3; ++q) {
+    const int i = rot[q][0], j = rot[q][1], c = rot[q][2];
+    const double a = m[i][c], b = m[j][c];
+    const double r = hypot(a, b);
+    if (r > 0.0) {
+      const double cs = a / r, sn = b / r;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        if (k <= c) continue;
+        const double x = m[i][k], y = m[j][k];
+        m[i][k] = fma(cs, x, sn * y);
+        m[j][k] = fma(cs, y, -(sn * x));
+      }
+      m[i][c] = r;
+      m[j][c] = 0.0;
+    }
+  }
+  U[0] = T(m[0][0]);
+  U[1] = T(m[0][1]);
+  U[2] = T(m[0][2]);
+  U[3] = T(m[1][1]);
+  U[4] = T(m[1][2]);
+  U[5] = T(m[2][2]);
 }
 
 template <typename T>
@@ -253,143 +280,109 @@ __device__ __forceinline__ void minus_R_hat(const typename Lanes<V>::S (&R)[9], 
 
 template <typename T, int LOSS>
 struct Ndt6Problem {
-  static constexpr int kFields = kNdtStreamed;  // planes an item reads: p, mu, A (see TiledLayout)
+  static constexpr int kFields = kNdtStreamed;  // planes an item reads: p, mu, U (see TiledLayout)
   static constexpr int kPlanes = 15;            // planes of a correspondence as the caller gives it (p, mu, S)
-  static constexpr bool kSPlanes = false;       // reads S instead of A (Ndt3Problem<float>)
+  static constexpr bool kSPlanes = false;       // reads S instead of U (Ndt3Problem<float>)
   static constexpr int kOut = 28;
   using Params = Ndt6Params<T>;
-  // x = {p(3), mu(3), A = SᵀS (a00 a01 a02 a11 a12 a22)}; V = T (one correspondence) or float2_t (two, fp32 only)
+  // x = {p(3), mu(3), U (u00 u01 u02 u11 u12 u22)}; V = T (one correspondence) or float2_t (two, fp32 only).  Zero-padded
+  // records have U = 0 → s = 0, H = g = 0, rho(0) = 0: no mask needed.
   template <typename V = T>
   __device__ static __forceinline__ void item(const V (&x)[kNdtStreamed], const Params& P,
                                               const bool (&)[Lanes<V>::n] /*valid*/, V (&acc)[28]) {
-    if constexpr (sizeof(typename Lanes<V>::S) == 8) {
-      // fp64: the A form below (zero-padded records have A = 0 → s = 0, H = g = 0, rho(0) = 0: no mask needed)
-      const T p3[3] = {x[0], x[1], x[2]}, mu3[3] = {x[3], x[4], x[5]};
-      const T A6[6] = {x[6], x[7], x[8], x[9], x[10], x[11]};
-      item_A(p3, mu3, A6, P, acc);
-    } else {
-      V e[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const V pw = sfma<V>(P.R[3 * i], x[0], sfma<V>(P.R[3 * i + 1], x[1], sfma<V>(P.R[3 * i + 2], x[2], splat<V>(P.t[i]))));
-        e[i] = pw - x[3 + i];
-      }
-      // fp32: H = w [I|M]ᵀ A [I|M], g = w [I|M]ᵀ A e, s = eᵀ A e from the stored A — ≈ 150 instead of ≈ 186 operations
-      // per correspondence of the S form, the same sums.  Measured error against the fp64 oracle unchanged (1.09e-6 against
-      // 1.07e-6 scaled, of which 1.0e-6 is the rounding of the inputs; profiles/r02_fp32_error.jsonl).  A is computed
-      // from the fp32-rounded S when the dataset is made, with the expression this item used on every pass before.
-      V A[3][3], Ae[3], wAe[3], B[3][3], M[3][3];
-      int q = 6;
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = i; j < 3; ++j) {
-          A[i][j] = x[q++];
-          A[j][i] = A[i][j];
-        }
-#pragma unroll
-      for (int i = 0; i < 3; ++i) Ae[i] = vfma<V>(A[i][0], e[0], vfma<V>(A[i][1], e[1], A[i][2] * e[2]));
-      const V s2 = vfma<V>(e[0], Ae[0], vfma<V>(e[1], Ae[1], e[2] * Ae[2]));
-      V rho2, w2;
-      loss_eval_v<V, LOSS>(s2, P.la, P.lb, P.lc, rho2, w2);
-      minus_R_hat<V>(P.R, x[0], x[1], x[2], M);
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        wAe[i] = w2 * Ae[i];
-#pragma unroll
-        for (int j = i; j < 3; ++j) {
-          A[i][j] = w2 * A[i][j];
-          A[j][i] = A[i][j];
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) B[i][b] = vfma<V>(A[i][0], M[0][b], vfma<V>(A[i][1], M[1][b], A[i][2] * M[2][b]));
-      acc[0] += A[0][0];
-      acc[1] += A[0][1];
-      acc[2] += A[0][2];
-      acc[6] += A[1][1];
-      acc[7] += A[1][2];
-      acc[11] += A[2][2];
-#pragma unroll
-      for (int b = 0; b < 3; ++b) {
-        acc[3 + b] += B[0][b];
-        acc[8 + b] += B[1][b];
-        acc[12 + b] += B[2][b];
-        acc[21 + b] += wAe[b];
-        acc[24 + b] = vfma<V>(M[0][b], wAe[0], vfma<V>(M[1][b], wAe[1], vfma<V>(M[2][b], wAe[2], acc[24 + b])));
-      }
-      int k = 15;
-#pragma unroll
-      for (int p = 0; p < 3; ++p)
-#pragma unroll
-        for (int q = p; q < 3; ++q) {
-          acc[k] = vfma<V>(M[0][p], B[0][q], vfma<V>(M[1][p], B[1][q], vfma<V>(M[2][p], B[2][q], acc[k])));
-          ++k;
-        }
-      acc[27] += rho2;
-    }
+    const V p3[3] = {x[0], x[1], x[2]}, mu3[3] = {x[3], x[4], x[5]};
+    const V U6[6] = {x[6], x[7], x[8], x[9], x[10], x[11]};
+    item_U<V>(p3, mu3, U6, P, acc);
   }
   __device__ static __forceinline__ void item(const T (&x)[kNdtStreamed], const Params& P, bool valid, T (&acc)[28]) {
     const bool v1[1] = {valid};
     item<T>(x, P, v1, acc);
   }
 
-  // The A form (flat datasets store A = SᵀS, the voxel table of the indexed layout too).  With J = [S | S M]:
-  //   s = rᵀr = eᵀAe,  g = w [A e ; Mᵀ A e],  H = w [A, A M ; · , Mᵀ A M]
-  // — ≈ 144 instead of ≈ 190 operations per correspondence, 12 instead of 15 values per flat record.
-  __device__ static __forceinline__ void item_A(const T (&p)[3], const T (&mu)[3], const T (&A)[6], const Params& P,
-                                                T (&acc)[28]) {
-    T e[3], Ae[3], M[3][3], B[3][3];
+  // The U form (flat datasets store the triangular factor U of S = QU, the voxel table of the indexed layout too).  With
+  // J = [S | S M] and Qᵀ orthogonal, J' = QᵀJ = [U | U M] and r' = Qᵀr = U e give the same sums as the reference's S form:
+  //   s = r'ᵀr',  g = w J'ᵀr',  H = w J'ᵀJ'
+  // — ≈ 140 instead of ≈ 190 operations per correspondence, 12 instead of 15 values per flat record.  U is triangular, so
+  // C = U M and the blocks of J'ᵀJ' cost 1 + 2 + 3 products per column.
+  template <typename V = T>
+  __device__ static __forceinline__ void item_U(const V (&p)[3], const V (&mu)[3], const V (&U)[6], const Params& P,
+                                                V (&acc)[28]) {
+    V e[3], r[3], M[3][3], C[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
-      e[i] = fma(P.R[3 * i], p[0], fma(P.R[3 * i + 1], p[1], fma(P.R[3 * i + 2], p[2], P.t[i]))) - mu[i];
-    const T a00 = A[0], a01 = A[1], a02 = A[2], a11 = A[3], a12 = A[4], a22 = A[5];
-    Ae[0] = fma(a00, e[0], fma(a01, e[1], a02 * e[2]));
-    Ae[1] = fma(a01, e[0], fma(a11, e[1], a12 * e[2]));
-    Ae[2] = fma(a02, e[0], fma(a12, e[1], a22 * e[2]));
-    const T s = fma(e[0], Ae[0], fma(e[1], Ae[1], e[2] * Ae[2]));
-    T rho, w;
-    loss_eval<T, LOSS>(s, P.la, P.lb, P.lc, rho, w);
-    minus_R_hat<T>(P.R, p[0], p[1], p[2], M);
+      e[i] = sfma<V>(P.R[3 * i], p[0], sfma<V>(P.R[3 * i + 1], p[1], sfma<V>(P.R[3 * i + 2], p[2], splat<V>(P.t[i])))) - mu[i];
+    const V u00 = U[0], u01 = U[1], u02 = U[2], u11 = U[3], u12 = U[4], u22 = U[5];
+    r[0] = vfma<V>(u00, e[0], vfma<V>(u01, e[1], u02 * e[2]));
+    r[1] = vfma<V>(u11, e[1], u12 * e[2]);
+    r[2] = u22 * e[2];
+    const V s = vfma<V>(r[0], r[0], vfma<V>(r[1], r[1], r[2] * r[2]));
+    V rho, w;
+    loss_eval_v<V, LOSS>(s, P.la, P.lb, P.lc, rho, w);
+    minus_R_hat<V>(P.R, p[0], p[1], p[2], M);
 #pragma unroll
     for (int b = 0; b < 3; ++b) {
-      B[0][b] = fma(a00, M[0][b], fma(a01, M[1][b], a02 * M[2][b]));
-      B[1][b] = fma(a01, M[0][b], fma(a11, M[1][b], a12 * M[2][b]));
-      B[2][b] = fma(a02, M[0][b], fma(a12, M[1][b], a22 * M[2][b]));
+      C[0][b] = vfma<V>(u00, M[0][b], vfma<V>(u01, M[1][b], u02 * M[2][b]));
+      C[1][b] = vfma<V>(u11, M[1][b], u12 * M[2][b]);
+      C[2][b] = u22 * M[2][b];
     }
-    // upper triangle, row-major: rows 0-2 = [A | B], rows 3-5 = MᵀB
-    acc[0] = fma(w, a00, acc[0]);
-    acc[1] = fma(w, a01, acc[1]);
-    acc[2] = fma(w, a02, acc[2]);
-    acc[3] = fma(w, B[0][0], acc[3]);
-    acc[4] = fma(w, B[0][1], acc[4]);
-    acc[5] = fma(w, B[0][2], acc[5]);
-    acc[6] = fma(w, a11, acc[6]);
-    acc[7] = fma(w, a12, acc[7]);
-    acc[8] = fma(w, B[1][0], acc[8]);
-    acc[9] = fma(w, B[1][1], acc[9]);
-    acc[10] = fma(w, B[1][2], acc[10]);
-    acc[11] = fma(w, a22, acc[11]);
-    acc[12] = fma(w, B[2][0], acc[12]);
-    acc[13] = fma(w, B[2][1], acc[13]);
-    acc[14] = fma(w, B[2][2], acc[14]);
-    int k = 15;
+    // upper triangle, row-major: rows 0-2 = [UᵀU | UᵀC], rows 3-5 = CᵀC
+    acc[0] = vfma<V>(w, u00 * u00, acc[0]);
+    acc[1] = vfma<V>(w, u00 * u01, acc[1]);
+    acc[2] = vfma<V>(w, u00 * u02, acc[2]);
+    acc[6] = vfma<V>(w, vfma<V>(u01, u01, u11 * u11), acc[6]);
+    acc[7] = vfma<V>(w, vfma<V>(u01, u02, u11 * u12), acc[7]);
+    acc[11] = vfma<V>(w, vfma<V>(u02, u02, vfma<V>(u12, u12, u22 * u22)), acc[11]);
+    if constexpr (sizeof(typename Lanes<V>::S) == 4) {
+      // fp32: w folded into C and r' once (wC, wr), every entry that reads them a plain fma chain — 9 operations fewer;
+      // fp64 keeps acc += w · (dot product): the 12 extra live values spill the voxel-indexed kernel's pipeline
+      V wC[3][3], wr[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a)
+      for (int k = 0; k < 3; ++k) {
+        wr[k] = w * r[k];
 #pragma unroll
-      for (int b = a; b < 3; ++b) {
-        const T c = fma(M[0][a], B[0][b], fma(M[1][a], B[1][b], M[2][a] * B[2][b]));
-        acc[k] = fma(w, c, acc[k]);
-        ++k;
+        for (int b = 0; b < 3; ++b) wC[k][b] = w * C[k][b];
       }
 #pragma unroll
-    for (int i = 0; i < 3; ++i) acc[21 + i] = fma(w, Ae[i], acc[21 + i]);
+      for (int b = 0; b < 3; ++b) {
+        acc[3 + b] = vfma<V>(u00, wC[0][b], acc[3 + b]);
+        acc[8 + b] = vfma<V>(u01, wC[0][b], vfma<V>(u11, wC[1][b], acc[8 + b]));
+        acc[12 + b] = vfma<V>(u02, wC[0][b], vfma<V>(u12, wC[1][b], vfma<V>(u22, wC[2][b], acc[12 + b])));
+      }
+      int k = 15;
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const T gw = fma(M[0][b], Ae[0], fma(M[1][b], Ae[1], M[2][b] * Ae[2]));
-      acc[24 + b] = fma(w, gw, acc[24 + b]);
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) {
+          acc[k] = vfma<V>(C[0][a], wC[0][b], vfma<V>(C[1][a], wC[1][b], vfma<V>(C[2][a], wC[2][b], acc[k])));
+          ++k;
+        }
+      acc[21] = vfma<V>(u00, wr[0], acc[21]);
+      acc[22] = vfma<V>(u01, wr[0], vfma<V>(u11, wr[1], acc[22]));
+      acc[23] = vfma<V>(u02, wr[0], vfma<V>(u12, wr[1], vfma<V>(u22, wr[2], acc[23])));
+#pragma unroll
+      for (int b = 0; b < 3; ++b)
+        acc[24 + b] = vfma<V>(C[0][b], wr[0], vfma<V>(C[1][b], wr[1], vfma<V>(C[2][b], wr[2], acc[24 + b])));
+    } else {
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        acc[3 + b] = vfma<V>(w, u00 * C[0][b], acc[3 + b]);
+        acc[8 + b] = vfma<V>(w, vfma<V>(u01, C[0][b], u11 * C[1][b]), acc[8 + b]);
+        acc[12 + b] = vfma<V>(w, vfma<V>(u02, C[0][b], vfma<V>(u12, C[1][b], u22 * C[2][b])), acc[12 + b]);
+      }
+      int k = 15;
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) {
+          acc[k] = vfma<V>(w, vfma<V>(C[0][a], C[0][b], vfma<V>(C[1][a], C[1][b], C[2][a] * C[2][b])), acc[k]);
+          ++k;
+        }
+      acc[21] = vfma<V>(w, u00 * r[0], acc[21]);
+      acc[22] = vfma<V>(w, vfma<V>(u01, r[0], u11 * r[1]), acc[22]);
+      acc[23] = vfma<V>(w, vfma<V>(u02, r[0], vfma<V>(u12, r[1], u22 * r[2])), acc[23]);
+#pragma unroll
+      for (int b = 0; b < 3; ++b)
+        acc[24 + b] = vfma<V>(w, vfma<V>(C[0][b], r[0], vfma<V>(C[1][b], r[1], C[2][b] * r[2])), acc[24 + b]);
     }
     acc[27] += rho;
   }
@@ -397,7 +390,7 @@ struct Ndt6Problem {
 
 template <typename T, int LOSS>
 struct Ndt3Problem {
-  // fp64: p, mu, A (item_A).  fp32 keeps the S form — p, mu and S (row-major) — and reads S from the dataset's S region:
+  // fp64: p, mu, U (item_U).  fp32 keeps the S form — p, mu and S (row-major) — and reads S from the dataset's S region:
   // its sums are pinned to the printed digit (tests/test_simd_class.py)
   static constexpr bool kSPlanes = sizeof(T) == 4;
   static constexpr int kFields = kSPlanes ? 15 : kNdtStreamed;
@@ -409,8 +402,8 @@ struct Ndt3Problem {
                                               V (&acc)[10]) {
     if constexpr (!kSPlanes) {
       const T p3[3] = {x[0], x[1], x[2]}, mu3[3] = {x[3], x[4], x[5]};
-      const T A6[6] = {x[6], x[7], x[8], x[9], x[10], x[11]};
-      item_A(p3, mu3, A6, P, acc);
+      const T U6[6] = {x[6], x[7], x[8], x[9], x[10], x[11]};
+      item_U(p3, mu3, U6, P, acc);
     } else {
       item_S<V>(x, P, acc);
     }
@@ -457,9 +450,10 @@ struct Ndt3Problem {
     item<T>(x, P, v1, acc);
   }
 
-  // A form (flat fp64 datasets, the voxel table of the indexed layout) with A = SᵀS: J = [S(:,0) S(:,1) S(:,0:2)·d] ⇒ JᵀJ = [[a00, a01, q0], [·, a11, q1], [·, ·, dᵀq]]
-  // with q = A(0:2,0:2)·d, and Jᵀr = [Ae₀, Ae₁, d·(Ae)(0:2)].
-  __device__ static __forceinline__ void item_A(const T (&p)[3], const T (&mu)[3], const T (&A)[6], const Params& P,
+  // U form (flat fp64 datasets, the voxel table of the indexed layout) with S = QU: J' = [U(:,0) U(:,1) U(:,0:2)·d] — U is
+  // upper triangular, so J'(:,0) = (u00, 0, 0), J'(:,1) = (u01, u11, 0), J'(:,2) = (u00 d0 + u01 d1, u11 d1, 0) — and
+  // r' = U e.
+  __device__ static __forceinline__ void item_U(const T (&p)[3], const T (&mu)[3], const T (&U)[6], const Params& P,
                                                 T (&acc)[10]) {
     const T ux = p[0], uy = p[1];
     T e[3];
@@ -468,24 +462,25 @@ struct Ndt3Problem {
     e[2] = p[2] - mu[2];
     const T d0 = fma(P.R2[1], ux, -(P.R2[0] * uy));
     const T d1 = fma(P.R2[3], ux, -(P.R2[2] * uy));
-    const T a00 = A[0], a01 = A[1], a02 = A[2], a11 = A[3], a12 = A[4], a22 = A[5];
-    const T Ae0 = fma(a00, e[0], fma(a01, e[1], a02 * e[2]));
-    const T Ae1 = fma(a01, e[0], fma(a11, e[1], a12 * e[2]));
-    const T Ae2 = fma(a02, e[0], fma(a12, e[1], a22 * e[2]));
-    const T s = fma(e[0], Ae0, fma(e[1], Ae1, e[2] * Ae2));
+    const T u00 = U[0], u01 = U[1], u02 = U[2], u11 = U[3], u12 = U[4], u22 = U[5];
+    const T r0 = fma(u00, e[0], fma(u01, e[1], u02 * e[2]));
+    const T r1 = fma(u11, e[1], u12 * e[2]);
+    const T r2 = u22 * e[2];
+    const T s = fma(r0, r0, fma(r1, r1, r2 * r2));
     T rho, w;
     loss_eval<T, LOSS>(s, P.la, P.lb, P.lc, rho, w);
-    const T q0 = fma(a00, d0, a01 * d1);
-    const T q1 = fma(a01, d0, a11 * d1);
-    acc[0] = fma(w, a00, acc[0]);
-    acc[1] = fma(w, a01, acc[1]);
-    acc[2] = fma(w, q0, acc[2]);
-    acc[3] = fma(w, a11, acc[3]);
-    acc[4] = fma(w, q1, acc[4]);
-    acc[5] = fma(w, fma(d0, q0, d1 * q1), acc[5]);
-    acc[6] = fma(w, Ae0, acc[6]);
-    acc[7] = fma(w, Ae1, acc[7]);
-    acc[8] = fma(w, fma(d0, Ae0, d1 * Ae1), acc[8]);
+    const T c0 = fma(u00, d0, u01 * d1);
+    const T c1 = u11 * d1;
+    const T w00 = w * u00, w01 = w * u01, w11 = w * u11, wc0 = w * c0, wc1 = w * c1;
+    acc[0] = fma(w00, u00, acc[0]);
+    acc[1] = fma(w00, u01, acc[1]);
+    acc[2] = fma(w00, c0, acc[2]);
+    acc[3] = fma(w01, u01, fma(w11, u11, acc[3]));
+    acc[4] = fma(w01, c0, fma(w11, c1, acc[4]));
+    acc[5] = fma(wc0, c0, fma(wc1, c1, acc[5]));
+    acc[6] = fma(w00, r0, acc[6]);
+    acc[7] = fma(w01, r0, fma(w11, r1, acc[7]));
+    acc[8] = fma(wc0, r0, fma(wc1, r1, acc[8]));
     acc[9] += rho;
   }
 };

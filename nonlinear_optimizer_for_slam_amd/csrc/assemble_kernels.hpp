@@ -9,7 +9,7 @@
 // the block's waves → one row of `partials`, then a fixed-order final pass → 28 doubles.
 // No atomics, so results are bit-reproducible for a fixed launch geometry.
 //
-// Bound: HBM bandwidth (NDT: p, mu and A = SᵀS, 96 B fp64 / 48 B fp32 per correspondence, ≈150 VALU ops); the
+// Bound: HBM bandwidth (NDT: p, mu and U with S = QU, 96 B fp64 / 48 B fp32 per correspondence, ≈150 VALU ops); the
 // contraction is a fixed 6×6 outer product so MFMA is deliberately not used.
 //
 // Math restated from (reference paths relative to nonlinear_optimizer/):

@@ -95,17 +95,17 @@ __global__ __launch_bounds__(1024) void final_reduce_kernel(const double* __rest
 // ---------------------------------------------------------------- ingestion kernels
 
 // One flat NDT record (p, mu, S row-major, already in the dataset's element type) → its 21 stored planes: p, mu, S and
-// A = SᵀS computed from the stored S (sqrt_info_to_A).  An all-zero record stores all zeros.
+// the triangular factor U of S = QU computed from the stored S (sqrt_info_to_U).  An all-zero record stores all zeros.
 template <typename DST>
 __device__ __forceinline__ void store_ndt_record(const TiledLayout& L, DST* __restrict__ dst, uint64_t i, const DST (&x)[15]) {
-  DST S[9], A[6];
+  DST S[9], U[6];
 #pragma unroll
   for (int k = 0; k < 9; ++k) S[k] = x[6 + k];
-  sqrt_info_to_A<DST>(S, A);
+  sqrt_info_to_U<DST>(S, U);
 #pragma unroll
   for (int f = 0; f < 15; ++f) dst[plane_offset(L, i, ndt_stored_plane(f))] = x[f];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) dst[plane_offset(L, i, 6 + k)] = A[k];
+  for (int k = 0; k < 6; ++k) dst[plane_offset(L, i, 6 + k)] = U[k];
 }
 
 // planar source planes (5 pointers, element type SRC) → tiled layout of DST, zero pads (reprojection).
@@ -166,19 +166,19 @@ __global__ __launch_bounds__(256) void unpack_records_kernel(const unsigned char
   }
 }
 
-// The A planes of items [first, first + count) of a flat NDT dataset from its stored S (the host-pack ingestion copies
-// p, mu and S into place; A is computed here, on the device, in the element type of the dataset).
+// The U planes of items [first, first + count) of a flat NDT dataset from its stored S (the host-pack ingestion copies
+// p, mu and S into place; U is computed here, on the device, from S in the element type of the dataset).
 template <typename T>
-__global__ __launch_bounds__(256) void ndt_a_planes_kernel(TiledLayout L, T* __restrict__ dst, uint64_t first, uint64_t count) {
+__global__ __launch_bounds__(256) void ndt_u_planes_kernel(TiledLayout L, T* __restrict__ dst, uint64_t first, uint64_t count) {
   const uint64_t j = uint64_t(blockIdx.x) * 256 + threadIdx.x;
   if (j >= count) return;
   const uint64_t i = first + j;
-  T S[9], A[6];
+  T S[9], U[6];
 #pragma unroll
   for (int k = 0; k < 9; ++k) S[k] = dst[plane_offset(L, i, kNdtStreamed + k)];
-  sqrt_info_to_A<T>(S, A);
+  sqrt_info_to_U<T>(S, U);
 #pragma unroll
-  for (int k = 0; k < 6; ++k) dst[plane_offset(L, i, 6 + k)] = A[k];
+  for (int k = 0; k < 6; ++k) dst[plane_offset(L, i, 6 + k)] = U[k];
 }
 
 // n_fields: stored planes (flat NDT: 21)

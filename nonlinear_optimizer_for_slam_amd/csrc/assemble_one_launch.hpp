@@ -183,12 +183,11 @@ __device__ __forceinline__ void state_load_sc1(const LmDevice* lm, nos_host::LmS
 //   reprojection fp32 (20 B)          : 10 + 14 → 24      → 3 145 728
 // i.e. at these sizes an LM iteration touches neither HBM nor the caches: its cost is the item math plus one grid-wide
 // hand-off.  The first touch (one pass over the dataset) is paid once per solve.
-// A resident NDT correspondence is what the dataset stores and the streamed form reads: {p, mu, A = SᵀS} — the solvers only
-// ever need A of the sqrt-information (with J = [S | S M]: s = eᵀAe, g = w [Ae ; MᵀAe], H = w [A, AM ; ·, MᵀAM] —
-// Ndt6Problem::item_A / Ndt3Problem::item_A).  A is computed ONCE, when the dataset is made (nos_core.hip), with the
-// expression the resident form used to apply at first touch: 12 values instead of 15 per item, ≈ 35 % fewer instructions
-// per item and iteration (fp64: 233 → ≈ 150), and 96 instead of 120 B per correspondence and iteration where the data is
-// streamed.  The fp32 3-DoF item keeps S (Ndt3Problem::kSPlanes).
+// A resident NDT correspondence is what the dataset stores and the streamed form reads: {p, mu, U} with S = QU — the solvers
+// only need S up to an orthogonal factor on the left (J' = QᵀJ = [U | U M], r' = U e: the same s, g and H —
+// Ndt6Problem::item_U / Ndt3Problem::item_U).  U is computed ONCE, when the dataset is made (nos_core.hip, sqrt_info_to_U):
+// 12 values instead of 15 per item, ≈ 35 % fewer instructions per item and iteration than the S form, and 96 instead of
+// 120 B per correspondence and iteration where the data is streamed.  The fp32 3-DoF item keeps S (Ndt3Problem::kSPlanes).
 // The shape is chosen by the planes of the caller's record (Problem::kPlanes), so an fp32 item keeps the mapping of items to
 // lanes — and with it the order of the reduction — of the S form.
 template <int FIELDS, int ELEM>

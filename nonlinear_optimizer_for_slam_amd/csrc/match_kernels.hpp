@@ -194,17 +194,17 @@ __global__ __launch_bounds__(256) void match_kernel(MapView map, const double* _
 #pragma unroll
     for (int f = 0; f < 3; ++f)
       put(3 + f, ok0 ? DST(map.mean[3 * size_t(best_j[0]) + f]) : DST(0), ok1 ? DST(map.mean[3 * size_t(best_j[1]) + f]) : DST(0));
-    DST S0[9], S1[9], A0[6], A1[6];
+    DST S0[9], S1[9], U0[6], U1[6];
 #pragma unroll
     for (int f = 0; f < 9; ++f) {
       S0[f] = ok0 ? DST(map.sqrt_info[9 * size_t(best_j[0]) + f]) : DST(0);
       S1[f] = ok1 ? DST(map.sqrt_info[9 * size_t(best_j[1]) + f]) : DST(0);
       put(ndt_stored_plane(6 + f), S0[f], S1[f]);
     }
-    sqrt_info_to_A<DST>(S0, A0);
-    sqrt_info_to_A<DST>(S1, A1);
+    sqrt_info_to_U<DST>(S0, U0);
+    sqrt_info_to_U<DST>(S1, U1);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) put(6 + k, A0[k], A1[k]);
+    for (int k = 0; k < 6; ++k) put(6 + k, U0[k], U1[k]);
   }
   // match count: wave sum → one atomic per wave (integer, order independent)
   int s = found;
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(64) void drop_last_matches_kernel(T* __restrict__ d
       for (int f = 6; f < 15; ++f) nonempty = nonempty || data[plane_offset(L, i, ndt_stored_plane(f))] != T(0);
     const unsigned long long mask = __ballot(nonempty);
     const uint64_t before = uint64_t(__popcll(mask & ((1ull << lane) - 1ull)));  // non-empty slots nearer to the end
-    if (nonempty && before < remaining)  // all 21 stored planes (A as well): the cleared record contributes nothing
+    if (nonempty && before < remaining)  // all 21 stored planes (U as well): the cleared record contributes nothing
       for (int f = 0; f < kNdtStored; ++f) data[plane_offset(L, i, f)] = T(0);
     const uint64_t found = uint64_t(__popcll(mask));
     remaining -= found < remaining ? found : remaining;

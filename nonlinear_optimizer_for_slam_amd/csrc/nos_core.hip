@@ -1088,7 +1088,7 @@ int alloc_shards(nos_ctx* ctx, nos_dataset* ds) {
 template <typename SRC>
 int retile_dispatch(const nos::PlanePtrs& src, int n_fields, const nos::TiledLayout& L, void* dst, int dtype,
                     hipStream_t stream) {
-  if (n_fields == NOS_NDT_PLANES) {  // flat NDT: one item per thread, its A planes computed on the way
+  if (n_fields == NOS_NDT_PLANES) {  // flat NDT: one item per thread, its U planes computed on the way
     const dim3 grid1(unsigned((L.n_padded + 255) / 256));
     if (dtype == NOS_F64)
       hipLaunchKernelGGL((nos::retile_ndt_kernel<SRC, double>), grid1, dim3(256), 0, stream, src, L, static_cast<double*>(dst));
@@ -1380,13 +1380,13 @@ int ingest_host_pack(nos_ctx* ctx, nos_dataset* ds, Shard& sh, const unsigned ch
   if (e == hipSuccess) e = hipStreamSynchronize(slot.copy_stream);
   if (e != hipSuccess)
     return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "host-pack ingestion failed: %s", hipGetErrorString(e));
-  if (ndt && cnt > 0) {  // A = SᵀS from the S just copied, in the dataset's element type
+  if (ndt && cnt > 0) {  // U (S = QU) from the S just copied, in the dataset's element type
     const dim3 grid(unsigned((cnt + 255) / 256));
     if (f64)
-      hipLaunchKernelGGL((nos::ndt_a_planes_kernel<double>), grid, dim3(256), 0, slot.stream, sh.layout,
+      hipLaunchKernelGGL((nos::ndt_u_planes_kernel<double>), grid, dim3(256), 0, slot.stream, sh.layout,
                          static_cast<double*>(sh.data), uint64_t(0), uint64_t(cnt));
     else
-      hipLaunchKernelGGL((nos::ndt_a_planes_kernel<float>), grid, dim3(256), 0, slot.stream, sh.layout,
+      hipLaunchKernelGGL((nos::ndt_u_planes_kernel<float>), grid, dim3(256), 0, slot.stream, sh.layout,
                          static_cast<float*>(sh.data), uint64_t(0), uint64_t(cnt));
     NOS_HIP_CHECK(hipGetLastError());
   }
@@ -1919,7 +1919,7 @@ size_t nos_dataset_stream_bytes(const nos_dataset* ds) {
   if (!ds) return 0;
   if (ds->kind == kKindNdtIndexed)  // point (3 values) + one 4-byte voxel id per slot; the voxel table is cache resident
     return ds->n * (3 * elem_size(ds->dtype) + sizeof(int32_t) * size_t(ds->shards.empty() ? 0 : ds->shards[0].n_slots));
-  // flat datasets: the planes of the caller's record (nos.h).  Flat NDT kernels stream 12 of the 15 (p, mu, A = SᵀS;
+  // flat datasets: the planes of the caller's record (nos.h).  Flat NDT kernels stream 12 of the 15 (p, mu, U with S = QU;
   // fp32 3-DoF: p, mu, S) — the figure stays the record's, which the test suite pins.
   return ds->n * size_t(ds->n_fields) * elem_size(ds->dtype);
 }
