@@ -152,10 +152,21 @@ def ndt6_items(planes, R, t, dtype=LD, order="ref"):
     return r, J
 
 
-def ndt6_accumulate(planes, R, t, loss=None, dtype=LD, order="ref"):
+def _terms(w, J, r, rho, dim):
+    """Per-item terms of {upper(H) | g | cost}: an [n_out, n] array in the precision of r (their sums are _sums')."""
+    rows = len(J)
+    out = [w * sum(J[k][i] * J[k][j] for k in range(rows)) for i, j in (TRI6 if dim == 6 else TRI3)]
+    out += [w * sum(J[k][i] * r[k] for k in range(rows)) for i in range(dim)]
+    return np.array(out + [rho])
+
+
+def ndt6_accumulate(planes, R, t, loss=None, dtype=LD, order="ref", terms=False):
+    """terms=True: the per-item terms ([28, n]) instead of their sums."""
     r, J = ndt6_items(planes, R, t, dtype, order)
     s = r[0] * r[0] + r[1] * r[1] + r[2] * r[2]
     rho, w = loss_eval(loss, s)
+    if terms:
+        return _terms(w, J, r, rho, 6)
     H, g, cost = _sums(w, J, r, rho, 6)
     return _pack(H, g, cost, TRI6)
 
@@ -180,15 +191,17 @@ def ndt3_items(planes, R2, t2, dtype=LD, order="ref"):
     return r, J
 
 
-def ndt3_accumulate(planes, R2, t2, loss=None, dtype=LD, order="ref"):
+def ndt3_accumulate(planes, R2, t2, loss=None, dtype=LD, order="ref", terms=False):
     r, J = ndt3_items(planes, R2, t2, dtype, order)
     s = r[0] * r[0] + r[1] * r[1] + r[2] * r[2]
     rho, w = loss_eval(loss, s)
+    if terms:
+        return _terms(w, J, r, rho, 3)
     H, g, cost = _sums(w, J, r, rho, 3)
     return _pack(H, g, cost, TRI3)
 
 
-def reproj_accumulate(planes, R, t, intr, loss=None, min_depth=0.03, dtype=LD):
+def reproj_accumulate(planes, R, t, intr, loss=None, min_depth=0.03, dtype=LD, terms=False):
     """The scalar class's rule: a correspondence with depth z < min_depth contributes nothing."""
     planes = np.asarray(planes, dtype=np.float64)
     R64, t64 = np.asarray(R, dtype=np.float64).reshape(3, 3), np.asarray(t, dtype=np.float64)
@@ -215,8 +228,29 @@ def reproj_accumulate(planes, R, t, intr, loss=None, min_depth=0.03, dtype=LD):
     J = [[np.where(ok, v, zero) for v in row] for row in J]
     s = r[0] * r[0] + r[1] * r[1]
     rho, w = loss_eval(loss, s)
+    if terms:
+        return _terms(w, J, r, rho, 6)
     H, g, cost = _sums(w, J, r, rho, 6)
     return _pack(H, g, cost, TRI6)
+
+
+def period_sums(terms, prefixes=()):
+    """Sums of a period's per-item terms (the `terms=True` output of an *_accumulate, in longdouble), for references of
+    datasets that tile that period: → (S_P, {r: S_r}, A_P, {r: A_r}) — the period's sums, the sums of its first r items,
+    and Σ|term| of both, per quantity."""
+    terms = np.asarray(terms, dtype=LD)
+    mag = np.abs(terms)
+    return (terms.sum(axis=1), {r: terms[:, :r].sum(axis=1) for r in prefixes},
+            mag.sum(axis=1), {r: mag[:, :r].sum(axis=1) for r in prefixes})
+
+
+def tiled_sums(terms, n):
+    """Reference sums of the first n items of the period `terms` ([n_out, P]) repeated: n = K·P + r → K·S_P + S_r, and
+    Σ|term| likewise (longdouble).  Costs one pass over the period, whatever n is."""
+    P = np.asarray(terms).shape[1]
+    K, r = divmod(int(n), P)
+    SP, Sr, AP, Ar = period_sums(terms, (r,))
+    return LD(K) * SP + Sr[r], LD(K) * AP + Ar[r]
 
 
 def unpack(out, dim):

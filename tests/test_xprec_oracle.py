@@ -191,3 +191,28 @@ def test_reprojection_threshold_case_counts_the_point_at_min_depth():
     out = xp.reproj_accumulate(planes, R, t, intr, None)
     H, _, _ = xp.unpack(out, 6)
     assert H[0, 0] == pytest.approx(5 / 0.03 ** 2, rel=1e-15)  # five points at z = min_depth, each with J00 = 1/z
+
+
+@pytest.mark.parametrize("kind", ["ndt6", "ndt3", "reproj"])
+def test_tiled_reference_equals_the_direct_sum(kind):
+    """period_sums / tiled_sums: the reference of a dataset that repeats a period P (n = K·P + r) from one pass over the
+    period equals the direct longdouble sum over the n items — P = 101, 3 periods plus a 37-item tail."""
+    P, n = 101, 3 * 101 + 37
+    rng = np.random.default_rng(5)
+    if kind == "reproj":
+        planes = np.concatenate([rng.uniform(-1, 1, (2, P)), rng.uniform(0.5, 4, (1, P)), rng.uniform(0, 600, (2, P))])
+        args = (np.eye(3), np.array([0.01, -0.02, 0.03]), (1 / 525.0, 1 / 525.0, 320.0, 240.0), ("huber", 0.01))
+        fn, dim = xp.reproj_accumulate, 6
+    else:
+        planes = np.concatenate([rng.uniform(-5, 5, (6, P)), rng.uniform(-1, 1, (9, P))])
+        if kind == "ndt6":
+            args, fn, dim = (np.eye(3), np.array([0.1, -0.2, 0.05]), ("exponential", 1.0, 1.0)), xp.ndt6_accumulate, 6
+        else:
+            args, fn, dim = (np.eye(2), np.array([0.1, -0.2]), ("huber", 0.5)), xp.ndt3_accumulate, 3
+    terms = fn(planes, *args, terms=True)
+    want = fn(np.tile(planes, 4)[:, :n], *args)
+    got, mag = xp.tiled_sums(terms, n)
+    assert max(xp.scaled_errors_ld(got, want, dim)) < 1e-17
+    assert np.all(mag >= np.abs(got)) and np.all(mag >= 0)
+    # the sums of the per-item terms are the accumulate's sums
+    assert max(xp.scaled_errors_ld(xp.period_sums(terms)[0], fn(planes, *args), dim)) < 1e-17
