@@ -206,15 +206,16 @@ struct ResidentShape<5, 4> { static constexpr int RI = 10, LI = 14; };
 // correspondences taken grid-stride exactly like assemble_kernel does — but the loop still lives in ONE launch: no kernel
 // boundary, no launch prologue and no ticket + last-block reduce per iteration (≈ 5 µs of every iteration at 10 M), the
 // tagged all-reduce instead, and the first chunk of iteration k + 1 is already in flight while iteration k is being
-// reduced and stepped (it does not depend on the pose).  `items_per_lane` then carries the number of chunks.  SPF: the
-// next chunk's loads are issued before the current chunk is evaluated (fp32), NT: non-temporal loads.
+// reduced and stepped (it does not depend on the pose).  `items_per_lane` then carries the number of chunks, and
+// `stream_lds` the number of chunks every workgroup keeps in dynamic LDS from iteration 1 on (below).  SPF: the next
+// chunk's loads are issued before the current chunk is evaluated (fp32), NT: non-temporal loads.
 template <typename Problem, typename T, int BLOCK, int RI, int LI, int SI = 0, bool SPF = false, bool NT = false>
 __global__ __launch_bounds__(BLOCK) void solve_cluster_kernel(TiledLayout L, typename Problem::Params P,
                                                              double* __restrict__ partials, LmDevice* lm, ClusterCtl* ctl,
                                                              double* __restrict__ cost_history, int history_capacity,
                                                              double* entry_host, unsigned long long* seq_host,
                                                              unsigned long long seq, uint32_t items_per_lane,
-                                                             const Mailbox* mail = nullptr) {
+                                                             const Mailbox* mail = nullptr, uint32_t stream_lds = 0u) {
   // mail != nullptr (device-memory mailbox communicator, one process per GPU): the sums of every iteration are exchanged with
   // the other ranks INSIDE this launch — a third stage behind the two of the tagged all-reduce (below)
   constexpr int kF = Problem::kFields;
@@ -262,13 +263,26 @@ __global__ __launch_bounds__(BLOCK) void solve_cluster_kernel(TiledLayout L, typ
   bool valid[RI > 0 ? RI : 1];
   static_assert(SI == 0 || (RI == 0 && LI == 0), "the streaming form keeps nothing resident");
   // streaming form: the chunk being evaluated next (the first one of every iteration is fetched ahead of time)
-  [[maybe_unused]] T xs[kF][SI > 0 ? SI : 1];
+  constexpr int kSI = SI > 0 ? SI : 1;
+  [[maybe_unused]] T xs[kF][kSI];
   [[maybe_unused]] uint64_t xs_i0 = 0;
-  [[maybe_unused]] auto fetch_chunk = [&](uint32_t c, T (&dst)[kF][SI > 0 ? SI : 1]) -> uint64_t {
-    const uint64_t i0 = uint64_t(c) * (uint64_t(BLOCK) * (SI > 0 ? SI : 1)) + uint64_t(threadIdx.x) * (SI > 0 ? SI : 1);
+  // Streaming form, what stays on chip between iterations: `stream_lds` (grid-uniform, 0 … 3) of this workgroup's chunks.
+  // Workgroup b evaluates chunks b, b + grid, b + 2 grid, … — its "rounds" 0, 1, 2, … — in that order in every iteration,
+  // so one workgroup always reads the same chunks.  That many of its rounds, spread evenly through the pass and never
+  // round 0 (the one prefetched during the all-reduce), are copied to dynamic LDS ([slot][field][lane][SI]) as iteration 0
+  // streams them and read from there afterwards.  Every lane keeps its order of items: the same sums, bit for bit.
+  [[maybe_unused]] const uint32_t my_rounds = blockIdx.x < J ? (J - blockIdx.x + gridDim.x - 1) / gridDim.x : 0u;
+  [[maybe_unused]] const uint32_t lds_k = SI > 0 ? min(stream_lds, my_rounds > 0u ? my_rounds - 1u : 0u) : 0u;
+  // round of LDS slot s (s < lds_k: 1 ≤ r(0) < r(1) < r(2) < my_rounds), no round beyond the last slot
+  [[maybe_unused]] const uint32_t lds_r0 = lds_k > 0u ? my_rounds / (lds_k + 1u) : ~0u;
+  [[maybe_unused]] const uint32_t lds_r1 = lds_k > 1u ? uint32_t(2ull * my_rounds / (lds_k + 1u)) : ~0u;
+  [[maybe_unused]] const uint32_t lds_r2 = lds_k > 2u ? uint32_t(3ull * my_rounds / (lds_k + 1u)) : ~0u;
+  [[maybe_unused]] auto lds_round = [&](uint32_t s) -> uint32_t { return s == 0u ? lds_r0 : s == 1u ? lds_r1 : s == 2u ? lds_r2 : ~0u; };
+  [[maybe_unused]] auto fetch_chunk = [&](uint32_t c, T (&dst)[kF][kSI]) -> uint64_t {
+    const uint64_t i0 = uint64_t(c) * (uint64_t(BLOCK) * kSI) + uint64_t(threadIdx.x) * kSI;
     const uint64_t off = (i0 >> L.tile_shift) * L.tile_stride + (i0 & L.tile_mask);
 #pragma unroll
-    for (int f = 0; f < kF; ++f) load_items<T, (SI > 0 ? SI : 1), NT>(base + field_offset<Problem>(L, i0, off, f), dst[f]);
+    for (int f = 0; f < kF; ++f) load_items<T, kSI, NT>(base + field_offset<Problem>(L, i0, off, f), dst[f]);
     return i0;
   };
   if constexpr (SI > 0) {
@@ -337,9 +351,8 @@ __global__ __launch_bounds__(BLOCK) void solve_cluster_kernel(TiledLayout L, typ
           Problem::item(xi, P, (i0 + it) < L.n, acc);
         }
       };
-      uint32_t c = blockIdx.x;
       if constexpr (SPF) {
-        for (; c < n_chunks; c += gridDim.x) {
+        for (uint32_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
           T xb[kF][SI > 0 ? SI : 1];
           uint64_t i1 = 0;
           const uint32_t cn = c + gridDim.x;
@@ -352,16 +365,55 @@ __global__ __launch_bounds__(BLOCK) void solve_cluster_kernel(TiledLayout L, typ
           xs_i0 = i1;
         }
       } else {
-        while (c < n_chunks) {
+        auto lds_at = [&](uint32_t s, int f, int e) -> T& {
+          return resident[((size_t(s) * kF + f) * BLOCK + threadIdx.x) * kSI + e];
+        };
+        auto evaluate_lds = [&](uint32_t s, uint32_t cl) {
+          const uint64_t i0 = uint64_t(cl) * (uint64_t(BLOCK) * kSI) + uint64_t(threadIdx.x) * kSI;
+#pragma unroll
+          for (int e = 0; e < kSI; ++e) {  // item by item
+            T xi[kF];
+#pragma unroll
+            for (int f = 0; f < kF; ++f) xi[f] = lds_at(s, f, e);
+            Problem::item(xi, P, (i0 + e) < L.n, acc);
+          }
+        };
+        // iteration 0 fills the LDS slots from the streamed registers; the later ones read them instead of streaming
+        const bool from_lds = it != 0u;  // grid-uniform
+        uint32_t s = 0;                  // LDS slot of the next resident round
+        uint32_t next_res = lds_round(0u);
+        auto evaluate_lds_rounds = [&](uint32_t k0, uint32_t k1) {  // rounds k0 … k1 - 1, all of them in LDS
+          for (uint32_t kr = k0; kr < k1; ++kr) {
+            evaluate_lds(s, blockIdx.x + kr * gridDim.x);
+            next_res = lds_round(++s);
+          }
+        };
+        // One trip per streamed round k; xs is written once per trip, whatever comes next, so that the loads land in the
+        // registers they are evaluated from (a conditional refill makes the compiler load into copies and wait for them).
+        for (uint32_t k = 0; k < my_rounds;) {  // block-uniform
           __builtin_amdgcn_sched_barrier(0);  // all loads of a chunk before any of its math (see assemble_kernel)
+          if (!from_lds && k == next_res) {  // iteration 0: keep this chunk
+#pragma unroll
+            for (int f = 0; f < kF; ++f)
+#pragma unroll
+              for (int e = 0; e < kSI; ++e) lds_at(s, f, e) = xs[f][e];
+            next_res = lds_round(++s);
+          }
           evaluate(xs, xs_i0);
-          c += gridDim.x;
-          if (c < n_chunks) xs_i0 = fetch_chunk(c, xs);
+          // the next streamed round, past the rounds that LDS serves
+          uint32_t kn = k + 1u;
+          if (from_lds)
+            for (uint32_t sn = s; kn == lds_round(sn); ++sn) ++kn;
+          // past the last round: the first chunk of the NEXT iteration, in flight during the all-reduce and the step below
+          // (every wave does, the polling ones too: letting only the other half prefetch measured 2 % slower at 10 M)
+          xs_i0 = fetch_chunk(blockIdx.x + (kn < my_rounds ? kn : 0u) * gridDim.x, xs);
+          evaluate_lds_rounds(k + 1u, kn);  // while those loads are in flight
+          k = kn;
         }
       }
-      // the first chunk of the NEXT iteration: in flight during the all-reduce and the step below
-      // (every wave does, the polling ones too: letting only the other half prefetch measured 2 % slower at 10 M)
-      if (blockIdx.x < n_chunks) xs_i0 = fetch_chunk(blockIdx.x, xs);
+      if constexpr (SPF) {
+        if (blockIdx.x < n_chunks) xs_i0 = fetch_chunk(blockIdx.x, xs);
+      }
     } else
     // (fp64 only: the fp32 kernels spill when their items are interleaved)
     if (sizeof(T) == 8 && J >= uint32_t(RI)) {  // grid-uniform; one straight-line block, so the scheduler can interleave the items

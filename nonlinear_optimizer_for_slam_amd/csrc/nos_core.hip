@@ -259,6 +259,7 @@ struct SingleBlockArgs {
   int items_per_lane = 1;  // correspondences every lane keeps resident (registers + LDS, nos::ResidentShape)
   int stream_chunks = 0;   // > 0: the streaming form (nothing resident; this many chunks of 512 x SI per iteration)
   bool nt = false;         // streaming form: non-temporal loads
+  int stream_lds_chunks = 0;      // streaming form: chunks per workgroup kept in LDS after iteration 0
   bool stage1_sc1 = false; // keep stage 1 of the tagged all-reduce on sc1 stores even where a group sits on one XCD (lm_cluster 5)
   const nos::Mailbox* mail = nullptr;  // device-memory mailbox communicator: the cross-rank exchange runs inside the launch
   double* partials = nullptr;
@@ -288,10 +289,20 @@ int launch_single(const nos::TiledLayout& L, const typename Problem::Params& P, 
     if (size_t(a.stream_chunks) * kChunk != L.n_padded) return fail(NOS_ERR_INVALID_ARGUMENT, "streaming solve: chunk count does not match the layout");
     const auto kernel = a.nt ? nos::solve_cluster_kernel<Problem, T, kBlock, 0, 0, kSI, kSPF, true>
                              : nos::solve_cluster_kernel<Problem, T, kBlock, 0, 0, kSI, kSPF, false>;
+    // chunks every workgroup keeps in LDS from iteration 1 on (the kernel clamps to its own chunk count)
+    uint32_t lds = uint32_t(std::min(std::max(a.stream_lds_chunks, 0), 3));
+    size_t dyn_bytes = lds * size_t(Problem::kFields) * kChunk * sizeof(T);
+    if (dyn_bytes > size_t(48) * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            int(dyn_bytes)) != hipSuccess) {
+      (void)hipGetLastError();  // LDS refused: stream everything, as without the option
+      lds = 0;
+      dyn_bytes = 0;
+    }
     t_last_kernel = reinterpret_cast<const void*>(kernel);
-    hipLaunchKernelGGL(kernel, dim3(a.cluster_blocks), dim3(kBlock), 0, stream, L, P, a.partials, a.lm, a.ctl, a.history,
+    hipLaunchKernelGGL(kernel, dim3(a.cluster_blocks), dim3(kBlock), dyn_bytes, stream, L, P, a.partials, a.lm, a.ctl, a.history,
                        a.history_capacity, a.entry, a.seq_host, a.seq, uint32_t(a.stream_chunks) | (a.stage1_sc1 ? 0x80000000u : 0u),
-                       a.mail);
+                       a.mail, lds);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(NOS_ERR_HIP, "streaming solve launch failed: %s", hipGetErrorString(e));
     return NOS_OK;
@@ -316,7 +327,7 @@ int launch_single(const nos::TiledLayout& L, const typename Problem::Params& P, 
     t_last_kernel = reinterpret_cast<const void*>(kernel);
     hipLaunchKernelGGL(kernel, dim3(a.cluster_blocks), dim3(kBlock), dyn_bytes, stream, L, P, a.partials, a.lm, a.ctl,
                        a.history, a.history_capacity, a.entry, a.seq_host, a.seq,
-                       uint32_t(a.items_per_lane) | (a.stage1_sc1 ? 0x80000000u : 0u), a.mail);
+                       uint32_t(a.items_per_lane) | (a.stage1_sc1 ? 0x80000000u : 0u), a.mail, 0u);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(NOS_ERR_HIP, "cluster solve launch failed: %s", hipGetErrorString(e));
     return NOS_OK;
@@ -817,6 +828,7 @@ int lm_solve(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, doub
       cl.items_per_lane = 0;
       cl.stream_chunks = int(sh.layout.n_padded / stream_chunk);
       cl.nt = use_nontemporal(ds, sh);
+      cl.stream_lds_chunks = ctx->settings.stream_lds_chunks;
     }
     cl.stage1_sc1 = ctx->settings.lm_cluster == 5;
     cl.mail = mailbox_in_launch ? ctx->d_mail : nullptr;
@@ -1550,6 +1562,7 @@ int nos_ctx_create(const int* device_ids, int n_devices, nos_ctx** out_ctx) {
     st.lm_single = env_int("NOS_LM_SINGLE", st.lm_single);
     st.lm_cluster = env_int("NOS_LM_CLUSTER", st.lm_cluster);
     st.lm_cluster_max_blocks = env_int("NOS_LM_CLUSTER_MAX_BLOCKS", st.lm_cluster_max_blocks);
+    st.stream_lds_chunks = env_int("NOS_STREAM_LDS_CHUNKS", st.stream_lds_chunks);
     st.pool = env_int("NOS_POOL", st.pool);
     st.tile_log2 = env_int("NOS_TILE_LOG2", int(kDefaultTileLog2));
     const char* ingest = getenv("NOS_INGEST");
@@ -1738,6 +1751,7 @@ const OptionEntry kOptions[] = {
     {"map_eigen_version", &nosd::Settings::map_eigen_version, 33, 34},
     {"debug_cluster_abort", &nosd::Settings::debug_cluster_abort, 0, 2},
     {"lm_cluster_max_blocks", &nosd::Settings::lm_cluster_max_blocks, 1, 256},
+    {"stream_lds_chunks", &nosd::Settings::stream_lds_chunks, 0, 3},
 };
 bool option_in_range(const OptionEntry& o, int value);
 void drop_out_of_range_settings(nosd::Settings& st) {

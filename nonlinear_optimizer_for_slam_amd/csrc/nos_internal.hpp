@@ -166,6 +166,8 @@ struct Settings {
   int debug_cluster_abort = 0;  // test hook (no environment name): the next one-launch solve finds `abort` raised; 2 = and the
                                 // give-up is remembered like a real one (the lm_cluster_retry_ms latch)
   int lm_cluster_max_blocks = 256;  // NOS_LM_CLUSTER_MAX_BLOCKS  workgroups of the one-launch loop (rehearsals: ranks sharing a GPU)
+  int stream_lds_chunks = 3;   // NOS_STREAM_LDS_CHUNKS  streamed one-launch loop: chunks per workgroup kept in LDS after
+                               //                        iteration 0 (0 … 3; 0 = everything streamed every iteration)
 };
 }  // namespace nosd
 
