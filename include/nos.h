@@ -397,6 +397,28 @@ int nos_reproj_solve(nos_dataset* ds, double R[9], double t[3], const double int
                      const nos_loss* loss, double min_depth, const nos_lm_options* options,
                      nos_lm_report* report);
 
+/* ---- many small pose problems in one launch ------------------------------------------
+ * n_problems independent solves, one pose each: problem i ends with exactly what nos_*_solve(ds[i], R + 9i, t + 3i, ...)
+ * would give it (planar: R2 + 4i, t2 + 2i) — pose, report and cost history.  Flat datasets of n x planes ≤ the context
+ * option "batch_max_elements" (NOS_BATCH_MAX_ELEMENTS; default 15 360, the single-workgroup size of nos_*_solve: 1 024
+ * NDT / 3 072 reprojection correspondences) run in ONE launch, one workgroup per problem (reports[i].launches = 1); the
+ * others — voxel-indexed datasets and larger problems — run one after the other through nos_*_solve after it.  A raised
+ * budget lets one workgroup loop over a larger problem: more problems per second when there are hundreds of them, more
+ * latency per problem.  The same dataset may appear several times (multi-start: datasets are only read).
+ * options->cost_history is NULL or has room for n_problems x max_iterations: row i starts at i * max_iterations and only
+ * its executed entries are written.  reprojection: intr [n][4], one set per problem.  One loss for all problems.
+ * n_problems == 0 returns NOS_OK.  Checked before anything runs (a rejected call writes nothing): NULL arrays,
+ * n_problems < 0, datasets of different contexts or element types (NOS_ERR_INVALID_ARGUMENT), a dataset of the wrong kind
+ * (NOS_ERR_WRONG_KIND), a multi-device context or one with a communicator (NOS_ERR_UNSUPPORTED: batches are process
+ * local). */
+int nos_ndt6_solve_batch(nos_dataset* const* ds, int32_t n_problems, double* R, double* t, const nos_loss* loss,
+                         const nos_lm_options* options, nos_lm_report* reports);
+int nos_ndt3_solve_batch(nos_dataset* const* ds, int32_t n_problems, double* R2, double* t2, const nos_loss* loss,
+                         const nos_lm_options* options, nos_lm_report* reports);
+int nos_reproj_solve_batch(nos_dataset* const* ds, int32_t n_problems, double* R, double* t, const double* intr,
+                           const nos_loss* loss, double min_depth, const nos_lm_options* options,
+                           nos_lm_report* reports);
+
 /* Test hook: ONE step of the device-resident loop on given sums and a given loop state — the stand-alone step kernel
  * (the same single-lane function every device loop form calls).  dof 6: sums[28], dof 3: sums[10].
  * state[22] = R (9, row-major; planar: R[0..3] = the 2x2 rotation) | t (3) | q w x y z (4) | lambda | previous_cost | cost |
@@ -456,7 +478,7 @@ int nos_pgo_time_sweep(nos_pose_graph* pg, int which, double lambda, int repeats
  * ---- experiment knobs ----------------------------------------------------------------
  * Read from the environment once, in nos_ctx_create (NOS_SC1, NOS_NT, NOS_FUSED, NOS_LM_FUSED, NOS_LM_WINDOW,
  * NOS_LM_SINGLE, NOS_LM_CLUSTER, NOS_POOL, NOS_TILE_LOG2, NOS_PLANE_SKEW, NOS_INGEST, NOS_INGEST_THREADS,
- * NOS_INDEXED_BPC, NOS_MATCH_DENSE, NOS_PGO_HOST_SCALARS, NOS_PGO_PRECOND, NOS_PGO_AGG; option only: "map_fma_mask",
+ * NOS_INDEXED_BPC, NOS_MATCH_DENSE, NOS_PGO_HOST_SCALARS, NOS_PGO_PRECOND, NOS_PGO_AGG, NOS_BATCH_MAX_ELEMENTS; option only: "map_fma_mask",
  * "map_eigen_version"); afterwards only through these setters (keys =
  * the names in lower case without the prefix, e.g. "lm_cluster"; "ingest": 0 auto, 1 pack, 2 unpack;
  * "debug_cluster_abort": test hook, makes the next one-launch solve give up and fall back).  Nothing on the solve /

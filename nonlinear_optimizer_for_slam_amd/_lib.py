@@ -38,6 +38,7 @@ C_ABI_SYMBOLS = (
     "nos_ndt6_accumulate", "nos_ndt3_accumulate", "nos_reproj_accumulate",
     "nos_ndt6_accumulate_async", "nos_ndt3_accumulate_async", "nos_reproj_accumulate_async",
     "nos_ndt6_solve", "nos_ndt3_solve", "nos_reproj_solve",
+    "nos_ndt6_solve_batch", "nos_ndt3_solve_batch", "nos_reproj_solve_batch",
     "nos_ctx_set_launch", "nos_ctx_set_option", "nos_ctx_get_option", "nos_runtime_info", "nos_ctx_comm_rccl_count",
     "nos_ctx_last_kernel", "nos_ctx_profile_begin", "nos_ctx_profile_end", "nos_ndt6_time_kernel", "nos_reproj_time_kernel",
     "nos_ndt3_time_kernel", "nos_status_string", "nos_last_error", "nos_version",
@@ -179,6 +180,10 @@ def _declare(lib):
     lib.nos_ndt6_solve.argtypes = [vp, dp, dp, lp, lmo, lmr]
     lib.nos_ndt3_solve.argtypes = [vp, dp, dp, lp, lmo, lmr]
     lib.nos_reproj_solve.argtypes = [vp, dp, dp, dp, lp, ctypes.c_double, lmo, lmr]
+    if hasattr(lib, "nos_ndt6_solve_batch"):  # absent from older builds loaded through NOS_HIP_LIB
+        lib.nos_ndt6_solve_batch.argtypes = [c_void_pp, ctypes.c_int32, dp, dp, lp, lmo, lmr]
+        lib.nos_ndt3_solve_batch.argtypes = [c_void_pp, ctypes.c_int32, dp, dp, lp, lmo, lmr]
+        lib.nos_reproj_solve_batch.argtypes = [c_void_pp, ctypes.c_int32, dp, dp, dp, lp, ctypes.c_double, lmo, lmr]
     lib.nos_ndt6_time_kernel.argtypes = [vp, dp, dp, lp, i, dp, dp]
     lib.nos_ndt3_time_kernel.argtypes = [vp, dp, dp, lp, i, dp, dp]
     lib.nos_reproj_time_kernel.argtypes = [vp, dp, dp, dp, lp, ctypes.c_double, i, dp, dp]

@@ -230,6 +230,63 @@ def _lm_call(fn, where, pre_args, post_args, R, t, max_iterations, gradient_tole
                   "cost_history": hist[:executed].copy()}
 
 
+def _batch_call(fn, where, datasets, R, t, nR, nt, post_args, max_iterations, gradient_tolerance, parameter_tolerance):
+    """Shared body of the batched solves: returns (R [B, nR], t [B, nt], [B report dicts shaped like _lm_call's])."""
+    from ._lib import NosLmOptions, NosLmReport
+    datasets = list(datasets)
+    B = len(datasets)
+    R = np.array(R, dtype=np.float64)  # copies: the inputs are not modified
+    t = np.array(t, dtype=np.float64)
+    if R.size != B * nR or t.size != B * nt:
+        raise ValueError("expected R [%d, %d] and t [%d, %d], got %s and %s" % (B, nR, B, nt, R.shape, t.shape))
+    R = np.ascontiguousarray(R.reshape(B, nR))
+    t = np.ascontiguousarray(t.reshape(B, nt))
+    handles = (ctypes.c_void_p * max(B, 1))(*[d._h for d in datasets])
+    m = max(int(max_iterations), 1)
+    hist = np.full((B, m), np.nan)  # row i starts at i * max_iterations
+    opt = NosLmOptions(int(max_iterations), 0, float(gradient_tolerance), float(parameter_tolerance), _dp(hist))
+    reps = (NosLmReport * max(B, 1))()
+    check(fn(handles, B, _dp(R), _dp(t), *post_args, ctypes.byref(opt), reps), where)
+    out = []
+    for i in range(B):
+        rep = reps[i]
+        executed = int(np.count_nonzero(~np.isnan(hist[i, :max(int(max_iterations), 0)])))
+        out.append({"iterations": rep.iterations, "ok": bool(rep.ok), "launches": rep.launches, "fallback": bool(rep.fallback),
+                    "printed_cost": rep.printed_cost, "last_cost": rep.last_cost, "final_lambda": rep.final_lambda,
+                    "cost_history": hist[i, :executed].copy()})
+    return R, t, out
+
+
+def solve6_batch(datasets, R, t, loss=None, max_iterations=100, gradient_tolerance=1e-6, parameter_tolerance=1e-6):
+    """B independent 6-DoF NDT solves, the small ones in one launch (nos_ndt6_solve_batch).  datasets: B NdtDatasets of one
+    context and element type (the same one may repeat); R [B, 9] or [B, 3, 3], t [B, 3].  Row i equals
+    datasets[i].solve6(R[i], t[i], ...).  Returns (R [B, 9], t [B, 3], [B reports])."""
+    l = make_loss(loss)
+    return _batch_call(hip_lib().nos_ndt6_solve_batch, "nos_ndt6_solve_batch", datasets, R, t, 9, 3, (ctypes.byref(l),),
+                       max_iterations, gradient_tolerance, parameter_tolerance)
+
+
+def solve3_batch(datasets, R2, t2, loss=None, max_iterations=100, gradient_tolerance=1e-6, parameter_tolerance=1e-6):
+    """B independent planar NDT solves (nos_ndt3_solve_batch): R2 [B, 4] or [B, 2, 2], t2 [B, 2].
+    Returns (R2 [B, 4], t2 [B, 2], [B reports])."""
+    l = make_loss(loss)
+    return _batch_call(hip_lib().nos_ndt3_solve_batch, "nos_ndt3_solve_batch", datasets, R2, t2, 4, 2, (ctypes.byref(l),),
+                       max_iterations, gradient_tolerance, parameter_tolerance)
+
+
+def reproj_solve_batch(datasets, R, t, intr, loss=None, min_depth=0.03, max_iterations=100, gradient_tolerance=1e-6,
+                       parameter_tolerance=1e-6):
+    """B independent reprojection solves (nos_reproj_solve_batch): R [B, 9] or [B, 3, 3], t [B, 3]; intr [B, 4], or [4] for
+    every problem.  Returns (R [B, 9], t [B, 3], [B reports])."""
+    B = len(datasets)
+    intr = np.asarray(intr, dtype=np.float64)
+    intr = np.ascontiguousarray(np.broadcast_to(intr, (B, 4)) if intr.shape == (4,) else intr.reshape(B, 4))
+    l = make_loss(loss)
+    return _batch_call(hip_lib().nos_reproj_solve_batch, "nos_reproj_solve_batch", datasets, R, t, 9, 3,
+                       (_dp(intr), ctypes.byref(l), ctypes.c_double(min_depth)), max_iterations, gradient_tolerance,
+                       parameter_tolerance)
+
+
 class _Dataset:
     _n_planes = 0
     _create = _create_dev = _create_rec = None

@@ -20,8 +20,8 @@
 //   robust loss   loss_function.h:28-33, 57-66
 //
 // Split by role (round 4): items → reductions → loop state and hand-offs → launch-per-pass kernel → one-launch loop →
-// voxel-indexed layout → the small stand-alone kernels.  Variants that were measured and lost live in
-// tools/exp/assemble_variants_r03.hpp, not here.
+// voxel-indexed layout → the small stand-alone kernels → many small solves in one launch.  Variants that were measured and
+// lost live in tools/exp/assemble_variants_r03.hpp, not here.
 #pragma once
 
-#include "assemble_misc.hpp"  // includes the others, in the order above
+#include "assemble_batch.hpp"  // includes the others, in the order above

@@ -19,20 +19,18 @@ namespace nos {
 // reprojection points, but no gain at 2 900 NDT correspondences (6 chunks) — hence a budget in plane-elements.
 constexpr size_t kSingleBlockMaxElements = size_t(1024) * 15;  // n × planes (nos.h): 1024 NDT or 3072 reprojection correspondences
 
-template <typename Problem, typename T, int BLOCK, bool NT = false>
-__global__ __launch_bounds__(BLOCK) void solve_single_block_kernel(TiledLayout L, typename Problem::Params P,
-                                                                  uint32_t n_chunks, LmDevice* lm,
-                                                                  double* __restrict__ cost_history, int history_capacity,
-                                                                  double* entry_host, unsigned long long* seq_host,
-                                                                  unsigned long long seq) {
+// The loop of the single-workgroup solve: one pass over the n_chunks chunks of 512 correspondences per iteration, block
+// reduction into s_sum, one lane steps the loop state s_lm (both in LDS, s_lm loaded before the call), until the state says
+// done.  Returns the iterations executed; s_sum then holds the sums of the last one.  solve_single_block_kernel (one problem)
+// and solve_batch_kernel (one problem per workgroup, assemble_batch.hpp) both run exactly this, so that a problem solved in
+// a batch gets the bits of its lone solve.
+template <typename Problem, typename T, int BLOCK, bool NT>
+__device__ __forceinline__ int single_block_loop(const TiledLayout& L, typename Problem::Params& P, uint32_t n_chunks,
+                                                 LmDevice& s_lm, double* s_sum, double* __restrict__ cost_history,
+                                                 int history_capacity) {
   constexpr int kF = Problem::kFields;
   constexpr int kOut = Problem::kOut;
   const T* __restrict__ base = static_cast<const T*>(L.base);
-  __shared__ double s_lm_raw[(sizeof(LmDevice) + 7) / 8];  // raw storage: the struct has default member initialisers
-  LmDevice& s_lm = *reinterpret_cast<LmDevice*>(s_lm_raw);
-  __shared__ double s_sum[kLmTotDoubles(kOut)];
-  if (threadIdx.x == 0) s_lm = *lm;
-  __syncthreads();
   int executed = 0;
   while (s_lm.st.done == 0) {  // block-uniform: every thread reads the same LDS word after a barrier
     set_pose(P, &s_lm);
@@ -77,6 +75,22 @@ __global__ __launch_bounds__(BLOCK) void solve_single_block_kernel(TiledLayout L
     ++executed;
     __syncthreads();
   }
+  return executed;
+}
+
+template <typename Problem, typename T, int BLOCK, bool NT = false>
+__global__ __launch_bounds__(BLOCK) void solve_single_block_kernel(TiledLayout L, typename Problem::Params P,
+                                                                  uint32_t n_chunks, LmDevice* lm,
+                                                                  double* __restrict__ cost_history, int history_capacity,
+                                                                  double* entry_host, unsigned long long* seq_host,
+                                                                  unsigned long long seq) {
+  constexpr int kOut = Problem::kOut;
+  __shared__ double s_lm_raw[(sizeof(LmDevice) + 7) / 8];  // raw storage: the struct has default member initialisers
+  LmDevice& s_lm = *reinterpret_cast<LmDevice*>(s_lm_raw);
+  __shared__ double s_sum[kLmTotDoubles(kOut)];
+  if (threadIdx.x == 0) s_lm = *lm;
+  __syncthreads();
+  const int executed = single_block_loop<Problem, T, BLOCK, NT>(L, P, n_chunks, s_lm, s_sum, cost_history, history_capacity);
   if (threadIdx.x < kOut && entry_host != nullptr && executed > 0)
     __hip_atomic_store(entry_host + kLogOut + threadIdx.x, s_sum[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (threadIdx.x == 0) {

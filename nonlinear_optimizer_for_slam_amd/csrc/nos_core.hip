@@ -1563,6 +1563,7 @@ int nos_ctx_create(const int* device_ids, int n_devices, nos_ctx** out_ctx) {
     st.lm_cluster = env_int("NOS_LM_CLUSTER", st.lm_cluster);
     st.lm_cluster_max_blocks = env_int("NOS_LM_CLUSTER_MAX_BLOCKS", st.lm_cluster_max_blocks);
     st.stream_lds_chunks = env_int("NOS_STREAM_LDS_CHUNKS", st.stream_lds_chunks);
+    st.batch_max_elements = env_int("NOS_BATCH_MAX_ELEMENTS", st.batch_max_elements);
     st.pool = env_int("NOS_POOL", st.pool);
     st.tile_log2 = env_int("NOS_TILE_LOG2", int(kDefaultTileLog2));
     const char* ingest = getenv("NOS_INGEST");
@@ -1685,6 +1686,7 @@ int nos_ctx_destroy(nos_ctx* ctx) {
       if (s.pack_pinned[b]) (void)hipHostFree(s.pack_pinned[b]);
       if (s.pack_done[b]) (void)hipEventDestroy(s.pack_done[b]);
     }
+    if (s.batch_pinned) (void)hipHostFree(s.batch_pinned);
     for (auto& pe : s.pool) (void)hipFree(pe.ptr);
     s.pool.clear();
     if (s.h_log) (void)hipHostFree(s.h_log);
@@ -1752,6 +1754,7 @@ const OptionEntry kOptions[] = {
     {"debug_cluster_abort", &nosd::Settings::debug_cluster_abort, 0, 2},
     {"lm_cluster_max_blocks", &nosd::Settings::lm_cluster_max_blocks, 1, 256},
     {"stream_lds_chunks", &nosd::Settings::stream_lds_chunks, 0, 3},
+    {"batch_max_elements", &nosd::Settings::batch_max_elements, 0, 1 << 30},
 };
 bool option_in_range(const OptionEntry& o, int value);
 void drop_out_of_range_settings(nosd::Settings& st) {

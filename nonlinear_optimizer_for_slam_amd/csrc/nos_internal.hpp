@@ -104,6 +104,8 @@ struct DeviceSlot {
   size_t stage_bytes = 0;
   void* pack_pinned[2] = {nullptr, nullptr};  // pinned host staging of the host-pack ingestion: [n_fields][chunk] elements
   size_t pack_bytes = 0;
+  void* batch_pinned = nullptr;  // pinned host staging of the batched solve (nos_batch.hip): descriptors up, results down
+  size_t batch_pinned_bytes = 0;
   hipEvent_t pack_done[2] = {nullptr, nullptr};
   // Device-buffer pool for dataset storage: nos_dataset_destroy parks the buffer here, the next dataset of a similar
   // size takes it over (the reference's outer loop re-Solves up to 10 times with correspondences of similar count).
@@ -168,6 +170,8 @@ struct Settings {
   int lm_cluster_max_blocks = 256;  // NOS_LM_CLUSTER_MAX_BLOCKS  workgroups of the one-launch loop (rehearsals: ranks sharing a GPU)
   int stream_lds_chunks = 3;   // NOS_STREAM_LDS_CHUNKS  streamed one-launch loop: chunks per workgroup kept in LDS after
                                //                        iteration 0 (0 … 3; 0 = everything streamed every iteration)
+  int batch_max_elements = int(nos::kSingleBlockMaxElements);  // NOS_BATCH_MAX_ELEMENTS  nos_*_solve_batch: a flat problem
+                               // of n x planes ≤ this runs in the batch launch (one workgroup), a larger one as a lone solve
 };
 }  // namespace nosd
 
@@ -366,6 +370,11 @@ int dataset_new(nos_ctx* ctx, int kind, size_t n, int dtype, nos_dataset** out, 
 int zero_pad(int dtype, int n_fields, const nos::TiledLayout& L, void* dst, hipStream_t stream);
 int unpack_records(int dtype, const unsigned char* d_rec, size_t stride, const nos::FieldOffsets& fo, int n_fields,
                    size_t first, size_t count, const nos::TiledLayout& L, void* dst, hipStream_t stream);
+int build_request(int problem, const nos_dataset* ds, const double* R, int nR, const double* t, int nt,
+                  const double* intr, double min_depth, const nos_loss* loss, Request* rq);
+// the device-resident loop of one dataset (nos_*_solve)
+int lm_solve(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, double* R, int nR, double* t, int nt,
+             nos_lm_report* report);
 // nos_match.hip: matcher tables from device-resident voxel statistics (valid may be null = all valid)
 int map_create_device(nos_ctx* ctx, size_t n_voxels, const double* d_means, const double* d_S, const unsigned char* d_valid,
                       double search_radius_sq, nos_ndt_map** out_map);

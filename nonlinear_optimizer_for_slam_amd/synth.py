@@ -59,6 +59,24 @@ REPROJ_INTR4 = (1.0 / 525.0, 1.0 / 525.0, 320.0, 240.0)    # inv_fx, inv_fy, cx,
 REPROJ_HUBER_THRESHOLD = 1.0 / 525.0                        # 1 px in normalised image coordinates
 
 
+def random_poses(count, seed=SEED, max_angle=0.1, max_translation=0.2, planar=False):
+    """`count` seeded start poses around the identity: angles uniform in ±max_angle rad (R = Rz Ry Rx), translation
+    components uniform in ±max_translation.  → (R [count, 9] row-major, t [count, 3]); planar: (R2 [count, 4], t2 [count, 2])."""
+    rng = np.random.default_rng(seed)
+    if planar:
+        yaw = rng.uniform(-max_angle, max_angle, count)
+        c, s = np.cos(yaw), np.sin(yaw)
+        return np.stack([c, -s, s, c], axis=1), rng.uniform(-max_translation, max_translation, (count, 2))
+    R = np.empty((count, 9))
+    for k, (rx, ry, rz) in enumerate(rng.uniform(-max_angle, max_angle, (count, 3))):
+        cx, sx, cy, sy, cz, sz = np.cos(rx), np.sin(rx), np.cos(ry), np.sin(ry), np.cos(rz), np.sin(rz)
+        Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+        Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+        Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+        R[k] = (Rz @ Ry @ Rx).reshape(-1)
+    return R, rng.uniform(-max_translation, max_translation, (count, 3))
+
+
 def true_pose(which="ndt"):
     """(R [3,3], t [3]) of the scene's ground truth; reprojection solves for its inverse."""
     R = np.zeros(9)
