@@ -419,6 +419,65 @@ int nos_reproj_solve_batch(nos_dataset* const* ds, int32_t n_problems, double* R
                            const nos_loss* loss, double min_depth, const nos_lm_options* options,
                            nos_lm_report* reports);
 
+/* ---- many scan-to-map registrations in one launch ------------------------------------
+ * The outer loop of the reference's test drivers (OptimizePoseAnalytic, MDM/tests/simple_optimization_test.cc:474-503):
+ * up to max_outer_iterations rounds of {MatchPointCloud at the current pose (:296-342, here nos_ndt_match), the solver
+ * class's tail drop (nos_dataset_drop_last_matches), Solve()}, stopping once the pose moved by less than 1e-5 in
+ * translation and in the quaternion vector part — for n_problems scans against ONE map, in ONE launch with one workgroup
+ * per problem: matching, tail drop, the LM loop of the single-workgroup nos_*_solve and the stopping test all run on the
+ * device, every round.  Problem i ends with what the Python loop pipeline.scan_to_map gives scans[i] from (R + 9i, t + 3i):
+ * pose, outer_iter and per round matches / used / iterations / printed cost — bit for bit for scans of ≤ 512 points (their
+ * 2n ≤ 1 024 slots are what nos_*_solve runs in one workgroup), to rounding above (the lone solve then sums in another
+ * order, in its multi-workgroup form).
+ * Every problem runs inside the launch, whatever its size: a large scan is slower here than through scan_to_map, one CU
+ * doing what the lone one-launch solve spreads over the chip (DESIGN.md §12 has the measured crossover); a caller with one
+ * large scan keeps using the lone path.  The context option batch_max_elements is not consulted.
+ * nos_ndt3_register_batch: R [n][9], t [n][3] stay full 3-D poses; every round solves for the top-left 2x2 and (x, y) and
+ * writes only those back (MahalanobisDistanceMinimizerHip3DOF), z, roll and pitch pass through.
+ * The same scan may appear several times (multi-start); scans and map are only read.  Per-problem scratch datasets,
+ * descriptors and results come from the context's buffer pool: one upload, one launch, one copy back, one synchronisation.
+ * A round whose solve fails (ok = 0, e.g. no match at all) ends that problem: its pose stays at the value before that
+ * round, reports[i].ok = 0 and outer_iter = that round (scan_to_map raises there); the other problems are unaffected.
+ * Checked before anything runs (a rejected call writes nothing): NULL arrays, n_problems < 0, scans or map of another
+ * context, max_outer_iterations < 1, keep_multiple < 0, an unknown dtype or loss, max_iterations < 0, or
+ * options->cost_history != NULL (NOS_ERR_INVALID_ARGUMENT); max_neighbors outside 1-2, a multi-device context or one with a
+ * communicator (NOS_ERR_UNSUPPORTED).  n_problems == 0 returns NOS_OK.
+ * Not covered: voxel-indexed matching, the simd_class semantics, one map per problem, multi-device batches. */
+typedef struct nos_register_round {
+  uint64_t matches;     /* real matches of the round (nos_ndt_match's n_matches) */
+  uint64_t used;        /* matches the solve summed: matches - matches % keep_multiple */
+  int32_t iterations;   /* the round's "iter:" */
+  int32_t ok;           /* 0: the round's solve failed */
+  double printed_cost;  /* the round's "COST:" */
+  double last_cost;
+} nos_register_round;
+
+typedef struct nos_register_options {
+  int32_t max_outer_iterations;  /* rounds at most (10 in OptimizePoseAnalytic) */
+  int32_t max_neighbors;         /* 1 or 2 (the reference: 2) */
+  int32_t keep_multiple;         /* 0 = no tail drop; k > 0: each round sums the first floor(N/k)*k of its N matches
+                                    (4: the scalar 3-DoF class and the captured 6-DoF runs; 8: the SIMD classes) */
+  int32_t dtype;                 /* NOS_F64 / NOS_F32: element type of the matched records */
+  nos_register_round* round_log; /* NULL, or n_problems x max_outer_iterations entries: row i starts at
+                                    i * max_outer_iterations, its first reports[i].rounds entries are written, the rest
+                                    zeroed */
+} nos_register_options;
+
+typedef struct nos_register_report {
+  int32_t outer_iter;  /* index of the round that met the stopping test, max_outer_iterations if none did (the reference's
+                          printed loop variable), or the round whose solve failed */
+  int32_t rounds;      /* rounds run */
+  int32_t ok;          /* 0: a round's solve failed */
+  int32_t pad;
+} nos_register_report;
+
+int nos_ndt6_register_batch(nos_ndt_map* map, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
+                            const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
+                            nos_register_report* reports);
+int nos_ndt3_register_batch(nos_ndt_map* map, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
+                            const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
+                            nos_register_report* reports);
+
 /* Test hook: ONE step of the device-resident loop on given sums and a given loop state — the stand-alone step kernel
  * (the same single-lane function every device loop form calls).  dof 6: sums[28], dof 3: sums[10].
  * state[22] = R (9, row-major; planar: R[0..3] = the 2x2 rotation) | t (3) | q w x y z (4) | lambda | previous_cost | cost |

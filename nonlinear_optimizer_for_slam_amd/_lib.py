@@ -39,6 +39,7 @@ C_ABI_SYMBOLS = (
     "nos_ndt6_accumulate_async", "nos_ndt3_accumulate_async", "nos_reproj_accumulate_async",
     "nos_ndt6_solve", "nos_ndt3_solve", "nos_reproj_solve",
     "nos_ndt6_solve_batch", "nos_ndt3_solve_batch", "nos_reproj_solve_batch",
+    "nos_ndt6_register_batch", "nos_ndt3_register_batch",
     "nos_ctx_set_launch", "nos_ctx_set_option", "nos_ctx_get_option", "nos_runtime_info", "nos_ctx_comm_rccl_count",
     "nos_ctx_last_kernel", "nos_ctx_profile_begin", "nos_ctx_profile_end", "nos_ndt6_time_kernel", "nos_reproj_time_kernel",
     "nos_ndt3_time_kernel", "nos_status_string", "nos_last_error", "nos_version",
@@ -60,6 +61,21 @@ class NosLmReport(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_int32), ("ok", ctypes.c_int32), ("launches", ctypes.c_int32),
                 ("fallback", ctypes.c_int32), ("printed_cost", ctypes.c_double), ("last_cost", ctypes.c_double),
                 ("final_lambda", ctypes.c_double)]
+
+
+class NosRegisterRound(ctypes.Structure):
+    _fields_ = [("matches", ctypes.c_uint64), ("used", ctypes.c_uint64), ("iterations", ctypes.c_int32),
+                ("ok", ctypes.c_int32), ("printed_cost", ctypes.c_double), ("last_cost", ctypes.c_double)]
+
+
+class NosRegisterOptions(ctypes.Structure):
+    _fields_ = [("max_outer_iterations", ctypes.c_int32), ("max_neighbors", ctypes.c_int32),
+                ("keep_multiple", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("round_log", ctypes.POINTER(NosRegisterRound))]
+
+
+class NosRegisterReport(ctypes.Structure):
+    _fields_ = [("outer_iter", ctypes.c_int32), ("rounds", ctypes.c_int32), ("ok", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
 class NosError(RuntimeError):
@@ -184,6 +200,10 @@ def _declare(lib):
         lib.nos_ndt6_solve_batch.argtypes = [c_void_pp, ctypes.c_int32, dp, dp, lp, lmo, lmr]
         lib.nos_ndt3_solve_batch.argtypes = [c_void_pp, ctypes.c_int32, dp, dp, lp, lmo, lmr]
         lib.nos_reproj_solve_batch.argtypes = [c_void_pp, ctypes.c_int32, dp, dp, dp, lp, ctypes.c_double, lmo, lmr]
+    if hasattr(lib, "nos_ndt6_register_batch"):  # absent from older builds loaded through NOS_HIP_LIB
+        ro, rr = ctypes.POINTER(NosRegisterOptions), ctypes.POINTER(NosRegisterReport)
+        lib.nos_ndt6_register_batch.argtypes = [vp, c_void_pp, ctypes.c_int32, dp, dp, lp, ro, lmo, rr]
+        lib.nos_ndt3_register_batch.argtypes = [vp, c_void_pp, ctypes.c_int32, dp, dp, lp, ro, lmo, rr]
     lib.nos_ndt6_time_kernel.argtypes = [vp, dp, dp, lp, i, dp, dp]
     lib.nos_ndt3_time_kernel.argtypes = [vp, dp, dp, lp, i, dp, dp]
     lib.nos_reproj_time_kernel.argtypes = [vp, dp, dp, dp, lp, ctypes.c_double, i, dp, dp]

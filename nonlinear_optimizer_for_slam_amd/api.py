@@ -287,6 +287,56 @@ def reproj_solve_batch(datasets, R, t, intr, loss=None, min_depth=0.03, max_iter
                        parameter_tolerance)
 
 
+def _register_call(fn, where, ndt_map, scans, R, t, loss, max_outer_iterations, keep_multiple, max_neighbors, dtype,
+                   max_iterations, gradient_tolerance, parameter_tolerance):
+    """Shared body of the batched registrations: returns (R [B, 9], t [B, 3], [B report dicts])."""
+    from ._lib import NosLmOptions, NosRegisterOptions, NosRegisterReport, NosRegisterRound
+    scans = list(scans)
+    B = len(scans)
+    R = np.array(R, dtype=np.float64)  # copies: the inputs are not modified
+    t = np.array(t, dtype=np.float64)
+    if R.size != B * 9 or t.size != B * 3:
+        raise ValueError("expected R [%d, 9] and t [%d, 3], got %s and %s" % (B, B, R.shape, t.shape))
+    R = np.ascontiguousarray(R.reshape(B, 9))
+    t = np.ascontiguousarray(t.reshape(B, 3))
+    handles = (ctypes.c_void_p * max(B, 1))(*[s._h for s in scans])
+    m = max(int(max_outer_iterations), 1)
+    log = (NosRegisterRound * (max(B, 1) * m))()  # row i starts at i * max_outer_iterations
+    ropt = NosRegisterOptions(int(max_outer_iterations), int(max_neighbors), int(keep_multiple or 0), _DTYPES[dtype], log)
+    opt = NosLmOptions(int(max_iterations), 0, float(gradient_tolerance), float(parameter_tolerance), None)
+    reps = (NosRegisterReport * max(B, 1))()
+    l = make_loss(loss)
+    check(fn(ndt_map._h, handles, B, _dp(R), _dp(t), ctypes.byref(l), ctypes.byref(ropt), ctypes.byref(opt), reps), where)
+    out = []
+    for i in range(B):
+        rep = reps[i]
+        rounds = [{"matches": int(e.matches), "used": int(e.used), "iterations": int(e.iterations), "ok": bool(e.ok),
+                   "printed_cost": float(e.printed_cost), "last_cost": float(e.last_cost)}
+                  for e in log[i * m:i * m + rep.rounds]]
+        out.append({"outer_iter": rep.outer_iter, "rounds": rounds, "ok": bool(rep.ok)})
+    return R, t, out
+
+
+def register6_batch(ndt_map, scans, R, t, loss, max_outer_iterations=10, keep_multiple=None, max_neighbors=2, dtype="f64",
+                    max_iterations=40, gradient_tolerance=1e-6, parameter_tolerance=1e-6):
+    """B scan-to-map registrations against one map in one launch (nos_ndt6_register_batch): every round's matching, tail
+    drop (keep_multiple), LM solve and stopping test run on the device.  scans: B Scans of the map's context (the same one
+    may repeat: multi-start); R [B, 9] or [B, 3, 3], t [B, 3] start poses.  Row i equals pipeline.scan_to_map from
+    (R[i], t[i]).  Returns (R [B, 9], t [B, 3], [B reports {outer_iter, rounds: [per-round dicts], ok}])."""
+    return _register_call(hip_lib().nos_ndt6_register_batch, "nos_ndt6_register_batch", ndt_map, scans, R, t, loss,
+                          max_outer_iterations, keep_multiple, max_neighbors, dtype, max_iterations, gradient_tolerance,
+                          parameter_tolerance)
+
+
+def register3_batch(ndt_map, scans, R, t, loss, max_outer_iterations=10, keep_multiple=None, max_neighbors=2, dtype="f64",
+                    max_iterations=40, gradient_tolerance=1e-6, parameter_tolerance=1e-6):
+    """Planar form (nos_ndt3_register_batch): R [B, 9], t [B, 3] are full 3-D poses; every round solves for the top-left
+    2x2 and (x, y) and writes only those back, as the 3-DoF drop-in class does."""
+    return _register_call(hip_lib().nos_ndt3_register_batch, "nos_ndt3_register_batch", ndt_map, scans, R, t, loss,
+                          max_outer_iterations, keep_multiple, max_neighbors, dtype, max_iterations, gradient_tolerance,
+                          parameter_tolerance)
+
+
 class _Dataset:
     _n_planes = 0
     _create = _create_dev = _create_rec = None

@@ -158,21 +158,21 @@ __device__ __forceinline__ void find_two_nearest(const MapView& map, double qx, 
       }
 }
 
-// One thread per scan point.  points: 3 planes of n doubles (local frame).
+// Scan point i (i < n_points) warped by `pose` and matched: writes slots 2i and 2i + 1 of the dataset and returns the
+// number of real matches among them (0-2).  match_kernel (one thread per point) and register_batch_kernel (the lanes of
+// one workgroup striding over a scan, assemble_register.hpp) both call this, so their records are the same bits.  The
+// warp's multiply-adds are spelled out, in the form the compiler chose for match_kernel when it was written as
+// `R0 x + R1 y + R2 z + t0`: left to the compiler, a different surrounding kernel could fuse another product.
 template <typename DST>
-__global__ __launch_bounds__(256) void match_kernel(MapView map, const double* __restrict__ px,
-                                                    const double* __restrict__ py,
-                                                    const double* __restrict__ pz, uint64_t n_points,
-                                                    PosePod pose, int max_neighbors, TiledLayout L,
-                                                    DST* __restrict__ dst,
-                                                    unsigned long long* __restrict__ n_matches) {
-  const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+__device__ __forceinline__ int match_point(const MapView& map, const double* __restrict__ px, const double* __restrict__ py,
+                                           const double* __restrict__ pz, uint64_t i, const PosePod& pose,
+                                           int max_neighbors, const TiledLayout& L, DST* __restrict__ dst) {
   int found = 0;
-  if (i < n_points) {
+  {
     const double x = px[i], y = py[i], z = pz[i];
-    const double qx = pose.R[0] * x + pose.R[1] * y + pose.R[2] * z + pose.t[0];
-    const double qy = pose.R[3] * x + pose.R[4] * y + pose.R[5] * z + pose.t[1];
-    const double qz = pose.R[6] * x + pose.R[7] * y + pose.R[8] * z + pose.t[2];
+    const double qx = __builtin_fma(pose.R[2], z, __builtin_fma(pose.R[0], x, pose.R[1] * y)) + pose.t[0];
+    const double qy = __builtin_fma(pose.R[5], z, __builtin_fma(pose.R[3], x, pose.R[4] * y)) + pose.t[1];
+    const double qz = __builtin_fma(pose.R[8], z, __builtin_fma(pose.R[6], x, pose.R[7] * y)) + pose.t[2];
     TwoNearest best;
     find_two_nearest(map, qx, qy, qz, best);
     const uint32_t (&best_j)[2] = best.j;
@@ -206,6 +206,19 @@ __global__ __launch_bounds__(256) void match_kernel(MapView map, const double* _
 #pragma unroll
     for (int k = 0; k < 6; ++k) put(6 + k, U0[k], U1[k]);
   }
+  return found;
+}
+
+// One thread per scan point.  points: 3 planes of n doubles (local frame).
+template <typename DST>
+__global__ __launch_bounds__(256) void match_kernel(MapView map, const double* __restrict__ px,
+                                                    const double* __restrict__ py,
+                                                    const double* __restrict__ pz, uint64_t n_points,
+                                                    PosePod pose, int max_neighbors, TiledLayout L,
+                                                    DST* __restrict__ dst,
+                                                    unsigned long long* __restrict__ n_matches) {
+  const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+  const int found = i < n_points ? match_point<DST>(map, px, py, pz, i, pose, max_neighbors, L, dst) : 0;
   // match count: wave sum → one atomic per wave (integer, order independent)
   int s = found;
 #pragma unroll
@@ -217,9 +230,9 @@ __global__ __launch_bounds__(256) void match_kernel(MapView map, const double* _
 // the reference's compacted correspondence vector does (floor(N/4)*4 of the scalar 3-DoF class,
 // MDM/mahalanobis_distance_minimizer_analytic_3dof.cc:33-36).  A record is empty when its sqrt-information is all zero.
 // One wave walks backwards from the end, 64 slots at a time; n_drop is small (< 8), so it touches the tail only.
+// drop_last_records is that wave's work (lane = 0 … 63), also run by the first wave of register_batch_kernel.
 template <typename T>
-__global__ __launch_bounds__(64) void drop_last_matches_kernel(T* __restrict__ data, TiledLayout L, uint64_t n_drop) {
-  const int lane = threadIdx.x;
+__device__ __forceinline__ void drop_last_records(T* __restrict__ data, const TiledLayout& L, uint64_t n_drop, int lane) {
   uint64_t remaining = n_drop;
   for (uint64_t pos = L.n; remaining > 0 && pos > 0; pos = pos > 64 ? pos - 64 : 0) {
     const bool in_range = pos > uint64_t(lane);
@@ -234,6 +247,11 @@ __global__ __launch_bounds__(64) void drop_last_matches_kernel(T* __restrict__ d
     const uint64_t found = uint64_t(__popcll(mask));
     remaining -= found < remaining ? found : remaining;
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void drop_last_matches_kernel(T* __restrict__ data, TiledLayout L, uint64_t n_drop) {
+  drop_last_records<T>(data, L, n_drop, int(threadIdx.x));
 }
 
 // tiled dataset → planar host-order planes (diagnostics / tests); flat NDT (ndt != 0): the 15 planes of nos.h (p, mu, S)

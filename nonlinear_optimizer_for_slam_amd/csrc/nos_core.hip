@@ -1071,12 +1071,16 @@ void pool_release(DeviceSlot& slot, void* ptr, size_t capacity) {
   }
 }
 
+int dataset_tile_log2(const nos_ctx* ctx, int dtype) {
+  const int tile_log2 = ctx->tile_log2 >= 0 ? ctx->tile_log2 : ctx->settings.tile_log2;
+  return tile_log2 < 0 ? (dtype == NOS_F32 ? kDefaultTileLog2F32 : 0) : tile_log2;
+}
+
 int alloc_shards(nos_ctx* ctx, nos_dataset* ds) {
   const int n_shards = int(ctx->slots.size());
   const size_t n = ds->n;
   const size_t per = (n + n_shards - 1) / size_t(n_shards);  // contiguous equal ranges
-  int tile_log2 = ctx->tile_log2 >= 0 ? ctx->tile_log2 : ctx->settings.tile_log2;
-  if (tile_log2 < 0) tile_log2 = ds->dtype == NOS_F32 ? kDefaultTileLog2F32 : 0;
+  const int tile_log2 = dataset_tile_log2(ctx, ds->dtype);
   if (tile_log2 != 0 && (tile_log2 < 10 || tile_log2 > 24)) return fail(NOS_ERR_INVALID_ARGUMENT, "tile_log2 out of range");
   ds->tile = tile_log2 > 0 ? (size_t(1) << tile_log2) : 0;
   ds->shards.resize(n_shards);

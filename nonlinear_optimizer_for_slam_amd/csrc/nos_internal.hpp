@@ -367,6 +367,11 @@ void pool_release(DeviceSlot& slot, void* ptr, size_t capacity);
 int env_int(const char* name, int dflt);
 size_t elem_size(int dtype);
 int dataset_new(nos_ctx* ctx, int kind, size_t n, int dtype, nos_dataset** out, nos_dataset** made);
+// layout of a dataset's shard: tile size by element type and context settings, then the planes (flat NDT: nos::kNdtStored)
+int dataset_tile_log2(const nos_ctx* ctx, int dtype);
+nos::TiledLayout make_layout(size_t n, int n_fields, int tile_log2, int plane_skew);
+size_t layout_elems(const nos::TiledLayout& L, int n_fields);
+int check_loss(const nos_loss* loss, int* kind_out);
 int zero_pad(int dtype, int n_fields, const nos::TiledLayout& L, void* dst, hipStream_t stream);
 int unpack_records(int dtype, const unsigned char* d_rec, size_t stride, const nos::FieldOffsets& fo, int n_fields,
                    size_t first, size_t count, const nos::TiledLayout& L, void* dst, hipStream_t stream);

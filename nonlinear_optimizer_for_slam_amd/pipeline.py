@@ -8,7 +8,7 @@ less than 1e-5 in translation and in the quaternion vector part.
 """
 import numpy as np
 
-from .api import NdtMap, Scan
+from .api import NdtMap, Scan, register3_batch, register6_batch
 from .solvers import MahalanobisDistanceMinimizerHip, MahalanobisDistanceMinimizerHip3DOF, Options, Pose
 
 
@@ -72,3 +72,34 @@ def scan_to_map(ctx, ndt_map, scan, initial_pose=None, loss=("exponential", 1.0,
     else:
         outer = max_outer_iterations  # never met the stopping test: the reference's loop variable ends at the bound
     return pose, rounds, outer
+
+
+def scan_to_map_batch(ctx, ndt_map, scans, initial_poses=None, loss=("exponential", 1.0, 1.0), options=None,
+                      max_outer_iterations=10, dof=6, dtype="f64", keep_multiple=None):
+    """scan_to_map for many scans against one map in ONE launch (api.register6_batch / register3_batch): the outer loop
+    runs on the device, one workgroup per scan.  scans: list of api.Scan (the same one may repeat); initial_poses: None
+    (identity for all) or a list of Poses.  → list of (Pose, rounds, outer_iter) shaped exactly as scan_to_map returns
+    them, or None where scan_to_map would raise RuntimeError (a round's solve failed; the other rows are unaffected).
+    Bit for bit scan_to_map's result for scans of ≤ 512 points, to rounding above."""
+    scans = list(scans)
+    B = len(scans)
+    if initial_poses is None:
+        initial_poses = [Pose() for _ in range(B)]
+    if len(initial_poses) != B:
+        raise ValueError("%d scans but %d initial poses" % (B, len(initial_poses)))
+    options = options or Options()
+    R0 = np.array([p.R.reshape(9) for p in initial_poses]).reshape(B, 9)
+    t0 = np.array([p.t.reshape(3) for p in initial_poses]).reshape(B, 3)
+    fn = register3_batch if dof == 3 else register6_batch
+    R, t, reports = fn(ndt_map, scans, R0, t0, loss, max_outer_iterations=max_outer_iterations,
+                       keep_multiple=keep_multiple, dtype=dtype, max_iterations=options.max_iterations,
+                       gradient_tolerance=options.gradient_tolerance, parameter_tolerance=options.parameter_tolerance)
+    out = []
+    for i, rep in enumerate(reports):
+        if not rep["ok"]:
+            out.append(None)
+            continue
+        rounds = [{"matches": r["matches"], "used": r["used"], "iterations": r["iterations"],
+                   "printed_cost": r["printed_cost"]} for r in rep["rounds"]]
+        out.append((Pose(R[i].reshape(3, 3), t[i]), rounds, rep["outer_iter"]))
+    return out
