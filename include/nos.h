@@ -547,7 +547,11 @@ int nos_pgo_time_sweep(nos_pose_graph* pg, int which, double lambda, int repeats
  *                 resident data (one launch per iteration above), 5 = as 1 with the all-reduce's first stage always through
  *                 sc1 stores, 3 = the arrival-counter all-reduce, 2 = at most one correspondence per lane, 0 = off.
  *   "tile_log2"   layout of datasets created afterwards: -1 (default) by element type — fp64 planar planes, fp32 tiles of
- *                 1024 correspondences; 0 planar; 10…24 tiles of 2^k. */
+ *                 1024 correspondences; 0 planar; 10…24 tiles of 2^k.
+ *   "stream_lds_chunks" / "stream_reg_rounds" (NOS_STREAM_LDS_CHUNKS, NOS_STREAM_REG_ROUNDS; 0…3, default 3)
+ *                 streamed one-launch loop: chunks every workgroup keeps in LDS / in spare vector registers after the
+ *                 first iteration instead of reading them from HBM again (the register count is clamped to what the kernel
+ *                 has room for: none for fp32 6-DoF NDT, 3 otherwise).  The results do not depend on either, bit for bit. */
 int nos_ctx_set_option(nos_ctx* ctx, const char* key, int value);
 int nos_ctx_get_option(const nos_ctx* ctx, const char* key, int* value);
 

@@ -215,21 +215,37 @@ struct ResidentShape<5, 8> { static constexpr int RI = 9, LI = 7; };
 template <>
 struct ResidentShape<5, 4> { static constexpr int RI = 10, LI = 14; };
 
+// Streaming form (SI > 0): rounds of BLOCK * SI correspondences a workgroup keeps in VECTOR REGISTERS from iteration 1 on,
+// next to the chunks in LDS.  One 512-thread workgroup per CU is two waves per SIMD, which are charged 256 registers per
+// lane whatever they use; the streamed kernels used 111-196, and a round is kFields * SI values per lane (NDT: 24 registers).
+// The count is a property of the instantiation, not a template parameter (the kernel's name is part of the tests), and is
+// chosen from what the compiler reports and what was measured: with three slots every streamed kernel stays within 256
+// registers without scratch (the headline, 6-DoF NDT fp64 with the exponential loss: 238), except fp32 6-DoF NDT, which
+// has room for one slot only (214-238 registers; two spill) — and ran 4.7 % SLOWER with that one than the loop without
+// slots (profiles/r07_ab.txt), so it keeps none; a kernel without slots runs round 6's loop unchanged.
+template <typename Problem, typename T>
+struct StreamRegRounds { static constexpr int kRR = 3; };
+template <int LOSS>
+struct StreamRegRounds<Ndt6Problem<float, LOSS>, float> { static constexpr int kRR = 0; };
+constexpr int kStreamRegRoundsMax = 3;  // the largest kRR: the range of the option stream_reg_rounds
+
 // SI > 0 selects the STREAMING form of the same kernel (instantiated with RI = LI = 0): the data set does not fit the
 // register files and LDS of the chip, so every LM iteration streams it from HBM again, in chunks of BLOCK * SI
 // correspondences taken grid-stride exactly like assemble_kernel does — but the loop still lives in ONE launch: no kernel
 // boundary, no launch prologue and no ticket + last-block reduce per iteration (≈ 5 µs of every iteration at 10 M), the
 // tagged all-reduce instead, and the first chunk of iteration k + 1 is already in flight while iteration k is being
 // reduced and stepped (it does not depend on the pose).  `items_per_lane` then carries the number of chunks, and
-// `stream_lds` the number of chunks every workgroup keeps in dynamic LDS from iteration 1 on (below).  SPF: the next
-// chunk's loads are issued before the current chunk is evaluated (fp32), NT: non-temporal loads.
+// `stream_lds` the number of chunks every workgroup keeps in dynamic LDS from iteration 1 on, `stream_reg` the number it
+// keeps in registers (below).  SPF: the next chunk's loads are issued before the current chunk is evaluated (fp32), NT:
+// non-temporal loads.
 template <typename Problem, typename T, int BLOCK, int RI, int LI, int SI = 0, bool SPF = false, bool NT = false>
 __global__ __launch_bounds__(BLOCK) void solve_cluster_kernel(TiledLayout L, typename Problem::Params P,
                                                              double* __restrict__ partials, LmDevice* lm, ClusterCtl* ctl,
                                                              double* __restrict__ cost_history, int history_capacity,
                                                              double* entry_host, unsigned long long* seq_host,
                                                              unsigned long long seq, uint32_t items_per_lane,
-                                                             const Mailbox* mail = nullptr, uint32_t stream_lds = 0u) {
+                                                             const Mailbox* mail = nullptr, uint32_t stream_lds = 0u,
+                                                             uint32_t stream_reg = 0u) {
   // mail != nullptr (device-memory mailbox communicator, one process per GPU): the sums of every iteration are exchanged with
   // the other ranks INSIDE this launch — a third stage behind the two of the tagged all-reduce (below)
   constexpr int kF = Problem::kFields;
@@ -280,17 +296,43 @@ __global__ __launch_bounds__(BLOCK) void solve_cluster_kernel(TiledLayout L, typ
   constexpr int kSI = SI > 0 ? SI : 1;
   [[maybe_unused]] T xs[kF][kSI];
   [[maybe_unused]] uint64_t xs_i0 = 0;
-  // Streaming form, what stays on chip between iterations: `stream_lds` (grid-uniform, 0 … 3) of this workgroup's chunks.
-  // Workgroup b evaluates chunks b, b + grid, b + 2 grid, … — its "rounds" 0, 1, 2, … — in that order in every iteration,
-  // so one workgroup always reads the same chunks.  That many of its rounds, spread evenly through the pass and never
-  // round 0 (the one prefetched during the all-reduce), are copied to dynamic LDS ([slot][field][lane][SI]) as iteration 0
-  // streams them and read from there afterwards.  Every lane keeps its order of items: the same sums, bit for bit.
+  // Streaming form, what stays on chip between iterations: `stream_lds` (grid-uniform, 0 … 3) of this workgroup's chunks in
+  // LDS and `stream_reg` (0 … kRR) in registers.  Workgroup b evaluates chunks b, b + grid, b + 2 grid, … — its "rounds"
+  // 0, 1, 2, … — in that order in every iteration, so one workgroup always reads the same chunks.  That many of its rounds,
+  // spread evenly through the pass, distinct, and never round 0 (the one prefetched during the all-reduce), are copied as
+  // iteration 0 streams them — to dynamic LDS ([slot][field][lane][SI]) or to the register slots xr — and read from there
+  // afterwards.  A workgroup with few rounds keeps fewer (LDS first).  Every lane keeps its order of items: the same sums,
+  // bit for bit.
+  [[maybe_unused]] constexpr int kRR = (SI > 0 && !SPF) ? StreamRegRounds<Problem, T>::kRR : 0;
+  static_assert(kRR <= kStreamRegRoundsMax, "the option's range covers every instantiation");
+  [[maybe_unused]] T xr[kRR > 0 ? kRR : 1][kF][kSI];  // statically indexed everywhere: registers
   [[maybe_unused]] const uint32_t my_rounds = blockIdx.x < J ? (J - blockIdx.x + gridDim.x - 1) / gridDim.x : 0u;
   [[maybe_unused]] const uint32_t lds_k = SI > 0 ? min(stream_lds, my_rounds > 0u ? my_rounds - 1u : 0u) : 0u;
+  [[maybe_unused]] const uint32_t reg_k = kRR > 0 ? min(min(stream_reg, uint32_t(kRR)), (my_rounds > 0u ? my_rounds - 1u : 0u) - lds_k) : 0u;
+  // The lds_k + reg_k on-chip rounds sit at rounds (i + 1) my_rounds / (lds_k + reg_k + 1), i = 0 …: 1 ≤ … < my_rounds,
+  // increasing.  LDS and register slots alternate (LDS first) as long as there are both, the kind left over takes the rest.
+  [[maybe_unused]] const uint32_t alt_k = min(lds_k, reg_k);
+  [[maybe_unused]] auto chip_round = [&](uint32_t i) -> uint32_t {
+    return uint32_t(uint64_t(i + 1u) * my_rounds / (lds_k + reg_k + 1u));
+  };
+  [[maybe_unused]] auto lds_slot_round = [&](uint32_t sl) -> uint32_t {
+    return sl < lds_k ? chip_round(sl < alt_k ? 2u * sl : alt_k + sl) : ~0u;
+  };
   // round of LDS slot s (s < lds_k: 1 ≤ r(0) < r(1) < r(2) < my_rounds), no round beyond the last slot
-  [[maybe_unused]] const uint32_t lds_r0 = lds_k > 0u ? my_rounds / (lds_k + 1u) : ~0u;
-  [[maybe_unused]] const uint32_t lds_r1 = lds_k > 1u ? uint32_t(2ull * my_rounds / (lds_k + 1u)) : ~0u;
-  [[maybe_unused]] const uint32_t lds_r2 = lds_k > 2u ? uint32_t(3ull * my_rounds / (lds_k + 1u)) : ~0u;
+  [[maybe_unused]] const uint32_t lds_r0 = lds_slot_round(0u);
+  [[maybe_unused]] const uint32_t lds_r1 = lds_slot_round(1u);
+  [[maybe_unused]] const uint32_t lds_r2 = lds_slot_round(2u);
+  // round of register slot j (j < reg_k, increasing), ~0u for a slot that is not used
+  [[maybe_unused]] uint32_t reg_r[kRR > 0 ? kRR : 1];
+#pragma unroll
+  for (int j = 0; j < (kRR > 0 ? kRR : 1); ++j)
+    reg_r[j] = uint32_t(j) < reg_k ? chip_round(uint32_t(j) < alt_k ? 2u * uint32_t(j) + 1u : alt_k + uint32_t(j)) : ~0u;
+#pragma unroll
+  for (int j = 0; j < (kRR > 0 ? kRR : 1); ++j)
+#pragma unroll
+    for (int f = 0; f < kF; ++f)
+#pragma unroll
+      for (int e = 0; e < kSI; ++e) xr[j][f][e] = T(0);
   [[maybe_unused]] auto lds_round = [&](uint32_t s) -> uint32_t { return s == 0u ? lds_r0 : s == 1u ? lds_r1 : s == 2u ? lds_r2 : ~0u; };
   [[maybe_unused]] auto fetch_chunk = [&](uint32_t c, T (&dst)[kF][kSI]) -> uint64_t {
     const uint64_t i0 = uint64_t(c) * (uint64_t(BLOCK) * kSI) + uint64_t(threadIdx.x) * kSI;
@@ -392,37 +434,104 @@ __global__ __launch_bounds__(BLOCK) void solve_cluster_kernel(TiledLayout L, typ
             Problem::item(xi, P, (i0 + e) < L.n, acc);
           }
         };
-        // iteration 0 fills the LDS slots from the streamed registers; the later ones read them instead of streaming
-        const bool from_lds = it != 0u;  // grid-uniform
-        uint32_t s = 0;                  // LDS slot of the next resident round
+        // iteration 0 fills the LDS and register slots from the streamed registers; the later ones read them instead of streaming
+        const bool on_chip = it != 0u;  // grid-uniform
+        uint32_t s = 0;                 // LDS slot of the next round kept in LDS
         uint32_t next_res = lds_round(0u);
-        auto evaluate_lds_rounds = [&](uint32_t k0, uint32_t k1) {  // rounds k0 … k1 - 1, all of them in LDS
-          for (uint32_t kr = k0; kr < k1; ++kr) {
-            evaluate_lds(s, blockIdx.x + kr * gridDim.x);
-            next_res = lds_round(++s);
-          }
+        auto in_registers = [&](uint32_t r) -> bool {
+          bool hit = false;
+#pragma unroll
+          for (int j = 0; j < kRR; ++j) hit = hit || r == reg_r[j];
+          return hit;
         };
-        // One trip per streamed round k; xs is written once per trip, whatever comes next, so that the loads land in the
-        // registers they are evaluated from (a conditional refill makes the compiler load into copies and wait for them).
-        for (uint32_t k = 0; k < my_rounds;) {  // block-uniform
-          __builtin_amdgcn_sched_barrier(0);  // all loads of a chunk before any of its math (see assemble_kernel)
-          if (!from_lds && k == next_res) {  // iteration 0: keep this chunk
+        // The pass is cut into kRR + 1 segments, unrolled, so that register slot j has a compile-time index: segment j is
+        // the trip loop over the streamed and LDS rounds in front of slot j's round, then that round from its registers
+        // (iteration 0: the trip loop runs through that round too and copies it out of xs).  A slot that is not used ends no
+        // segment: the first segment behind the last used slot runs to the end of the pass, the others make no trip.
+        // One trip per streamed round k; xs is written once per trip, by that trip's one load path, whatever comes next, so
+        // that the loads land in the registers they are evaluated from (a conditional refill makes the compiler load into
+        // copies and wait for them).  xr is only ever copied out of xs, never loaded into.
+        uint32_t k = 0;  // the next streamed round: xs holds it (or its loads are in flight)
+        if constexpr (kRR == 0) {
+          // no register slot: round 6's loop as it was (the segmented form below costs the fp32 6-DoF kernel 5 % even with
+          // nothing in registers, profiles/r07_ab.txt)
+          while (k < my_rounds) {  // block-uniform
+            __builtin_amdgcn_sched_barrier(0);  // all loads of a chunk before any of its math (see assemble_kernel)
+            if (!on_chip && k == next_res) {  // iteration 0: keep this chunk
 #pragma unroll
-            for (int f = 0; f < kF; ++f)
+              for (int f = 0; f < kF; ++f)
 #pragma unroll
-              for (int e = 0; e < kSI; ++e) lds_at(s, f, e) = xs[f][e];
-            next_res = lds_round(++s);
+                for (int e = 0; e < kSI; ++e) lds_at(s, f, e) = xs[f][e];
+              next_res = lds_round(++s);
+            }
+            evaluate(xs, xs_i0);
+            uint32_t kn = k + 1u;
+            if (on_chip)
+              for (uint32_t sn = s; kn == lds_round(sn); ++sn) ++kn;
+            xs_i0 = fetch_chunk(blockIdx.x + (kn < my_rounds ? kn : 0u) * gridDim.x, xs);
+            for (uint32_t kr = k + 1u; kr < kn; ++kr) {  // the LDS rounds in between, while those loads are in flight
+              evaluate_lds(s, blockIdx.x + kr * gridDim.x);
+              next_res = lds_round(++s);
+            }
+            k = kn;
           }
-          evaluate(xs, xs_i0);
-          // the next streamed round, past the rounds that LDS serves
-          uint32_t kn = k + 1u;
-          if (from_lds)
-            for (uint32_t sn = s; kn == lds_round(sn); ++sn) ++kn;
-          // past the last round: the first chunk of the NEXT iteration, in flight during the all-reduce and the step below
-          // (every wave does, the polling ones too: letting only the other half prefetch measured 2 % slower at 10 M)
-          xs_i0 = fetch_chunk(blockIdx.x + (kn < my_rounds ? kn : 0u) * gridDim.x, xs);
-          evaluate_lds_rounds(k + 1u, kn);  // while those loads are in flight
-          k = kn;
+        } else
+#pragma unroll
+        for (int j = 0; j <= kRR; ++j) {
+          const uint32_t rj = j < kRR ? reg_r[j < kRR ? j : 0] : ~0u;
+          const uint32_t stop = min(rj, my_rounds);                            // rounds below belong to this segment
+          const uint32_t hi = (!on_chip && rj != ~0u) ? rj + 1u : stop;        // streamed rounds below are this segment's trips
+          auto lds_rounds_below = [&](uint32_t lim) {  // the LDS rounds in front of round lim
+            while (next_res < lim) {
+              evaluate_lds(s, blockIdx.x + next_res * gridDim.x);
+              next_res = lds_round(++s);
+            }
+          };
+          if (on_chip && j > 0) lds_rounds_below(min(k, stop));  // those behind the previous segment's register round
+          while (k < hi) {  // block-uniform
+            __builtin_amdgcn_sched_barrier(0);  // all loads of a chunk before any of its math (see assemble_kernel)
+            if (!on_chip) {  // iteration 0: keep this chunk
+              if (k == next_res) {
+#pragma unroll
+                for (int f = 0; f < kF; ++f)
+#pragma unroll
+                  for (int e = 0; e < kSI; ++e) lds_at(s, f, e) = xs[f][e];
+                next_res = lds_round(++s);
+              }
+              if constexpr (kRR > 0) {
+                if (j < kRR && k == rj) {
+#pragma unroll
+                  for (int f = 0; f < kF; ++f)
+#pragma unroll
+                    for (int e = 0; e < kSI; ++e) xr[j < kRR ? j : 0][f][e] = xs[f][e];
+                }
+              }
+            }
+            evaluate(xs, xs_i0);
+            // the next streamed round, past the rounds that LDS and the registers serve
+            uint32_t kn = k + 1u;
+            if (on_chip) {
+              for (uint32_t sn = s;;) {
+                if (kn == lds_round(sn)) {
+                  ++sn;
+                  ++kn;
+                } else if (in_registers(kn)) {
+                  ++kn;
+                } else {
+                  break;
+                }
+              }
+            }
+            // past the last round: the first chunk of the NEXT iteration, in flight during the all-reduce and the step below
+            // (every wave does, the polling ones too: letting only the other half prefetch measured 2 % slower at 10 M)
+            xs_i0 = fetch_chunk(blockIdx.x + (kn < my_rounds ? kn : 0u) * gridDim.x, xs);
+            if (on_chip) lds_rounds_below(min(kn, stop));  // while those loads are in flight
+            k = kn;
+          }
+          if constexpr (kRR > 0) {
+            if (j < kRR && on_chip && rj != ~0u)
+              evaluate(xr[j < kRR ? j : 0], uint64_t(blockIdx.x + rj * gridDim.x) * (uint64_t(BLOCK) * kSI) + uint64_t(threadIdx.x) * kSI);
+          }
         }
       }
       if constexpr (SPF) {

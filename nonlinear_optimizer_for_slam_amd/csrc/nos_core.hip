@@ -260,6 +260,7 @@ struct SingleBlockArgs {
   int stream_chunks = 0;   // > 0: the streaming form (nothing resident; this many chunks of 512 x SI per iteration)
   bool nt = false;         // streaming form: non-temporal loads
   int stream_lds_chunks = 0;      // streaming form: chunks per workgroup kept in LDS after iteration 0
+  int stream_reg_rounds = 0;      // streaming form: rounds per workgroup kept in vector registers after iteration 0
   bool stage1_sc1 = false; // keep stage 1 of the tagged all-reduce on sc1 stores even where a group sits on one XCD (lm_cluster 5)
   const nos::Mailbox* mail = nullptr;  // device-memory mailbox communicator: the cross-rank exchange runs inside the launch
   double* partials = nullptr;
@@ -299,10 +300,12 @@ int launch_single(const nos::TiledLayout& L, const typename Problem::Params& P, 
       lds = 0;
       dyn_bytes = 0;
     }
+    // rounds every workgroup keeps in registers from iteration 1 on (the kernel clamps to its own slot and round counts)
+    const uint32_t reg = uint32_t(std::min(std::max(a.stream_reg_rounds, 0), nos::kStreamRegRoundsMax));
     t_last_kernel = reinterpret_cast<const void*>(kernel);
     hipLaunchKernelGGL(kernel, dim3(a.cluster_blocks), dim3(kBlock), dyn_bytes, stream, L, P, a.partials, a.lm, a.ctl, a.history,
                        a.history_capacity, a.entry, a.seq_host, a.seq, uint32_t(a.stream_chunks) | (a.stage1_sc1 ? 0x80000000u : 0u),
-                       a.mail, lds);
+                       a.mail, lds, reg);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(NOS_ERR_HIP, "streaming solve launch failed: %s", hipGetErrorString(e));
     return NOS_OK;
@@ -327,7 +330,7 @@ int launch_single(const nos::TiledLayout& L, const typename Problem::Params& P, 
     t_last_kernel = reinterpret_cast<const void*>(kernel);
     hipLaunchKernelGGL(kernel, dim3(a.cluster_blocks), dim3(kBlock), dyn_bytes, stream, L, P, a.partials, a.lm, a.ctl,
                        a.history, a.history_capacity, a.entry, a.seq_host, a.seq,
-                       uint32_t(a.items_per_lane) | (a.stage1_sc1 ? 0x80000000u : 0u), a.mail, 0u);
+                       uint32_t(a.items_per_lane) | (a.stage1_sc1 ? 0x80000000u : 0u), a.mail, 0u, 0u);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(NOS_ERR_HIP, "cluster solve launch failed: %s", hipGetErrorString(e));
     return NOS_OK;
@@ -829,6 +832,7 @@ int lm_solve(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, doub
       cl.stream_chunks = int(sh.layout.n_padded / stream_chunk);
       cl.nt = use_nontemporal(ds, sh);
       cl.stream_lds_chunks = ctx->settings.stream_lds_chunks;
+      cl.stream_reg_rounds = ctx->settings.stream_reg_rounds;
     }
     cl.stage1_sc1 = ctx->settings.lm_cluster == 5;
     cl.mail = mailbox_in_launch ? ctx->d_mail : nullptr;
@@ -1567,6 +1571,7 @@ int nos_ctx_create(const int* device_ids, int n_devices, nos_ctx** out_ctx) {
     st.lm_cluster = env_int("NOS_LM_CLUSTER", st.lm_cluster);
     st.lm_cluster_max_blocks = env_int("NOS_LM_CLUSTER_MAX_BLOCKS", st.lm_cluster_max_blocks);
     st.stream_lds_chunks = env_int("NOS_STREAM_LDS_CHUNKS", st.stream_lds_chunks);
+    st.stream_reg_rounds = env_int("NOS_STREAM_REG_ROUNDS", st.stream_reg_rounds);
     st.batch_max_elements = env_int("NOS_BATCH_MAX_ELEMENTS", st.batch_max_elements);
     st.pool = env_int("NOS_POOL", st.pool);
     st.tile_log2 = env_int("NOS_TILE_LOG2", int(kDefaultTileLog2));
@@ -1758,6 +1763,7 @@ const OptionEntry kOptions[] = {
     {"debug_cluster_abort", &nosd::Settings::debug_cluster_abort, 0, 2},
     {"lm_cluster_max_blocks", &nosd::Settings::lm_cluster_max_blocks, 1, 256},
     {"stream_lds_chunks", &nosd::Settings::stream_lds_chunks, 0, 3},
+    {"stream_reg_rounds", &nosd::Settings::stream_reg_rounds, 0, nos::kStreamRegRoundsMax},
     {"batch_max_elements", &nosd::Settings::batch_max_elements, 0, 1 << 30},
 };
 bool option_in_range(const OptionEntry& o, int value);

@@ -170,6 +170,8 @@ struct Settings {
   int lm_cluster_max_blocks = 256;  // NOS_LM_CLUSTER_MAX_BLOCKS  workgroups of the one-launch loop (rehearsals: ranks sharing a GPU)
   int stream_lds_chunks = 3;   // NOS_STREAM_LDS_CHUNKS  streamed one-launch loop: chunks per workgroup kept in LDS after
                                //                        iteration 0 (0 … 3; 0 = everything streamed every iteration)
+  int stream_reg_rounds = 3;   // NOS_STREAM_REG_ROUNDS  streamed one-launch loop: rounds per workgroup kept in vector registers
+                               //                        after iteration 0 (0 … 3, clamped per kernel; 0 = none)
   int batch_max_elements = int(nos::kSingleBlockMaxElements);  // NOS_BATCH_MAX_ELEMENTS  nos_*_solve_batch: a flat problem
                                // of n x planes ≤ this runs in the batch launch (one workgroup), a larger one as a lone solve
 };
