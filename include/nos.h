@@ -314,6 +314,43 @@ int nos_map_stats_get(const nos_map_stats* stats, double* means_xyz, double* sqr
 int nos_map_stats_get_eigen(const nos_map_stats* stats, double* eigenvalues, double* eigenvectors);
 int nos_map_stats_destroy(nos_map_stats* stats);
 
+/* ---- incremental NDT voxel map on the device ---------------------
+ * UpdateNdtMap of the reference's test harness is an UPDATE (MDM/tests/simple_optimization_test.cc:236-281): it adds a
+ * batch of points to the count / sum / moment of the voxels they fall into, in a map that already exists (:240-252), and
+ * re-derives mean, covariance, eigen-decomposition and sqrt-information for the touched voxels only
+ * (updated_voxel_key_set, :254-280).  nos_ndt_map_build above is the one-shot form; a nos_voxel_map is the map that
+ * exists between calls: a growable, device-resident store of per-voxel key, count, the nine sums, mean, sqrt-information
+ * and validity.  An insert costs what its batch costs, never what the points already absorbed would.
+ *   flags: 0 (harness formula) or NOS_MAP_PROPER_SQRT_INFORMATION.  NOS_MAP_REFERENCE_EXACT is rejected with
+ *   NOS_ERR_UNSUPPORTED: its sequential, calibrated accumulation in point order is a different piece of work (one-shot
+ *   builds only).  capacity_hint (voxels) only avoids early growth: arrays and table double as needed.  Single-device
+ *   contexts only, like the map build; voxel coordinates are limited to +-2^20 cells per axis, a voxel to 2^32 - 1 points.
+ * Voxel ids (the order of nos_voxel_map_stats, the matcher's tie-break in a snapshot) are a function of the sequence of
+ * batches alone: batch of first appearance, then ascending integer cell coordinates.  One insert into an empty store
+ * gives the statistics of nos_ndt_map_build bit for bit; sums are merged per voxel as store + batch, so results after
+ * several inserts agree with a one-shot build to rounding (exactly when the sums are exact).
+ * A batch that holds a non-finite coordinate (NOS_ERR_INVALID_ARGUMENT) or a point outside the addressable grid
+ * (NOS_ERR_UNSUPPORTED) is rejected as a whole and leaves the store unchanged, like every rejected call here (a rejected
+ * call writes nothing, *n_touched included).  n_points == 0 is a no-op.  *n_touched (optional) = voxels the batch fell into. */
+typedef struct nos_voxel_map nos_voxel_map;
+int nos_voxel_map_create(nos_ctx* ctx, double voxel_resolution, double search_radius_sq, int flags,
+                         size_t capacity_hint, nos_voxel_map** out);
+/* points_xyz: [n_points][3] host memory, map frame (:240-252) */
+int nos_voxel_map_insert(nos_voxel_map* map, size_t n_points, const double* points_xyz, size_t* n_touched);
+/* The points of a device-resident scan (local frame), warped by R p + t on the device with the operation order of the
+ * matcher's warp: what the harness does between OptimizePose and the next UpdateNdtMap.  Only the pose crosses PCIe. */
+int nos_voxel_map_insert_scan(nos_voxel_map* map, nos_scan* scan, const double R[9], const double t[3],
+                              size_t* n_touched);
+/* Any output pointer may be NULL.  n_voxels: voxels that hold at least one point; n_valid: NDT::is_valid among them
+ * (MDM/types.h:21); n_points: points absorbed. */
+int nos_voxel_map_info(const nos_voxel_map* map, size_t* n_voxels, size_t* n_valid, unsigned long long* n_points);
+/* A ready-to-match nos_ndt_map of the store as it is now: an ordinary, independent map (destroy it with
+ * nos_ndt_map_destroy) that stays valid after later inserts and after the store is destroyed. */
+int nos_voxel_map_snapshot(nos_voxel_map* map, nos_ndt_map** out_map);
+/* The per-voxel numbers in voxel-id order; read with nos_map_stats_get, free with nos_map_stats_destroy. */
+int nos_voxel_map_stats(nos_voxel_map* map, nos_map_stats** out_stats);
+int nos_voxel_map_destroy(nos_voxel_map* map);
+
 /* ---- the hot path -------------------------------------------------------------
  * nos_ndt6_accumulate replaces
  *   MahalanobisDistanceMinimizerAnalyticSIMD::ComputeCostAndDerivatives

@@ -31,7 +31,9 @@ C_ABI_SYMBOLS = (
     "nos_ndt_dataset_create_from_records", "nos_reproj_dataset_create_from_records",
     "nos_dataset_download", "nos_ndt_map_create", "nos_ndt_map_destroy", "nos_ndt_map_size", "nos_scan_create",
     "nos_scan_destroy", "nos_scan_size", "nos_scan_sort_by_cell", "nos_scan_order", "nos_ndt_match", "nos_ndt_indexed_dataset_create", "nos_ndt_match_indexed", "nos_ndt_map_build", "nos_map_stats_size",
-    "nos_map_stats_get", "nos_map_stats_get_eigen", "nos_map_stats_destroy", "nos_dataset_drop_last_matches", "nos_pgo_create", "nos_pgo_destroy", "nos_pgo_num_unknowns",
+    "nos_map_stats_get", "nos_map_stats_get_eigen", "nos_map_stats_destroy",
+    "nos_voxel_map_create", "nos_voxel_map_insert", "nos_voxel_map_insert_scan", "nos_voxel_map_info", "nos_voxel_map_snapshot",
+    "nos_voxel_map_stats", "nos_voxel_map_destroy", "nos_dataset_drop_last_matches", "nos_pgo_create", "nos_pgo_destroy", "nos_pgo_num_unknowns",
     "nos_pgo_linearize", "nos_pgo_solve", "nos_pgo_retract", "nos_pgo_get_state", "nos_pgo_get_vector",
     "nos_pgo_matvec", "nos_pgo_time_sweep", "nos_pgo_layout_info", "nos_debug_lm_step", "nos_dataset_destroy", "nos_dataset_size", "nos_dataset_dtype", "nos_dataset_stream_bytes",
     "nos_dataset_set_simd_class",
@@ -159,6 +161,14 @@ def _declare(lib):
     if hasattr(lib, "nos_map_stats_get_eigen"):
         lib.nos_map_stats_get_eigen.argtypes = [vp, dp, dp]
     lib.nos_map_stats_destroy.argtypes = [vp]
+    if hasattr(lib, "nos_voxel_map_create"):  # absent from older builds loaded through NOS_HIP_LIB
+        lib.nos_voxel_map_create.argtypes = [vp, ctypes.c_double, ctypes.c_double, i, sz, c_void_pp]
+        lib.nos_voxel_map_insert.argtypes = [vp, sz, dp, ctypes.POINTER(sz)]
+        lib.nos_voxel_map_insert_scan.argtypes = [vp, vp, dp, dp, ctypes.POINTER(sz)]
+        lib.nos_voxel_map_info.argtypes = [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_ulonglong)]
+        lib.nos_voxel_map_snapshot.argtypes = [vp, c_void_pp]
+        lib.nos_voxel_map_stats.argtypes = [vp, c_void_pp]
+        lib.nos_voxel_map_destroy.argtypes = [vp]
     if hasattr(lib, "nos_dataset_drop_last_matches"):
         lib.nos_dataset_drop_last_matches.argtypes = [vp, sz]
     ip = ctypes.POINTER(ctypes.c_int32)

@@ -701,6 +701,107 @@ class NdtMap:
             pass
 
 
+def _read_map_stats(lib, hs):
+    """nos_map_stats handle → dict with means, sqrt_infos, valid, counts, cells (the handle stays the caller's)."""
+    V = int(lib.nos_map_stats_size(hs))
+    means = np.zeros((V, 3))
+    S = np.zeros((V, 9))
+    valid = np.zeros(V, dtype=np.uint8)
+    counts = np.zeros(V, dtype=np.uint32)
+    cells = np.zeros((V, 3), dtype=np.int64)
+    check(lib.nos_map_stats_get(hs, _dp(means), _dp(S), valid.ctypes.data_as(ctypes.c_char_p),
+                                counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                cells.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), "nos_map_stats_get")
+    return {"means": means, "sqrt_infos": S.reshape(V, 3, 3), "valid": valid.astype(bool), "counts": counts, "cells": cells}
+
+
+class VoxelMap:
+    """Incremental NDT voxel map (nos_voxel_map): a device-resident store that grows scan by scan — the reference's
+    UpdateNdtMap used as the update it is.  insert() / insert_scan() add a batch to the voxels it falls into and
+    re-derive the statistics of those voxels only; snapshot() gives an ordinary, independent NdtMap to match against.
+
+    Voxel ids (the order of stats(), the matcher's tie-break) follow the sequence of batches: batch of first appearance,
+    then ascending cell.  proper_sqrt_information as in NdtMap.build; capacity (voxels) only avoids early growth."""
+
+    def __init__(self, ctx, voxel_resolution=1.0, search_radius_sq=1.0, proper_sqrt_information=True, capacity=0,
+                 flags=None):
+        self._ctx = ctx
+        self._lib = ctx._lib
+        self._h = None
+        h = ctypes.c_void_p()
+        flags = int(bool(proper_sqrt_information)) if flags is None else int(flags)
+        check(self._lib.nos_voxel_map_create(ctx.handle, ctypes.c_double(voxel_resolution), ctypes.c_double(search_radius_sq),
+                                             flags, int(capacity), ctypes.byref(h)), "nos_voxel_map_create")
+        self._h = h
+        ctx._adopt(self)
+
+    def insert(self, points):
+        """points [n,3] in the map frame (host) → number of voxels the batch fell into."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = ctypes.c_size_t()
+        check(self._lib.nos_voxel_map_insert(self._h, pts.shape[0], _dp(pts), ctypes.byref(n)), "nos_voxel_map_insert")
+        return int(n.value)
+
+    def insert_scan(self, scan, R, t):
+        """The points of an api.Scan warped by R p + t on the device → number of voxels touched."""
+        R = _dvec(R, 9)
+        t = _dvec(t, 3)
+        n = ctypes.c_size_t()
+        check(self._lib.nos_voxel_map_insert_scan(self._h, scan._h, _dp(R), _dp(t), ctypes.byref(n)),
+              "nos_voxel_map_insert_scan")
+        return int(n.value)
+
+    def snapshot(self):
+        """→ NdtMap of the store as it is now; it stays valid after later inserts and after close()."""
+        h = ctypes.c_void_p()
+        check(self._lib.nos_voxel_map_snapshot(self._h, ctypes.byref(h)), "nos_voxel_map_snapshot")
+        m = NdtMap.__new__(NdtMap)
+        m._ctx = self._ctx
+        m._lib = self._lib
+        m._h = h
+        self._ctx._adopt(m)
+        return m
+
+    def stats(self):
+        """→ dict with means, sqrt_infos, valid, counts, cells in voxel-id order (the keys NdtMap.build returns)."""
+        hs = ctypes.c_void_p()
+        check(self._lib.nos_voxel_map_stats(self._h, ctypes.byref(hs)), "nos_voxel_map_stats")
+        try:
+            return _read_map_stats(self._lib, hs)
+        finally:
+            self._lib.nos_map_stats_destroy(hs)
+
+    def _info(self):
+        v, ok, n = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_ulonglong()
+        check(self._lib.nos_voxel_map_info(self._h, ctypes.byref(v), ctypes.byref(ok), ctypes.byref(n)), "nos_voxel_map_info")
+        return int(v.value), int(ok.value), int(n.value)
+
+    def __len__(self):
+        return self._info()[0]
+
+    @property
+    def n_valid(self):
+        return self._info()[1]
+
+    @property
+    def n_points(self):
+        return self._info()[2]
+
+    def close(self):
+        if self._h:
+            self._lib.nos_voxel_map_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        # at interpreter shutdown the HIP runtime may already be gone: leave the handle to the OS
+        if sys is None or sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Scan:
     """Device-resident scan points in the sensor's local frame (nos_scan): points [n,3]."""
 

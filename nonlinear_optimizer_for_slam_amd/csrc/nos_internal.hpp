@@ -264,6 +264,17 @@ struct nos_scan {
   uint32_t* d_order = nullptr; // after nos_scan_sort_by_cell: original index of the point stored at each position
 };
 
+// per-voxel numbers of a map build (nos_mapbuild.hip) or of a voxel store (nos_voxelmap.hip), on the host
+struct nos_map_stats {
+  std::vector<double> means;            // [V][3] voxel order = ascending packed (ix, iy, iz); reference-exact mode: first seen
+  std::vector<double> sqrt_infos;       // [V][9]
+  std::vector<unsigned char> valid;     // [V]
+  std::vector<uint32_t> counts;         // [V]
+  std::vector<int64_t> cells;           // [V][3] integer voxel coordinates
+  std::vector<double> evals;            // [V][3] un-floored eigenvalues           (reference-exact mode only)
+  std::vector<double> evecs;            // [V][9] row-major eigenvector matrix V   (reference-exact mode only)
+};
+
 namespace nosd {
 
 constexpr int kSeqSlot = 32;  // index (in doubles) of the sequence word inside the pinned block
@@ -385,6 +396,10 @@ int lm_solve(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, doub
 // nos_match.hip: matcher tables from device-resident voxel statistics (valid may be null = all valid)
 int map_create_device(nos_ctx* ctx, size_t n_voxels, const double* d_means, const double* d_S, const unsigned char* d_valid,
                       double search_radius_sq, nos_ndt_map** out_map);
+// nos_mapbuild.hip: voxel_sums_kernel on device-resident 32-byte point records (the incremental store's batches run the
+// build's own kernel, so a segment's nine sums are the same bits from either)
+hipError_t launch_voxel_sums(const double* d_records, const uint32_t* sorted_idx, const uint32_t* seg_offset,
+                             const uint32_t* seg_count, uint32_t n_voxels, double* acc_out, hipStream_t stream);
 // nos_indexed.hip
 int launch_indexed(const nos_dataset* ds, const Shard& sh, const Request& rq, double* partials,
                    const nos::FusedFinal& fin, hipStream_t stream, int* rows_out);

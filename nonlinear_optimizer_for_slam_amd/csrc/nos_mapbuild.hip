@@ -7,16 +7,6 @@
 
 using namespace nosd;
 
-struct nos_map_stats {
-  std::vector<double> means;            // [V][3] voxel order = ascending packed (ix, iy, iz); reference-exact mode: first seen
-  std::vector<double> sqrt_infos;       // [V][9]
-  std::vector<unsigned char> valid;     // [V]
-  std::vector<uint32_t> counts;         // [V]
-  std::vector<int64_t> cells;           // [V][3] integer voxel coordinates
-  std::vector<double> evals;            // [V][3] un-floored eigenvalues           (reference-exact mode only)
-  std::vector<double> evecs;            // [V][9] row-major eigenvector matrix V   (reference-exact mode only)
-};
-
 namespace nosd {
 // nos_mapexact.hip (compiled with -ffp-contract=off)
 hipError_t launch_map_exact(const double* px, const double* py, const double* pz, const uint32_t* sorted_idx,
@@ -24,6 +14,15 @@ hipError_t launch_map_exact(const double* px, const double* py, const double* pz
                             int eigen_version, double* acc, double* mean, double* sqrt_info, unsigned char* valid,
                             double* evals, double* evecs, uint32_t* first_idx, hipStream_t stream);
 }  // namespace nosd
+
+hipError_t nosd::launch_voxel_sums(const double* d_records, const uint32_t* sorted_idx, const uint32_t* seg_offset,
+                                   const uint32_t* seg_count, uint32_t n_voxels, double* acc_out, hipStream_t stream) {
+  if (n_voxels == 0) return hipSuccess;
+  const double* none = nullptr;
+  hipLaunchKernelGGL(nos::voxel_sums_kernel, dim3(unsigned((size_t(n_voxels) * nos::kWave + 255) / 256)), dim3(256), 0, stream, none,
+                     none, none, d_records, sorted_idx, seg_offset, seg_count, n_voxels, acc_out);
+  return hipGetLastError();
+}
 
 extern "C" {
 

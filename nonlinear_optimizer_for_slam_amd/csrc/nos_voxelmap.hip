@@ -1,0 +1,332 @@
+// nos_voxelmap.hip — incremental NDT voxel store: a device-resident map that grows scan by scan.
+#include "nos_internal.hpp"
+
+#include <rocprim/rocprim.hpp>
+
+#include "voxelmap_kernels.hpp"
+
+using namespace nosd;
+
+struct nos_voxel_map {
+  nos_ctx* ctx = nullptr;
+  double voxel_resolution = 1.0;
+  double search_radius_sq = 1.0;
+  int flags = 0;
+  size_t capacity = 0;            // slots the arrays have room for (a power of two); the table has 2 * capacity entries
+  uint32_t n_voxels = 0;          // slots in use
+  size_t n_valid = 0;
+  unsigned long long n_points = 0;
+  void* d_block = nullptr;        // the ONE allocation behind the arrays and the table of `view`
+  unsigned int* d_info = nullptr; // [nos::kInfoWords]
+  bool broken = false;            // a merge reported a probe error: the store's content is undefined
+  nos::VoxelStoreView view{};
+};
+
+namespace {
+
+inline int hip_fail(hipError_t e, const char* what) {
+  return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+}
+
+// Arrays and table for `capacity` slots in one allocation; the table's keys start empty.
+hipError_t store_alloc(size_t capacity, hipStream_t st, void** block, nos::VoxelStoreView* v) {
+  auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+  const size_t table = 2 * capacity;
+  const size_t b_key = up(capacity * sizeof(uint64_t)), b_count = up(capacity * sizeof(uint32_t));
+  const size_t b_acc = up(capacity * 9 * sizeof(double)), b_mean = up(capacity * 3 * sizeof(double));
+  const size_t b_S = up(capacity * 9 * sizeof(double)), b_valid = up(capacity);
+  const size_t b_tkey = up(table * sizeof(unsigned long long)), b_tslot = up(table * sizeof(uint32_t));
+  char* base = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), b_key + b_count + b_acc + b_mean + b_S + b_valid + b_tkey + b_tslot);
+  if (e != hipSuccess) return e;
+  char* p = base;
+  v->key = reinterpret_cast<uint64_t*>(p), p += b_key;
+  v->count = reinterpret_cast<uint32_t*>(p), p += b_count;
+  v->acc = reinterpret_cast<double*>(p), p += b_acc;
+  v->mean = reinterpret_cast<double*>(p), p += b_mean;
+  v->sqrt_info = reinterpret_cast<double*>(p), p += b_S;
+  v->valid = reinterpret_cast<unsigned char*>(p), p += b_valid;
+  v->table_key = reinterpret_cast<unsigned long long*>(p), p += b_tkey;
+  v->table_slot = reinterpret_cast<uint32_t*>(p);
+  v->table_mask = uint32_t(table - 1);
+  e = hipMemsetAsync(v->table_key, 0xFF, table * sizeof(unsigned long long), st);
+  if (e != hipSuccess) {
+    (void)hipFree(base);
+    return e;
+  }
+  *block = base;
+  return hipSuccess;
+}
+
+// Room for `need` slots: arrays and table double (new allocation, device copies, every key hashed into the new table)
+// until they hold them.  The store is untouched when this fails.
+int store_reserve(nos_voxel_map* vm, size_t need) {
+  if (need <= vm->capacity) return NOS_OK;
+  if (need > (size_t(1) << 30)) return fail(NOS_ERR_UNSUPPORTED, "too many voxels for one store");
+  size_t capacity = vm->capacity;
+  while (capacity < need) capacity *= 2;
+  DeviceSlot& slot = vm->ctx->slots[0];
+  hipStream_t st = slot.stream;
+  void* block = nullptr;
+  nos::VoxelStoreView nv{};
+  hipError_t e = store_alloc(capacity, st, &block, &nv);
+  if (e != hipSuccess) return hip_fail(e, "growing the voxel store");
+  const size_t V = vm->n_voxels;
+  nv.n_voxels = vm->n_voxels;
+  unsigned int err = 0;
+  if (V > 0) {
+    const nos::VoxelStoreView& ov = vm->view;
+    e = hipMemcpyAsync(nv.key, ov.key, V * sizeof(uint64_t), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(nv.count, ov.count, V * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(nv.acc, ov.acc, V * 9 * sizeof(double), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(nv.mean, ov.mean, V * 3 * sizeof(double), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(nv.sqrt_info, ov.sqrt_info, V * 9 * sizeof(double), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(nv.valid, ov.valid, V, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(vm->d_info + nos::kInfoProbeError, 0, sizeof(unsigned int), st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(nos::voxel_rehash_kernel, dim3(unsigned((V + 255) / 256)), dim3(256), 0, st, nv, vm->d_info);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&err, vm->d_info + nos::kInfoProbeError, sizeof err, hipMemcpyDeviceToHost, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the old block is freed below
+  if (e != hipSuccess || err != 0) {
+    (void)hipFree(block);
+    if (e != hipSuccess) return hip_fail(e, "growing the voxel store");
+    return fail(NOS_ERR_HIP, "growing the voxel store failed: the new table overflowed");
+  }
+  (void)hipFree(vm->d_block);
+  vm->d_block = block;
+  vm->view = nv;
+  vm->capacity = capacity;
+  return NOS_OK;
+}
+
+// One insert.  host_xyz != nullptr: [n][3] in the map frame; otherwise d_planes = 3 planes of n doubles in a local frame,
+// warped by `pose` on the device.
+int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const double* d_planes, const nos::PosePod& pose,
+                 size_t* n_touched) {
+  if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+  if (n >= 0xFFFFFFFFull) return fail(NOS_ERR_UNSUPPORTED, "too many points for one insert");
+  if (n == 0) {
+    if (n_touched) *n_touched = 0;
+    return NOS_OK;
+  }
+  DeviceSlot& slot = vm->ctx->slots[0];
+  hipStream_t st = slot.stream;
+  DeviceBuffers buf(&slot);  // arena: every temporary comes from the slot's buffer pool — no hipMalloc / hipFree per insert
+  double *rec = nullptr, *staged = nullptr, *seg_acc = nullptr;
+  uint64_t *keys = nullptr, *keys_sorted = nullptr, *uniq = nullptr;
+  uint32_t *idx = nullptr, *idx_sorted = nullptr, *counts = nullptr, *offsets = nullptr, *n_runs = nullptr;
+  uint32_t *run_slot = nullptr, *miss = nullptr, *rank = nullptr;
+  hipError_t e = hipSetDevice(slot.device);
+  buf.reserve(n * (7 * sizeof(double) + 3 * sizeof(uint64_t) + 4 * sizeof(uint32_t)) + (size_t(16) << 20));
+  if (e == hipSuccess) e = buf.alloc(&rec, n * 4);
+  if (e == hipSuccess && host_xyz) e = buf.alloc(&staged, n * 3);
+  if (e == hipSuccess) e = buf.alloc(&keys, n);
+  if (e == hipSuccess) e = buf.alloc(&keys_sorted, n);
+  if (e == hipSuccess) e = buf.alloc(&uniq, n);
+  if (e == hipSuccess) e = buf.alloc(&idx, n);
+  if (e == hipSuccess) e = buf.alloc(&idx_sorted, n);
+  if (e == hipSuccess) e = buf.alloc(&counts, n);
+  if (e == hipSuccess) e = buf.alloc(&offsets, n);
+  if (e == hipSuccess) e = buf.alloc(&n_runs, 1);
+  size_t t1 = 0, t2 = 0, t3 = 0;
+  void* tmp = nullptr;
+  if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, t1, keys, keys_sorted, idx, idx_sorted, n, 0, 63, st);
+  if (e == hipSuccess) e = rocprim::run_length_encode(nullptr, t2, keys_sorted, n, uniq, counts, n_runs, st);
+  if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, t3, counts, offsets, 0u, n, rocprim::plus<uint32_t>(), st);
+  if (e == hipSuccess) e = buf.alloc_bytes(&tmp, std::max(std::max(t1, t2), std::max(t3, size_t(16))));
+  // step 1: records, keys, the finite / in-range check
+  unsigned int h_info[nos::kInfoWords] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t U = 0;
+  if (e == hipSuccess) e = hipMemsetAsync(vm->d_info, 0, 4 * sizeof(unsigned int), st);  // bad, far, probe error, new
+  if (e == hipSuccess && host_xyz) e = hipMemcpyAsync(staged, host_xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    const dim3 grid(unsigned((n + 255) / 256));
+    const double inv_res = 1.0 / vm->voxel_resolution;
+    if (host_xyz)
+      hipLaunchKernelGGL((nos::voxel_points_kernel<false>), grid, dim3(256), 0, st, staged, uint64_t(n), pose, inv_res, rec, keys,
+                         idx, vm->d_info);
+    else
+      hipLaunchKernelGGL((nos::voxel_points_kernel<true>), grid, dim3(256), 0, st, d_planes, uint64_t(n), pose, inv_res, rec, keys,
+                         idx, vm->d_info);
+    e = hipGetLastError();
+  }
+  // step 2: stable sort of (packed key, index), run-length encode.  The packed key orders cells exactly as the build's
+  // compact in-box key does, so a run's points are summed in the order the build sums them.
+  if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, t1, keys, keys_sorted, idx, idx_sorted, n, 0, 63, st);
+  if (e == hipSuccess) e = rocprim::run_length_encode(tmp, t2, keys_sorted, n, uniq, counts, n_runs, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(&U, n_runs, sizeof U, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_info, vm->d_info, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the one wait in the middle: run count and flags
+  if (e != hipSuccess) return hip_fail(e, "voxel store insert (sort)");
+  // nothing of the store has been written so far: a rejected batch leaves it as it was
+  if (h_info[nos::kInfoBadPoint] != 0)
+    return fail(NOS_ERR_INVALID_ARGUMENT, "point %u has a non-finite coordinate", h_info[nos::kInfoBadPoint] - 1u);
+  if (h_info[nos::kInfoFarPoint] != 0)
+    return fail(NOS_ERR_UNSUPPORTED, "point %u lies outside the addressable grid (+-2^20 cells per axis)",
+                h_info[nos::kInfoFarPoint] - 1u);
+  int rc = store_reserve(vm, size_t(vm->n_voxels) + U);  // load factor <= 1/2 whatever the number of new voxels
+  if (rc != NOS_OK) return rc;
+  buf.reserve(size_t(U) * (9 * sizeof(double) + 3 * sizeof(uint32_t)) + (size_t(1) << 20));
+  size_t t4 = 0;
+  void* tmp4 = nullptr;
+  e = buf.alloc(&seg_acc, size_t(U) * 9);
+  if (e == hipSuccess) e = buf.alloc(&run_slot, U);
+  if (e == hipSuccess) e = buf.alloc(&miss, U);
+  if (e == hipSuccess) e = buf.alloc(&rank, U);
+  if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, t4, miss, rank, 0u, size_t(U), rocprim::plus<uint32_t>(), st);
+  if (e == hipSuccess) e = buf.alloc_bytes(&tmp4, std::max(t4, size_t(16)));
+  if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, t3, counts, offsets, 0u, size_t(U), rocprim::plus<uint32_t>(), st);
+  if (e != hipSuccess) return hip_fail(e, "voxel store insert (segments)");
+  // step 3: the build's sums kernel on the batch; step 4: lookup, rank of the misses, merge + finish
+  const nos::MapBuildParams prm{5, 0.01, 0.01, (vm->flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0};
+  e = launch_voxel_sums(rec, idx_sorted, offsets, counts, U, seg_acc, st);
+  if (e != hipSuccess) return hip_fail(e, "voxel store insert (sums)");
+  const dim3 ugrid(unsigned((size_t(U) + 255) / 256));
+  hipLaunchKernelGGL(nos::voxel_lookup_kernel, ugrid, dim3(256), 0, st, vm->view, uniq, U, run_slot, miss, vm->d_info);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = rocprim::exclusive_scan(tmp4, t4, miss, rank, 0u, size_t(U), rocprim::plus<uint32_t>(), st);
+  if (e != hipSuccess) return hip_fail(e, "voxel store insert (lookup)");  // still nothing written
+  hipLaunchKernelGGL(nos::voxel_merge_kernel, ugrid, dim3(256), 0, st, vm->view, uniq, counts, seg_acc, run_slot, rank, U, prm,
+                     vm->d_info);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(h_info, vm->d_info, sizeof h_info, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the wait at the end
+  if (e != hipSuccess || h_info[nos::kInfoProbeError] != 0) {
+    vm->broken = true;
+    if (e != hipSuccess) return hip_fail(e, "voxel store insert (merge)");
+    return fail(NOS_ERR_HIP, "voxel store insert failed: a table probe found no free entry");
+  }
+  vm->n_voxels += h_info[nos::kInfoNew];
+  vm->view.n_voxels = vm->n_voxels;
+  vm->n_valid = size_t(int(h_info[nos::kInfoValid]));
+  vm->n_points += n;
+  if (n_touched) *n_touched = U;
+  return NOS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nos_voxel_map_create(nos_ctx* ctx, double voxel_resolution, double search_radius_sq, int flags, size_t capacity_hint,
+                         nos_voxel_map** out) {
+  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
+  if (!ctx || !out) return fail(NOS_ERR_INVALID_ARGUMENT, "ctx / out is NULL");
+  if (ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "a voxel store needs a single-device context");
+  if (flags & NOS_MAP_REFERENCE_EXACT)
+    return fail(NOS_ERR_UNSUPPORTED, "NOS_MAP_REFERENCE_EXACT accumulates sequentially in point order: one-shot builds only");
+  if (flags & ~NOS_MAP_PROPER_SQRT_INFORMATION) return fail(NOS_ERR_INVALID_ARGUMENT, "unknown flags");
+  if (!(voxel_resolution > 0.0) || !std::isfinite(voxel_resolution)) return fail(NOS_ERR_INVALID_ARGUMENT, "bad voxel resolution");
+  if (!(search_radius_sq > 0.0) || !std::isfinite(search_radius_sq)) return fail(NOS_ERR_INVALID_ARGUMENT, "bad search radius");
+  if (capacity_hint > (size_t(1) << 30)) return fail(NOS_ERR_UNSUPPORTED, "too many voxels for one store");
+  std::unique_ptr<nos_voxel_map> vm(new (std::nothrow) nos_voxel_map());
+  if (!vm) return fail(NOS_ERR_OUT_OF_MEMORY, "host allocation failed");
+  vm->ctx = ctx;
+  vm->voxel_resolution = voxel_resolution;
+  vm->search_radius_sq = search_radius_sq;
+  vm->flags = flags;
+  vm->capacity = 16;
+  while (vm->capacity < capacity_hint) vm->capacity *= 2;
+  DeviceSlot& slot = ctx->slots[0];
+  hipError_t e = hipSetDevice(slot.device);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&vm->d_info), nos::kInfoWords * sizeof(unsigned int));
+  if (e == hipSuccess) e = hipMemsetAsync(vm->d_info, 0, nos::kInfoWords * sizeof(unsigned int), slot.stream);
+  if (e == hipSuccess) e = store_alloc(vm->capacity, slot.stream, &vm->d_block, &vm->view);
+  if (e == hipSuccess) e = hipStreamSynchronize(slot.stream);
+  if (e != hipSuccess) {
+    if (vm->d_info) (void)hipFree(vm->d_info);
+    if (vm->d_block) (void)hipFree(vm->d_block);
+    return hip_fail(e, "voxel store create");
+  }
+  *out = vm.release();
+  return NOS_OK;
+}
+
+int nos_voxel_map_insert(nos_voxel_map* vm, size_t n_points, const double* points_xyz, size_t* n_touched) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!vm) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map is NULL");
+  if (!points_xyz && n_points > 0) return fail(NOS_ERR_INVALID_ARGUMENT, "points is NULL");
+  const nos::PosePod identity{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}};
+  return store_insert(vm, n_points, points_xyz, nullptr, identity, n_touched);
+}
+
+int nos_voxel_map_insert_scan(nos_voxel_map* vm, nos_scan* scan, const double R[9], const double t[3], size_t* n_touched) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!vm || !scan || !R || !t) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (vm->ctx != scan->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map and scan belong to different contexts");
+  nos::PosePod pose;
+  for (int k = 0; k < 9; ++k) pose.R[k] = R[k];
+  for (int k = 0; k < 3; ++k) pose.t[k] = t[k];
+  return store_insert(vm, scan->n, nullptr, scan->d_planes, pose, n_touched);
+}
+
+int nos_voxel_map_info(const nos_voxel_map* vm, size_t* n_voxels, size_t* n_valid, unsigned long long* n_points) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!vm) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map is NULL");
+  if (n_voxels) *n_voxels = vm->n_voxels;
+  if (n_valid) *n_valid = vm->n_valid;
+  if (n_points) *n_points = vm->n_points;
+  return NOS_OK;
+}
+
+int nos_voxel_map_snapshot(nos_voxel_map* vm, nos_ndt_map** out_map) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!vm || !out_map) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+  *out_map = nullptr;
+  // the matcher's tables straight from the store's device-resident statistics; the map copies what it keeps
+  return map_create_device(vm->ctx, vm->n_voxels, vm->view.mean, vm->view.sqrt_info, vm->view.valid, vm->search_radius_sq,
+                           out_map);
+}
+
+int nos_voxel_map_stats(nos_voxel_map* vm, nos_map_stats** out_stats) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!vm || !out_stats) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+  *out_stats = nullptr;
+  std::unique_ptr<nos_map_stats> stats(new (std::nothrow) nos_map_stats());
+  if (!stats) return fail(NOS_ERR_OUT_OF_MEMORY, "host allocation failed");
+  const size_t V = vm->n_voxels;
+  std::vector<uint64_t> h_keys(V);
+  stats->means.resize(V * 3);
+  stats->sqrt_infos.resize(V * 9);
+  stats->valid.resize(V);
+  stats->counts.resize(V);
+  stats->cells.resize(V * 3);
+  if (V > 0) {
+    DeviceSlot& slot = vm->ctx->slots[0];
+    hipStream_t st = slot.stream;
+    const nos::VoxelStoreView& v = vm->view;
+    hipError_t e = hipSetDevice(slot.device);
+    if (e == hipSuccess) e = hipMemcpyAsync(stats->means.data(), v.mean, V * 3 * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(stats->sqrt_infos.data(), v.sqrt_info, V * 9 * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(stats->valid.data(), v.valid, V, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(stats->counts.data(), v.count, V * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_keys.data(), v.key, V * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(e, "voxel store download");
+  }
+  const int64_t bias = int64_t(1) << 20;
+  for (size_t s = 0; s < V; ++s) {
+    stats->cells[3 * s + 0] = int64_t((h_keys[s] >> 42) & 0x1FFFFFull) - bias;
+    stats->cells[3 * s + 1] = int64_t((h_keys[s] >> 21) & 0x1FFFFFull) - bias;
+    stats->cells[3 * s + 2] = int64_t(h_keys[s] & 0x1FFFFFull) - bias;
+  }
+  *out_stats = stats.release();
+  return NOS_OK;
+}
+
+int nos_voxel_map_destroy(nos_voxel_map* vm) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!vm) return NOS_OK;
+  (void)hipSetDevice(vm->ctx->slots[0].device);
+  if (vm->d_block) (void)hipFree(vm->d_block);
+  if (vm->d_info) (void)hipFree(vm->d_info);
+  delete vm;
+  return NOS_OK;
+}
+
+}  // extern "C"

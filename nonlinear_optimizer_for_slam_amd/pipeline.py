@@ -8,7 +8,7 @@ less than 1e-5 in translation and in the quaternion vector part.
 """
 import numpy as np
 
-from .api import NdtMap, Scan, register3_batch, register6_batch
+from .api import NdtMap, Scan, VoxelMap, register3_batch, register6_batch
 from .solvers import MahalanobisDistanceMinimizerHip, MahalanobisDistanceMinimizerHip3DOF, Options, Pose
 
 
@@ -103,3 +103,23 @@ def scan_to_map_batch(ctx, ndt_map, scans, initial_poses=None, loss=("exponentia
                    "printed_cost": r["printed_cost"]} for r in rep["rounds"]]
         out.append((Pose(R[i].reshape(3, 3), t[i]), rounds, rep["outer_iter"]))
     return out
+
+
+def odometry(ctx, voxel_map, scans, initial_pose=None, **scan_to_map_kwargs):
+    """Scan-to-map odometry over a growing map (api.VoxelMap): for each scan, snapshot the store → scan_to_map from the
+    previous scan's pose → insert the scan at the pose found (VoxelMap.insert_scan, warped on the device).  The harness's
+    sequence UpdateNdtMap → OptimizePose → UpdateNdtMap (MDM/tests/simple_optimization_test.cc:236-281, 474-503) with the
+    map kept on the device between frames.  scans: iterable of api.Scan; scan_to_map_kwargs go to scan_to_map unchanged.
+    → (list of Poses, list of per-scan round lists)."""
+    pose = Pose() if initial_pose is None else Pose(initial_pose.R, initial_pose.t)
+    poses, all_rounds = [], []
+    for scan in scans:
+        ndt_map = voxel_map.snapshot()
+        try:
+            pose, rounds, _ = scan_to_map(ctx, ndt_map, scan, initial_pose=pose, **scan_to_map_kwargs)
+        finally:
+            ndt_map.close()
+        voxel_map.insert_scan(scan, pose.R, pose.t)
+        poses.append(Pose(pose.R, pose.t))
+        all_rounds.append(rounds)
+    return poses, all_rounds
