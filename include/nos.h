@@ -349,6 +349,44 @@ int nos_voxel_map_info(const nos_voxel_map* map, size_t* n_voxels, size_t* n_val
 int nos_voxel_map_snapshot(nos_voxel_map* map, nos_ndt_map** out_map);
 /* The per-voxel numbers in voxel-id order; read with nos_map_stats_get, free with nos_map_stats_destroy. */
 int nos_voxel_map_stats(nos_voxel_map* map, nos_map_stats** out_stats);
+/* Sliding window: removes voxels by a box around a point and / or by age, compacts the survivors on the device and
+ * rebuilds the key -> slot table.  The store can shrink.
+ * Keep rule (exact):
+ *   NOS_PRUNE_BOX: the voxel with integer cell (cx, cy, cz) is kept iff on every axis k
+ *       floor((center[k] - half_extent[k]) * inv_res) <= c_k <= floor((center[k] + half_extent[k]) * inv_res),
+ *     both bounds computed on the host in double with inv_res = 1.0 / voxel_resolution (the factor an insert multiplies a
+ *     coordinate by before floor()), then clamped to the addressable +-2^20 cells (a box that lies wholly beyond them
+ *     keeps nothing).  In words: a voxel survives iff its cell [c res, (c + 1) res) meets the closed box; both faces are
+ *     inclusive.
+ *   NOS_PRUNE_AGE: kept iff epoch - stamp <= max_age, where epoch counts the inserts that returned NOS_OK with at least
+ *     one point (a rejected insert does not advance it) and a voxel's stamp is the epoch of the last insert that touched
+ *     it.  max_age = 0 keeps only what the last insert touched.  Stamps are 32 bits wide: ages are exact below 2^32 inserts.
+ *   With both bits set a voxel must pass both tests.
+ * Voxel ids stay a function of the sequence of calls alone: a prune renumbers the survivors by their rank among the
+ * survivors (their relative order is kept); a cell that was removed and is seen again is a new voxel, appended by the
+ * usual rule, starting from zero count and zero sums.  n_points of nos_voxel_map_info drops by the removed voxels' counts.
+ * When nothing is to be removed the call writes nothing, allocates nothing and leaves `generation` as it was.  When the
+ * survivors fit in a quarter of the capacity, the capacity becomes the smallest power of two >= 2 * survivors (never
+ * below 16 nor below the capacity the store was created with); otherwise it is unchanged.  Results never depend on it.
+ * NOS_ERR_INVALID_ARGUMENT, store unchanged: what == NULL, what->what == 0 or unknown bits, struct_size <
+ * sizeof(nos_voxel_prune), (NOS_PRUNE_BOX) a non-finite center or half_extent or a negative half_extent.  A failure
+ * half-way (e.g. out of memory for the new block) leaves the store exactly as it was.  *n_removed (optional) = voxels
+ * removed; a rejected call does not write it. */
+#define NOS_PRUNE_BOX 1
+#define NOS_PRUNE_AGE 2
+typedef struct nos_voxel_prune {
+  size_t struct_size;            /* sizeof(nos_voxel_prune), for later growth */
+  int what;                      /* NOS_PRUNE_BOX | NOS_PRUNE_AGE, at least one */
+  double center[3];              /* map frame, metric */
+  double half_extent[3];         /* >= 0, finite */
+  unsigned long long max_age;    /* in inserts */
+} nos_voxel_prune;
+int nos_voxel_map_prune(nos_voxel_map* map, const nos_voxel_prune* what, size_t* n_removed);
+/* Any output pointer may be NULL.  capacity: slots the arrays have room for; bytes: device memory the store holds;
+ * epoch: see NOS_PRUNE_AGE; generation: times the store's device block was replaced (growth, a prune that removed
+ * something). */
+int nos_voxel_map_memory(const nos_voxel_map* map, size_t* capacity, size_t* bytes,
+                         unsigned long long* epoch, unsigned long long* generation);
 int nos_voxel_map_destroy(nos_voxel_map* map);
 
 /* ---- the hot path -------------------------------------------------------------

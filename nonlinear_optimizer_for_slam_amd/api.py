@@ -721,7 +721,8 @@ class VoxelMap:
     re-derive the statistics of those voxels only; snapshot() gives an ordinary, independent NdtMap to match against.
 
     Voxel ids (the order of stats(), the matcher's tie-break) follow the sequence of batches: batch of first appearance,
-    then ascending cell.  proper_sqrt_information as in NdtMap.build; capacity (voxels) only avoids early growth."""
+    then ascending cell.  proper_sqrt_information as in NdtMap.build; capacity (voxels) only avoids early growth.
+    prune() removes voxels by a box and / or by age (a sliding window) and renumbers the survivors by their rank."""
 
     def __init__(self, ctx, voxel_resolution=1.0, search_radius_sq=1.0, proper_sqrt_information=True, capacity=0,
                  flags=None):
@@ -770,6 +771,42 @@ class VoxelMap:
             return _read_map_stats(self._lib, hs)
         finally:
             self._lib.nos_map_stats_destroy(hs)
+
+    def prune(self, center=None, half_extent=None, max_age=None):
+        """Sliding window (nos_voxel_map_prune) → number of voxels removed.  center [3] with half_extent ([3], or a scalar
+        for a cube): keep the voxels whose cell meets the closed box center ± half_extent.  max_age: keep the voxels an
+        insert touched within the last max_age inserts (0 = the last insert only).  Both: a voxel must pass both.  The
+        survivors keep their order and are renumbered by rank; the store may shrink."""
+        if (center is None) != (half_extent is None):
+            raise ValueError("center and half_extent go together")
+        if center is None and max_age is None:
+            raise ValueError("prune needs a box (center, half_extent), max_age, or both")
+        rule = _lib.NosVoxelPrune()
+        rule.struct_size = ctypes.sizeof(_lib.NosVoxelPrune)
+        if center is not None:
+            rule.what |= _lib.NOS_PRUNE_BOX
+            c = _dvec(center, 3)
+            h = np.asarray(half_extent, dtype=np.float64)
+            h = np.full(3, float(h)) if h.ndim == 0 else _dvec(h, 3)
+            for k in range(3):
+                rule.center[k], rule.half_extent[k] = c[k], h[k]
+        if max_age is not None:
+            if int(max_age) < 0:
+                raise ValueError("max_age must be >= 0")
+            rule.what |= _lib.NOS_PRUNE_AGE
+            rule.max_age = int(max_age)
+        n = ctypes.c_size_t()
+        check(self._lib.nos_voxel_map_prune(self._h, ctypes.byref(rule), ctypes.byref(n)), "nos_voxel_map_prune")
+        return int(n.value)
+
+    def memory(self):
+        """→ dict: capacity (slots), bytes (device memory held), epoch (successful non-empty inserts so far), generation
+        (times the device block was replaced: growth, a prune that removed something)."""
+        cap, nbytes = ctypes.c_size_t(), ctypes.c_size_t()
+        epoch, gen = ctypes.c_ulonglong(), ctypes.c_ulonglong()
+        check(self._lib.nos_voxel_map_memory(self._h, ctypes.byref(cap), ctypes.byref(nbytes), ctypes.byref(epoch),
+                                             ctypes.byref(gen)), "nos_voxel_map_memory")
+        return {"capacity": int(cap.value), "bytes": int(nbytes.value), "epoch": int(epoch.value), "generation": int(gen.value)}
 
     def _info(self):
         v, ok, n = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_ulonglong()

@@ -13,10 +13,14 @@ struct nos_voxel_map {
   double search_radius_sq = 1.0;
   int flags = 0;
   size_t capacity = 0;            // slots the arrays have room for (a power of two); the table has 2 * capacity entries
+  size_t min_capacity = 0;        // the capacity the store was created with: a prune never shrinks below it
   uint32_t n_voxels = 0;          // slots in use
   size_t n_valid = 0;
   unsigned long long n_points = 0;
+  unsigned long long epoch = 0;   // inserts that merged at least one point; a slot's stamp is the epoch of its last touch
+  unsigned long long generation = 0;  // times d_block was replaced (growth, a prune that removed something)
   void* d_block = nullptr;        // the ONE allocation behind the arrays and the table of `view`
+  size_t block_bytes = 0;
   unsigned int* d_info = nullptr; // [nos::kInfoWords]
   bool broken = false;            // a merge reported a probe error: the store's content is undefined
   nos::VoxelStoreView view{};
@@ -29,15 +33,16 @@ inline int hip_fail(hipError_t e, const char* what) {
 }
 
 // Arrays and table for `capacity` slots in one allocation; the table's keys start empty.
-hipError_t store_alloc(size_t capacity, hipStream_t st, void** block, nos::VoxelStoreView* v) {
+hipError_t store_alloc(size_t capacity, hipStream_t st, void** block, size_t* block_bytes, nos::VoxelStoreView* v) {
   auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
   const size_t table = 2 * capacity;
   const size_t b_key = up(capacity * sizeof(uint64_t)), b_count = up(capacity * sizeof(uint32_t));
   const size_t b_acc = up(capacity * 9 * sizeof(double)), b_mean = up(capacity * 3 * sizeof(double));
-  const size_t b_S = up(capacity * 9 * sizeof(double)), b_valid = up(capacity);
+  const size_t b_S = up(capacity * 9 * sizeof(double)), b_valid = up(capacity), b_stamp = up(capacity * sizeof(uint32_t));
   const size_t b_tkey = up(table * sizeof(unsigned long long)), b_tslot = up(table * sizeof(uint32_t));
   char* base = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), b_key + b_count + b_acc + b_mean + b_S + b_valid + b_tkey + b_tslot);
+  const size_t bytes = b_key + b_count + b_acc + b_mean + b_S + b_valid + b_stamp + b_tkey + b_tslot;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
   if (e != hipSuccess) return e;
   char* p = base;
   v->key = reinterpret_cast<uint64_t*>(p), p += b_key;
@@ -46,6 +51,7 @@ hipError_t store_alloc(size_t capacity, hipStream_t st, void** block, nos::Voxel
   v->mean = reinterpret_cast<double*>(p), p += b_mean;
   v->sqrt_info = reinterpret_cast<double*>(p), p += b_S;
   v->valid = reinterpret_cast<unsigned char*>(p), p += b_valid;
+  v->stamp = reinterpret_cast<uint32_t*>(p), p += b_stamp;
   v->table_key = reinterpret_cast<unsigned long long*>(p), p += b_tkey;
   v->table_slot = reinterpret_cast<uint32_t*>(p);
   v->table_mask = uint32_t(table - 1);
@@ -55,6 +61,7 @@ hipError_t store_alloc(size_t capacity, hipStream_t st, void** block, nos::Voxel
     return e;
   }
   *block = base;
+  *block_bytes = bytes;
   return hipSuccess;
 }
 
@@ -68,8 +75,9 @@ int store_reserve(nos_voxel_map* vm, size_t need) {
   DeviceSlot& slot = vm->ctx->slots[0];
   hipStream_t st = slot.stream;
   void* block = nullptr;
+  size_t block_bytes = 0;
   nos::VoxelStoreView nv{};
-  hipError_t e = store_alloc(capacity, st, &block, &nv);
+  hipError_t e = store_alloc(capacity, st, &block, &block_bytes, &nv);
   if (e != hipSuccess) return hip_fail(e, "growing the voxel store");
   const size_t V = vm->n_voxels;
   nv.n_voxels = vm->n_voxels;
@@ -82,6 +90,7 @@ int store_reserve(nos_voxel_map* vm, size_t need) {
     if (e == hipSuccess) e = hipMemcpyAsync(nv.mean, ov.mean, V * 3 * sizeof(double), hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(nv.sqrt_info, ov.sqrt_info, V * 9 * sizeof(double), hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(nv.valid, ov.valid, V, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(nv.stamp, ov.stamp, V * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(vm->d_info + nos::kInfoProbeError, 0, sizeof(unsigned int), st);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(nos::voxel_rehash_kernel, dim3(unsigned((V + 255) / 256)), dim3(256), 0, st, nv, vm->d_info);
@@ -97,8 +106,10 @@ int store_reserve(nos_voxel_map* vm, size_t need) {
   }
   (void)hipFree(vm->d_block);
   vm->d_block = block;
+  vm->block_bytes = block_bytes;
   vm->view = nv;
   vm->capacity = capacity;
+  ++vm->generation;
   return NOS_OK;
 }
 
@@ -138,7 +149,7 @@ int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const doub
   if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, t3, counts, offsets, 0u, n, rocprim::plus<uint32_t>(), st);
   if (e == hipSuccess) e = buf.alloc_bytes(&tmp, std::max(std::max(t1, t2), std::max(t3, size_t(16))));
   // step 1: records, keys, the finite / in-range check
-  unsigned int h_info[nos::kInfoWords] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned int h_info[nos::kInfoWords] = {};
   uint32_t U = 0;
   if (e == hipSuccess) e = hipMemsetAsync(vm->d_info, 0, 4 * sizeof(unsigned int), st);  // bad, far, probe error, new
   if (e == hipSuccess && host_xyz) e = hipMemcpyAsync(staged, host_xyz, n * 3 * sizeof(double), hipMemcpyHostToDevice, st);
@@ -190,9 +201,9 @@ int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const doub
   if (e == hipSuccess) e = rocprim::exclusive_scan(tmp4, t4, miss, rank, 0u, size_t(U), rocprim::plus<uint32_t>(), st);
   if (e != hipSuccess) return hip_fail(e, "voxel store insert (lookup)");  // still nothing written
   hipLaunchKernelGGL(nos::voxel_merge_kernel, ugrid, dim3(256), 0, st, vm->view, uniq, counts, seg_acc, run_slot, rank, U, prm,
-                     vm->d_info);
+                     uint32_t(vm->epoch + 1), vm->d_info);
   e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(h_info, vm->d_info, sizeof h_info, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_info, vm->d_info, 5 * sizeof(unsigned int), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);  // the wait at the end
   if (e != hipSuccess || h_info[nos::kInfoProbeError] != 0) {
     vm->broken = true;
@@ -203,7 +214,93 @@ int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const doub
   vm->view.n_voxels = vm->n_voxels;
   vm->n_valid = size_t(int(h_info[nos::kInfoValid]));
   vm->n_points += n;
+  ++vm->epoch;  // what the merge stamped the touched slots with
   if (n_touched) *n_touched = U;
+  return NOS_OK;
+}
+
+// One prune: keep flags and totals, scan, ONE wait; when something goes, the survivors move to a fresh
+// block in their old order and the table is rebuilt there.  A failure at any point leaves the store as it was.
+int store_prune(nos_voxel_map* vm, const nos::VoxelKeepRule& rule, size_t* n_removed) {
+  const size_t V = vm->n_voxels;
+  if (V == 0) {
+    if (n_removed) *n_removed = 0;
+    return NOS_OK;
+  }
+  DeviceSlot& slot = vm->ctx->slots[0];
+  hipStream_t st = slot.stream;
+  DeviceBuffers buf(&slot);
+  uint32_t *keep = nullptr, *new_slot = nullptr;
+  size_t t1 = 0;
+  void* tmp = nullptr;
+  hipError_t e = hipSetDevice(slot.device);
+  buf.reserve(V * 2 * sizeof(uint32_t) + (size_t(1) << 20));
+  if (e == hipSuccess) e = buf.alloc(&keep, V);
+  if (e == hipSuccess) e = buf.alloc(&new_slot, V);
+  if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, t1, keep, new_slot, 0u, V, rocprim::plus<uint32_t>(), st);
+  if (e == hipSuccess) e = buf.alloc_bytes(&tmp, std::max(t1, size_t(16)));
+  // removed voxels, their points (two words), valid voxels kept: words kInfoRemoved … kInfoKeptValid
+  unsigned int totals[4] = {0, 0, 0, 0};
+  static_assert(nos::kInfoKeptValid == nos::kInfoRemoved + 3 && nos::kInfoRemovedPoints == nos::kInfoRemoved + 1, "info layout");
+  if (e == hipSuccess) e = hipMemsetAsync(vm->d_info + nos::kInfoRemoved, 0, sizeof totals, st);
+  const dim3 grid(unsigned((V + 255) / 256));
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(nos::voxel_keep_kernel, grid, dim3(256), 0, st, vm->view, rule, keep, vm->d_info);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, t1, keep, new_slot, 0u, V, rocprim::plus<uint32_t>(), st);
+  if (e == hipSuccess) e = hipMemcpyAsync(totals, vm->d_info + nos::kInfoRemoved, sizeof totals, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the one wait: what goes?
+  if (e != hipSuccess) return hip_fail(e, "voxel store prune (keep)");
+  const size_t removed = totals[0];
+  if (removed == 0) {  // the common per-frame case: nothing written, nothing allocated
+    if (n_removed) *n_removed = 0;
+    return NOS_OK;
+  }
+  const unsigned long long removed_points = (unsigned long long)totals[1] | ((unsigned long long)totals[2] << 32);
+  const size_t kept = V - removed;
+  size_t capacity = vm->capacity;
+  if (kept <= vm->capacity / 4) {
+    capacity = 16;
+    while (capacity < 2 * kept) capacity *= 2;
+    capacity = std::max(capacity, vm->min_capacity);
+  }
+  void* block = nullptr;
+  size_t block_bytes = 0;
+  nos::VoxelStoreView nv{};
+  e = store_alloc(capacity, st, &block, &block_bytes, &nv);
+  if (e != hipSuccess) return hip_fail(e, "voxel store prune (new block)");
+  nv.n_voxels = uint32_t(kept);
+  unsigned int err = 0;
+  e = hipMemsetAsync(vm->d_info + nos::kInfoProbeError, 0, sizeof(unsigned int), st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(nos::voxel_compact_kernel, grid, dim3(256), 0, st, vm->view, nv, keep, new_slot, vm->d_info);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&err, vm->d_info + nos::kInfoProbeError, sizeof err, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the closing wait: the old block is freed below
+  if (e != hipSuccess || err != 0) {
+    (void)hipFree(block);
+    if (e != hipSuccess) return hip_fail(e, "voxel store prune (compact)");
+    return fail(NOS_ERR_HIP, "voxel store prune failed: the new table overflowed");
+  }
+  // the device-side valid counter follows (in stream order before any later merge)
+  e = hipMemcpyAsync(vm->d_info + nos::kInfoValid, vm->d_info + nos::kInfoKeptValid, sizeof(unsigned int),
+                     hipMemcpyDeviceToDevice, st);
+  if (e != hipSuccess) {
+    (void)hipFree(block);
+    return hip_fail(e, "voxel store prune (counter)");
+  }
+  (void)hipFree(vm->d_block);
+  vm->d_block = block;
+  vm->block_bytes = block_bytes;
+  vm->view = nv;
+  vm->capacity = capacity;
+  vm->n_voxels = uint32_t(kept);
+  vm->n_valid = totals[3];
+  vm->n_points -= removed_points;
+  ++vm->generation;
+  if (n_removed) *n_removed = removed;
   return NOS_OK;
 }
 
@@ -230,11 +327,12 @@ int nos_voxel_map_create(nos_ctx* ctx, double voxel_resolution, double search_ra
   vm->flags = flags;
   vm->capacity = 16;
   while (vm->capacity < capacity_hint) vm->capacity *= 2;
+  vm->min_capacity = vm->capacity;
   DeviceSlot& slot = ctx->slots[0];
   hipError_t e = hipSetDevice(slot.device);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&vm->d_info), nos::kInfoWords * sizeof(unsigned int));
   if (e == hipSuccess) e = hipMemsetAsync(vm->d_info, 0, nos::kInfoWords * sizeof(unsigned int), slot.stream);
-  if (e == hipSuccess) e = store_alloc(vm->capacity, slot.stream, &vm->d_block, &vm->view);
+  if (e == hipSuccess) e = store_alloc(vm->capacity, slot.stream, &vm->d_block, &vm->block_bytes, &vm->view);
   if (e == hipSuccess) e = hipStreamSynchronize(slot.stream);
   if (e != hipSuccess) {
     if (vm->d_info) (void)hipFree(vm->d_info);
@@ -269,6 +367,45 @@ int nos_voxel_map_info(const nos_voxel_map* vm, size_t* n_voxels, size_t* n_vali
   if (n_voxels) *n_voxels = vm->n_voxels;
   if (n_valid) *n_valid = vm->n_valid;
   if (n_points) *n_points = vm->n_points;
+  return NOS_OK;
+}
+
+int nos_voxel_map_prune(nos_voxel_map* vm, const nos_voxel_prune* what, size_t* n_removed) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!vm || !what) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (what->struct_size < sizeof(nos_voxel_prune)) return fail(NOS_ERR_INVALID_ARGUMENT, "struct_size is smaller than nos_voxel_prune");
+  if (what->what == 0 || (what->what & ~(NOS_PRUNE_BOX | NOS_PRUNE_AGE)))
+    return fail(NOS_ERR_INVALID_ARGUMENT, "what must be NOS_PRUNE_BOX, NOS_PRUNE_AGE or both");
+  nos::VoxelKeepRule rule{};
+  rule.use_box = (what->what & NOS_PRUNE_BOX) ? 1 : 0;
+  rule.use_age = (what->what & NOS_PRUNE_AGE) ? 1 : 0;
+  if (rule.use_box) {
+    const double inv_res = 1.0 / vm->voxel_resolution;  // what voxel_points_kernel is handed
+    const double lim = double(1 << 20);
+    for (int k = 0; k < 3; ++k) {
+      const double c = what->center[k], h = what->half_extent[k];
+      if (!std::isfinite(c) || !std::isfinite(h) || h < 0.0)
+        return fail(NOS_ERR_INVALID_ARGUMENT, "the box needs a finite center and a finite, non-negative half extent");
+      // a cell survives iff it intersects the closed box; a box beyond the addressable grid keeps nothing
+      const double lo = std::floor((c - h) * inv_res), hi = std::floor((c + h) * inv_res);
+      rule.lo[k] = int32_t(std::min(std::max(lo, -lim), lim));
+      rule.hi[k] = int32_t(std::min(std::max(hi, -lim - 1.0), lim - 1.0));
+    }
+  }
+  if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+  rule.epoch = uint32_t(vm->epoch);
+  rule.max_age = what->max_age > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(what->max_age);
+  return store_prune(vm, rule, n_removed);
+}
+
+int nos_voxel_map_memory(const nos_voxel_map* vm, size_t* capacity, size_t* bytes, unsigned long long* epoch,
+                         unsigned long long* generation) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!vm) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map is NULL");
+  if (capacity) *capacity = vm->capacity;
+  if (bytes) *bytes = vm->block_bytes + nos::kInfoWords * sizeof(unsigned int);
+  if (epoch) *epoch = vm->epoch;
+  if (generation) *generation = vm->generation;
   return NOS_OK;
 }
 

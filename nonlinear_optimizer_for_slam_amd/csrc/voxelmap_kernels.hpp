@@ -18,6 +18,11 @@
 // Slot numbers (= voxel ids, the matcher's tie-break) are a function of the sequence of batches alone: batch of first
 // appearance, then ascending cell — a missing voxel gets V_old + (its rank among the batch's misses in sorted-key order),
 // never a counter bumped with atomicAdd.
+//
+// One prune = voxel_keep_kernel (a 0/1 flag per slot by box and / or age, and the totals of what goes) → exclusive scan
+// of the flags → voxel_compact_kernel (every kept slot moves to its rank among the kept ones in a FRESH block and enters
+// that block's empty table).  Out of place, because a parallel in-place stable compaction races: a lane's destination is
+// another lane's unread source.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,7 +42,10 @@ enum VoxelInfoWord {
   kInfoProbeError = 2,  // a probe loop ran through the whole table (cannot happen at load factor <= 1/2)
   kInfoNew = 3,         // voxels the last merge created
   kInfoValid = 4,       // valid voxels in the store (kept across inserts; int)
-  kInfoWords = 8
+  kInfoRemoved = 5,     // voxels the last keep pass marked for removal
+  kInfoRemovedPoints = 6,  // their points: one 64-bit counter in words 6 and 7
+  kInfoKeptValid = 8,   // valid voxels among those the last keep pass kept
+  kInfoWords = 12
 };
 
 // The store as the kernels see it.  Arrays have room for `capacity` slots, the first n_voxels are in use; the table has
@@ -49,6 +57,7 @@ struct VoxelStoreView {
   double* mean;           // [capacity][3]
   double* sqrt_info;      // [capacity][9]
   unsigned char* valid;   // [capacity]
+  uint32_t* stamp;        // [capacity] the store's insert counter (low 32 bits) at the last insert that touched the slot
   unsigned long long* table_key;  // [table_mask + 1]
   uint32_t* table_slot;           // [table_mask + 1]
   uint32_t table_mask;
@@ -138,13 +147,15 @@ __global__ __launch_bounds__(256) void voxel_lookup_kernel(VoxelStoreView s, con
 // Step 4b.  One lane per touched voxel: a miss takes slot n_voxels + rank (rank = exclusive scan of `miss`, i.e. its
 // place among the batch's new voxels in ascending cell order) and enters the table; then count += n and
 // acc[k] = acc[k] + seg[k] with plain loads and stores (a new voxel's sums ARE the segment's: the bits of a one-shot
-// build), and the finish for this slot only.  The valid-voxel counter moves by an integer atomic per wave.
+// build), the finish for this slot only, and stamp = this insert's number.  The valid-voxel counter moves by an integer
+// atomic per wave.
 __global__ __launch_bounds__(256) void voxel_merge_kernel(VoxelStoreView s, const uint64_t* __restrict__ run_key,
                                                           const uint32_t* __restrict__ run_count,
                                                           const double* __restrict__ seg_acc /* [n_runs][9] */,
                                                           const uint32_t* __restrict__ run_slot,
                                                           const uint32_t* __restrict__ rank, uint32_t n_runs,
-                                                          MapBuildParams prm, unsigned int* __restrict__ info) {
+                                                          MapBuildParams prm, uint32_t epoch,
+                                                          unsigned int* __restrict__ info) {
   const uint32_t u = blockIdx.x * 256 + threadIdx.x;
   int delta = 0;
   if (u < n_runs) {
@@ -176,6 +187,7 @@ __global__ __launch_bounds__(256) void voxel_merge_kernel(VoxelStoreView s, cons
     for (int k = 0; k < 3; ++k) s.mean[3 * size_t(slot) + k] = mean[k];
     for (int k = 0; k < 9; ++k) s.sqrt_info[9 * size_t(slot) + k] = S[k];
     s.valid[slot] = ok;
+    s.stamp[slot] = epoch;
     delta = int(ok) - int(was_valid);
   }
 #pragma unroll
@@ -188,6 +200,84 @@ __global__ __launch_bounds__(256) void voxel_rehash_kernel(VoxelStoreView s, uns
   const uint32_t v = blockIdx.x * 256 + threadIdx.x;
   if (v >= s.n_voxels) return;
   voxel_table_insert(s, s.key[v], v, &info[kInfoProbeError]);
+}
+
+// What a prune keeps.  Box: cell c is kept iff lo[k] <= c[k] <= hi[k] on every axis (bounds computed on the host in
+// double, see nos_voxel_map_prune).  Age: kept iff epoch - stamp <= max_age, in 32-bit wrap-around arithmetic.
+struct VoxelKeepRule {
+  int32_t lo[3], hi[3];
+  uint32_t epoch, max_age;
+  int use_box, use_age;
+};
+
+__host__ __device__ __forceinline__ void unpack_cell(uint64_t key, int32_t c[3]) {
+  const int32_t bias = 1 << 20;
+  c[0] = int32_t((key >> 42) & 0x1FFFFFull) - bias;
+  c[1] = int32_t((key >> 21) & 0x1FFFFFull) - bias;
+  c[2] = int32_t(key & 0x1FFFFFull) - bias;
+}
+
+// Prune, step 1.  One lane per slot in use: keep[v] = 1 iff the voxel passes every test the rule asks for.  The totals
+// (voxels removed, their points, valid voxels kept) move by one integer atomic per wave each.  Nothing of the store is written.
+__global__ __launch_bounds__(256) void voxel_keep_kernel(VoxelStoreView s, VoxelKeepRule rule, uint32_t* __restrict__ keep,
+                                                         unsigned int* __restrict__ info) {
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+  unsigned int removed = 0, kept_valid = 0;
+  unsigned long long removed_points = 0;
+  if (v < s.n_voxels) {
+    bool ok = true;
+    if (rule.use_box) {
+      int32_t c[3];
+      unpack_cell(s.key[v], c);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) ok = ok && c[k] >= rule.lo[k] && c[k] <= rule.hi[k];
+    }
+    if (rule.use_age) ok = ok && uint32_t(rule.epoch - s.stamp[v]) <= rule.max_age;
+    keep[v] = ok ? 1u : 0u;
+    if (ok) {
+      kept_valid = s.valid[v] ? 1u : 0u;
+    } else {
+      removed = 1u;
+      removed_points = s.count[v];
+    }
+  }
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    removed += __shfl_xor(removed, o, kWave);
+    kept_valid += __shfl_xor(kept_valid, o, kWave);
+    removed_points += __shfl_xor(removed_points, o, kWave);
+  }
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    if (removed != 0) {
+      atomicAdd(&info[kInfoRemoved], removed);
+      atomicAdd(reinterpret_cast<unsigned long long*>(&info[kInfoRemovedPoints]), removed_points);
+    }
+    if (kept_valid != 0) atomicAdd(&info[kInfoKeptValid], kept_valid);
+  }
+}
+
+// Prune, step 2.  One lane per slot of the old block: a kept slot moves, with everything it holds, to
+// new_slot[v] (= its rank among the kept slots, so the order of the survivors is theirs) in the new block `d`, and its
+// key enters d's table, which starts empty.  Keys are unique, so the CAS insert of the merge is all it takes.
+__global__ __launch_bounds__(256) void voxel_compact_kernel(VoxelStoreView s, VoxelStoreView d,
+                                                            const uint32_t* __restrict__ keep,
+                                                            const uint32_t* __restrict__ new_slot,
+                                                            unsigned int* __restrict__ info) {
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= s.n_voxels || keep[v] == 0) return;
+  const uint32_t w = new_slot[v];
+  const uint64_t key = s.key[v];
+  d.key[w] = key;
+  d.count[w] = s.count[v];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) d.acc[9 * size_t(w) + k] = s.acc[9 * size_t(v) + k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) d.mean[3 * size_t(w) + k] = s.mean[3 * size_t(v) + k];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) d.sqrt_info[9 * size_t(w) + k] = s.sqrt_info[9 * size_t(v) + k];
+  d.valid[w] = s.valid[v];
+  d.stamp[w] = s.stamp[v];
+  voxel_table_insert(d, key, w, &info[kInfoProbeError]);
 }
 
 }  // namespace nos

@@ -105,13 +105,17 @@ def scan_to_map_batch(ctx, ndt_map, scans, initial_poses=None, loss=("exponentia
     return out
 
 
-def odometry(ctx, voxel_map, scans, initial_pose=None, **scan_to_map_kwargs):
+def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, max_voxel_age=None, **scan_to_map_kwargs):
     """Scan-to-map odometry over a growing map (api.VoxelMap): for each scan, snapshot the store → scan_to_map from the
     previous scan's pose → insert the scan at the pose found (VoxelMap.insert_scan, warped on the device).  The harness's
     sequence UpdateNdtMap → OptimizePose → UpdateNdtMap (MDM/tests/simple_optimization_test.cc:236-281, 474-503) with the
     map kept on the device between frames.  scans: iterable of api.Scan; scan_to_map_kwargs go to scan_to_map unchanged.
+    window_half_extent ([3] or a scalar, metres) and / or max_voxel_age (inserts): a sliding window — after each insert
+    the store is pruned (VoxelMap.prune) to the box pose.t ± window_half_extent and / or to the voxels touched within the
+    last max_voxel_age inserts; with both None nothing is pruned.
     → (list of Poses, list of per-scan round lists)."""
     pose = Pose() if initial_pose is None else Pose(initial_pose.R, initial_pose.t)
+    windowed = window_half_extent is not None or max_voxel_age is not None
     poses, all_rounds = [], []
     for scan in scans:
         ndt_map = voxel_map.snapshot()
@@ -120,6 +124,10 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, **scan_to_map_kwargs):
         finally:
             ndt_map.close()
         voxel_map.insert_scan(scan, pose.R, pose.t)
+        if windowed:
+            box = window_half_extent is not None
+            voxel_map.prune(center=pose.t if box else None, half_extent=window_half_extent if box else None,
+                            max_age=max_voxel_age)
         poses.append(Pose(pose.R, pose.t))
         all_rounds.append(rounds)
     return poses, all_rounds
