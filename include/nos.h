@@ -236,6 +236,35 @@ size_t nos_scan_size(const nos_scan* scan);
  * (MDM/tests/simple_optimization_test.cc:296-342). */
 int nos_scan_sort_by_cell(nos_scan* scan, double cell_edge);
 int nos_scan_order(const nos_scan* scan, uint32_t* order_out);
+/* Voxel-grid filter on the device: a NEW, independent scan that holds the first point of every voxel.
+ * Replaces FilterPoints of the reference's test harness (MDM/tests/simple_optimization_test.cc:206-223).
+ * Rule (exact):
+ *   cell     a point's cell is (floor(x * inv_res), floor(y * inv_res), floor(z * inv_res)) with inv_res = 1.0 / voxel_size
+ *            computed once on the host in double: one rounded multiply, then floor — the expression the map build and
+ *            the voxel map evaluate.  Points that lie exactly on a cell face (the reference's room at 0.1 m and 0.05 m)
+ *            make every other formulation (a division, a fused multiply) give another result.
+ *   kept     point i is kept iff no point with a smaller ORIGINAL index lies in the same cell.  The original index is
+ *            what nos_scan_order reports: the index in the array given to nos_scan_create (the position itself for a
+ *            scan that was never sorted nor filtered).  The kept set therefore does not depend on whether
+ *            nos_scan_sort_by_cell ran first.
+ *   identity two points share a voxel iff their three integer cells are equal.  The reference's Cantor-paired `int`
+ *            key agrees with this wherever its arithmetic does not overflow.
+ *   output   the kept points in the input's stored order: ascending index for a never-sorted scan (the reference's
+ *            push_back order), the spatial order for a cell-sorted one.  nos_scan_order(out) gives every kept point's
+ *            original index in the source array; a later nos_scan_sort_by_cell(out) composes with it as usual.  The
+ *            input scan is unchanged.
+ * The result is the same bytes from run to run and does not depend on launch geometry or on the size of the hash table
+ * the call builds (an integer minimum per cell decides, never arrival order).
+ * Cells are limited to +-2^20 per axis; single-device contexts only.  A rejected call writes nothing, *out_scan included:
+ *   NOS_ERR_INVALID_ARGUMENT  scan or out_scan is NULL; voxel_size is not a finite number > 0; a point has a non-finite
+ *                             coordinate
+ *   NOS_ERR_UNSUPPORTED       a point's cell lies outside the addressable grid; the scan has >= 2^32 - 1 points
+ *   NOS_ERR_OUT_OF_MEMORY     the temporaries (12 B per table entry, the table a power of two >= 2 n entries, plus 8 B per
+ *                             point) or the new scan do not fit; nothing stays allocated
+ * An empty scan filters to an empty scan. */
+int nos_scan_filter(nos_scan* scan, double voxel_size, nos_scan** out_scan);
+/* points_xyz_out: [nos_scan_size][3], the points in stored order (diagnostics, tests, callers that need them back) */
+int nos_scan_points(const nos_scan* scan, double* points_xyz_out);
 int nos_ndt_match(nos_ndt_map* map, nos_scan* scan, const double R[9], const double t[3],
                   int max_neighbors, int dtype, nos_dataset** out_ds, size_t* n_matches);
 /* Tail drop of the reference's solver classes for a matcher-written dataset.  The scalar 3-DoF class uses only the

@@ -842,18 +842,44 @@ class VoxelMap:
 class Scan:
     """Device-resident scan points in the sensor's local frame (nos_scan): points [n,3]."""
 
-    def __init__(self, ctx, points, sort_cell=None):
+    def __init__(self, ctx, points, sort_cell=None, filter_voxel=None):
         """sort_cell: if set, reorder the points by grid cell of that edge (nos_scan_sort_by_cell) — faster matching
-        for scans whose points do not arrive in spatial order; `order` then maps positions to input indices."""
+        for scans whose points do not arrive in spatial order; `order` then maps positions to input indices.
+        filter_voxel: if set, keep the first point of every voxel of that edge (nos_scan_filter, on the device) before
+        sorting; the raw device copy is released and `order` maps positions to indices of `points`."""
         self._ctx = ctx
         self._lib = ctx._lib
+        self._h = None
         pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
         h = ctypes.c_void_p()
         check(self._lib.nos_scan_create(ctx.handle, pts.shape[0], _dp(pts), ctypes.byref(h)), "nos_scan_create")
         self._h = h
         ctx._adopt(self)
+        if filter_voxel is not None:
+            kept = self.filtered(filter_voxel)
+            self._lib.nos_scan_destroy(self._h)
+            self._h, kept._h = kept._h, None
         if sort_cell is not None:
             self.sort_by_cell(sort_cell)
+
+    def filtered(self, voxel_size):
+        """→ a new Scan with the first point (smallest input index) of every voxel of edge voxel_size, in this scan's
+        stored order (nos_scan_filter: FilterPoints of the reference's harness, on the device).  Its `order` gives every
+        kept point's index in the array this scan was made from.  This scan is unchanged."""
+        h = ctypes.c_void_p()
+        check(self._lib.nos_scan_filter(self._h, ctypes.c_double(voxel_size), ctypes.byref(h)), "nos_scan_filter")
+        out = Scan.__new__(Scan)
+        out._ctx = self._ctx
+        out._lib = self._lib
+        out._h = h
+        self._ctx._adopt(out)
+        return out
+
+    def points(self):
+        """→ the points [n,3] in stored order (nos_scan_points; diagnostics and tests)."""
+        out = np.zeros((len(self), 3), dtype=np.float64)
+        check(self._lib.nos_scan_points(self._h, _dp(out)), "nos_scan_points")
+        return out
 
     def sort_by_cell(self, cell_edge):
         check(self._lib.nos_scan_sort_by_cell(self._h, ctypes.c_double(cell_edge)), "nos_scan_sort_by_cell")

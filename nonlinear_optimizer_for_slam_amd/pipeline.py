@@ -105,7 +105,8 @@ def scan_to_map_batch(ctx, ndt_map, scans, initial_poses=None, loss=("exponentia
     return out
 
 
-def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, max_voxel_age=None, **scan_to_map_kwargs):
+def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, max_voxel_age=None, filter_voxel_size=None,
+             insert_filtered=False, **scan_to_map_kwargs):
     """Scan-to-map odometry over a growing map (api.VoxelMap): for each scan, snapshot the store → scan_to_map from the
     previous scan's pose → insert the scan at the pose found (VoxelMap.insert_scan, warped on the device).  The harness's
     sequence UpdateNdtMap → OptimizePose → UpdateNdtMap (MDM/tests/simple_optimization_test.cc:236-281, 474-503) with the
@@ -113,17 +114,26 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
     window_half_extent ([3] or a scalar, metres) and / or max_voxel_age (inserts): a sliding window — after each insert
     the store is pruned (VoxelMap.prune) to the box pose.t ± window_half_extent and / or to the voxels touched within the
     last max_voxel_age inserts; with both None nothing is pruned.
+    filter_voxel_size: each frame's scan is voxel-filtered on the device (Scan.filtered, the harness's FilterPoints, :91)
+    and the filtered scan is registered, while the FULL scan is inserted — the harness builds its map from all points and
+    registers the filtered ones (:81, :91-92); insert_filtered=True inserts the filtered scan instead.  The filtered scan
+    is closed after the frame.  None: the scans are registered and inserted as they are.
     → (list of Poses, list of per-scan round lists)."""
     pose = Pose() if initial_pose is None else Pose(initial_pose.R, initial_pose.t)
     windowed = window_half_extent is not None or max_voxel_age is not None
     poses, all_rounds = [], []
     for scan in scans:
-        ndt_map = voxel_map.snapshot()
+        registered = scan if filter_voxel_size is None else scan.filtered(filter_voxel_size)
         try:
-            pose, rounds, _ = scan_to_map(ctx, ndt_map, scan, initial_pose=pose, **scan_to_map_kwargs)
+            ndt_map = voxel_map.snapshot()
+            try:
+                pose, rounds, _ = scan_to_map(ctx, ndt_map, registered, initial_pose=pose, **scan_to_map_kwargs)
+            finally:
+                ndt_map.close()
+            voxel_map.insert_scan(registered if insert_filtered else scan, pose.R, pose.t)
         finally:
-            ndt_map.close()
-        voxel_map.insert_scan(scan, pose.R, pose.t)
+            if registered is not scan:
+                registered.close()
         if windowed:
             box = window_half_extent is not None
             voxel_map.prune(center=pose.t if box else None, half_extent=window_half_extent if box else None,
