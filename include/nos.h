@@ -378,6 +378,26 @@ int nos_voxel_map_info(const nos_voxel_map* map, size_t* n_voxels, size_t* n_val
 int nos_voxel_map_snapshot(nos_voxel_map* map, nos_ndt_map** out_map);
 /* The per-voxel numbers in voxel-id order; read with nos_map_stats_get, free with nos_map_stats_destroy. */
 int nos_voxel_map_stats(nos_voxel_map* map, nos_map_stats** out_stats);
+/* The matcher on the LIVE store: MatchPointCloud of the reference's test harness
+ * (MDM/tests/simple_optimization_test.cc:296-342) — every scan point warped by R p + t and matched to its (up to)
+ * max_neighbors nearest valid voxel means with squared distance < search_radius_sq — without a snapshot.  Arguments and
+ * results are those of nos_ndt_match.  Contract: the returned flat dataset and *n_matches are bit for bit what
+ * nos_voxel_map_snapshot followed by nos_ndt_match returns for the same arguments, subject to the caveat below.
+ * The candidates of a point are the voxel cells its search ball touches, looked up in the key -> slot table the inserts
+ * maintain: the call sorts nothing, allocates nothing proportional to the map, launches one kernel plus the dataset's
+ * padding and waits once: its work follows the scan, not the size of the map (time not measured yet).  The dataset is independent of the
+ * store (the records are copied into it): later inserts, prunes or the store's destruction do not touch it.  The store is
+ * not modified: voxels, epoch, generation and stamps stay as they were.
+ * Caveat: a voxel is looked for in its own cell.  The cells visited per axis are floor((q - r - g) / resolution) ...
+ * floor((q + r + g) / resolution) with r = sqrt(search_radius_sq) and the guard band g = resolution / 1024, so a voxel
+ * whose stored mean lies outside its own cell by more than g may be missed where a snapshot would find it.  Rounding alone
+ * does not get there: g covers every store with (points in a voxel) x (largest |cell coordinate| + 1) <= 2^42.
+ * Rejected before anything runs, *out_ds unwritten: NOS_ERR_INVALID_ARGUMENT for a NULL argument (n_matches may be
+ * NULL), a scan of another context, an unknown dtype; NOS_ERR_UNSUPPORTED for max_neighbors outside 1-2, a multi-device
+ * context, and a search ball that spans more than 9 cells per axis, i.e. 2 r / resolution + 2 > 9 (at a resolution below
+ * r / 3.5 the snapshot's coarser grid is the better structure); NOS_ERR_HIP for a store an earlier failure left undefined. */
+int nos_voxel_map_match(nos_voxel_map* map, nos_scan* scan, const double R[9], const double t[3],
+                        int max_neighbors, int dtype, nos_dataset** out_ds, size_t* n_matches);
 /* Sliding window: removes voxels by a box around a point and / or by age, compacts the survivors on the device and
  * rebuilds the key -> slot table.  The store can shrink.
  * Keep rule (exact):

@@ -718,7 +718,8 @@ def _read_map_stats(lib, hs):
 class VoxelMap:
     """Incremental NDT voxel map (nos_voxel_map): a device-resident store that grows scan by scan — the reference's
     UpdateNdtMap used as the update it is.  insert() / insert_scan() add a batch to the voxels it falls into and
-    re-derive the statistics of those voxels only; snapshot() gives an ordinary, independent NdtMap to match against.
+    re-derive the statistics of those voxels only; snapshot() gives an ordinary, independent NdtMap to match against,
+    match() matches a scan against the store itself.
 
     Voxel ids (the order of stats(), the matcher's tie-break) follow the sequence of batches: batch of first appearance,
     then ascending cell.  proper_sqrt_information as in NdtMap.build; capacity (voxels) only avoids early growth.
@@ -762,6 +763,18 @@ class VoxelMap:
         m._h = h
         self._ctx._adopt(m)
         return m
+
+    def match(self, scan, R, t, max_neighbors=2, dtype="f64"):
+        """NdtMap.match against the store as it is now, without a snapshot (nos_voxel_map_match) → (NdtDataset with
+        2 slots per scan point, number of real matches): bit for bit what snapshot().match(...) returns, at the cost of
+        the scan alone.  The dataset is independent of the store; the store is not modified."""
+        R = _dvec(R, 9)
+        t = _dvec(t, 3)
+        h = ctypes.c_void_p()
+        n = ctypes.c_size_t()
+        check(self._lib.nos_voxel_map_match(self._h, scan._h, _dp(R), _dp(t), max_neighbors, _DTYPES[dtype],
+                                            ctypes.byref(h), ctypes.byref(n)), "nos_voxel_map_match")
+        return NdtDataset(self._ctx, h), int(n.value)
 
     def stats(self):
         """→ dict with means, sqrt_infos, valid, counts, cells in voxel-id order (the keys NdtMap.build returns)."""

@@ -158,55 +158,78 @@ __device__ __forceinline__ void find_two_nearest(const MapView& map, double qx, 
       }
 }
 
+// The local point (x, y, z) warped by `pose`.  The multiply-adds are spelled out, in the form the compiler chose for
+// match_kernel when it was written as `R0 x + R1 y + R2 z + t0`: left to the compiler, a different surrounding kernel
+// could fuse another product.  match_point and voxel_match_kernel call this; the voxel store's insert (voxel_points_kernel) spells the same form.
+__device__ __forceinline__ void warp_point(const PosePod& pose, double x, double y, double z, double& qx, double& qy,
+                                           double& qz) {
+  qx = __builtin_fma(pose.R[2], z, __builtin_fma(pose.R[0], x, pose.R[1] * y)) + pose.t[0];
+  qy = __builtin_fma(pose.R[5], z, __builtin_fma(pose.R[3], x, pose.R[4] * y)) + pose.t[1];
+  qz = __builtin_fma(pose.R[8], z, __builtin_fma(pose.R[6], x, pose.R[7] * y)) + pose.t[2];
+}
+
+// Slots 2i and 2i + 1 of the dataset for scan point i = (x, y, z): record k holds the local point, mean[best_j[k]] and
+// sqrt_info[best_j[k]] (and its triangular factor U), or all zeros when best_j[k] is 0xFFFFFFFF (or k = 1 and
+// max_neighbors = 1).  → the number of real records (0-2).  `mean` [V][3] and `sqrt_info` [V][9] are whatever arrays the
+// search indexed: the snapshot's cell-ordered copies (match_point) or the voxel store's own (voxel_match_kernel,
+// voxelmatch_kernels.hpp) — one record writer, so the two routes store the same bits for the same voxel.
+template <typename DST>
+__device__ __forceinline__ int write_match_records(const double* __restrict__ mean, const double* __restrict__ sqrt_info,
+                                                   const uint32_t (&best_j)[2], double x, double y, double z, uint64_t i,
+                                                   int max_neighbors, const TiledLayout& L, DST* __restrict__ dst) {
+  // two consecutive slots 2i, 2i+1 → one 2-wide store per field
+  const uint64_t i0 = 2 * i;
+  using V2 = DST __attribute__((ext_vector_type(2)));
+  const bool ok0 = best_j[0] != 0xFFFFFFFFu;
+  const bool ok1 = best_j[1] != 0xFFFFFFFFu && max_neighbors > 1;
+  const double pl[3] = {x, y, z};
+  auto put = [&](int plane, DST v0, DST v1) {  // slots 2i, 2i + 1 of one stored plane
+    V2 v;
+    v[0] = v0;
+    v[1] = v1;
+    *reinterpret_cast<V2*>(dst + plane_offset(L, i0, plane)) = v;
+  };
+#pragma unroll
+  for (int f = 0; f < 3; ++f) put(f, ok0 ? DST(pl[f]) : DST(0), ok1 ? DST(pl[f]) : DST(0));
+#pragma unroll
+  for (int f = 0; f < 3; ++f)
+    put(3 + f, ok0 ? DST(mean[3 * size_t(best_j[0]) + f]) : DST(0), ok1 ? DST(mean[3 * size_t(best_j[1]) + f]) : DST(0));
+  DST S0[9], S1[9], U0[6], U1[6];
+#pragma unroll
+  for (int f = 0; f < 9; ++f) {
+    S0[f] = ok0 ? DST(sqrt_info[9 * size_t(best_j[0]) + f]) : DST(0);
+    S1[f] = ok1 ? DST(sqrt_info[9 * size_t(best_j[1]) + f]) : DST(0);
+    put(ndt_stored_plane(6 + f), S0[f], S1[f]);
+  }
+  sqrt_info_to_U<DST>(S0, U0);
+  sqrt_info_to_U<DST>(S1, U1);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) put(6 + k, U0[k], U1[k]);
+  return int(ok0) + int(ok1);
+}
+
+// The number of real matches of a launch: wave sum of the per-lane counts → one atomic per wave (integer, order
+// independent).  Every lane of the block calls this (lanes without a point with found = 0).
+__device__ __forceinline__ void add_match_count(int found, unsigned long long* __restrict__ n_matches) {
+  int s = found;
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+  if ((threadIdx.x & (kWave - 1)) == 0 && s > 0) atomicAdd(n_matches, (unsigned long long)s);
+}
+
 // Scan point i (i < n_points) warped by `pose` and matched: writes slots 2i and 2i + 1 of the dataset and returns the
 // number of real matches among them (0-2).  match_kernel (one thread per point) and register_batch_kernel (the lanes of
-// one workgroup striding over a scan, assemble_register.hpp) both call this, so their records are the same bits.  The
-// warp's multiply-adds are spelled out, in the form the compiler chose for match_kernel when it was written as
-// `R0 x + R1 y + R2 z + t0`: left to the compiler, a different surrounding kernel could fuse another product.
+// one workgroup striding over a scan, assemble_register.hpp) both call this, so their records are the same bits.
 template <typename DST>
 __device__ __forceinline__ int match_point(const MapView& map, const double* __restrict__ px, const double* __restrict__ py,
                                            const double* __restrict__ pz, uint64_t i, const PosePod& pose,
                                            int max_neighbors, const TiledLayout& L, DST* __restrict__ dst) {
-  int found = 0;
-  {
-    const double x = px[i], y = py[i], z = pz[i];
-    const double qx = __builtin_fma(pose.R[2], z, __builtin_fma(pose.R[0], x, pose.R[1] * y)) + pose.t[0];
-    const double qy = __builtin_fma(pose.R[5], z, __builtin_fma(pose.R[3], x, pose.R[4] * y)) + pose.t[1];
-    const double qz = __builtin_fma(pose.R[8], z, __builtin_fma(pose.R[6], x, pose.R[7] * y)) + pose.t[2];
-    TwoNearest best;
-    find_two_nearest(map, qx, qy, qz, best);
-    const uint32_t (&best_j)[2] = best.j;
-    // two consecutive slots 2i, 2i+1 → one 2-wide store per field
-    const uint64_t i0 = 2 * i;
-    using V2 = DST __attribute__((ext_vector_type(2)));
-    const bool ok0 = best_j[0] != 0xFFFFFFFFu;
-    const bool ok1 = best_j[1] != 0xFFFFFFFFu && max_neighbors > 1;
-    found = int(ok0) + int(ok1);
-    const double pl[3] = {x, y, z};
-    auto put = [&](int plane, DST v0, DST v1) {  // slots 2i, 2i + 1 of one stored plane
-      V2 v;
-      v[0] = v0;
-      v[1] = v1;
-      *reinterpret_cast<V2*>(dst + plane_offset(L, i0, plane)) = v;
-    };
-#pragma unroll
-    for (int f = 0; f < 3; ++f) put(f, ok0 ? DST(pl[f]) : DST(0), ok1 ? DST(pl[f]) : DST(0));
-#pragma unroll
-    for (int f = 0; f < 3; ++f)
-      put(3 + f, ok0 ? DST(map.mean[3 * size_t(best_j[0]) + f]) : DST(0), ok1 ? DST(map.mean[3 * size_t(best_j[1]) + f]) : DST(0));
-    DST S0[9], S1[9], U0[6], U1[6];
-#pragma unroll
-    for (int f = 0; f < 9; ++f) {
-      S0[f] = ok0 ? DST(map.sqrt_info[9 * size_t(best_j[0]) + f]) : DST(0);
-      S1[f] = ok1 ? DST(map.sqrt_info[9 * size_t(best_j[1]) + f]) : DST(0);
-      put(ndt_stored_plane(6 + f), S0[f], S1[f]);
-    }
-    sqrt_info_to_U<DST>(S0, U0);
-    sqrt_info_to_U<DST>(S1, U1);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) put(6 + k, U0[k], U1[k]);
-  }
-  return found;
+  const double x = px[i], y = py[i], z = pz[i];
+  double qx, qy, qz;
+  warp_point(pose, x, y, z, qx, qy, qz);
+  TwoNearest best;
+  find_two_nearest(map, qx, qy, qz, best);
+  return write_match_records<DST>(map.mean, map.sqrt_info, best.j, x, y, z, i, max_neighbors, L, dst);
 }
 
 // One thread per scan point.  points: 3 planes of n doubles (local frame).
@@ -219,11 +242,7 @@ __global__ __launch_bounds__(256) void match_kernel(MapView map, const double* _
                                                     unsigned long long* __restrict__ n_matches) {
   const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
   const int found = i < n_points ? match_point<DST>(map, px, py, pz, i, pose, max_neighbors, L, dst) : 0;
-  // match count: wave sum → one atomic per wave (integer, order independent)
-  int s = found;
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
-  if ((threadIdx.x & (kWave - 1)) == 0 && s > 0) atomicAdd(n_matches, (unsigned long long)s);
+  add_match_count(found, n_matches);
 }
 
 // Clears the last n_drop NON-EMPTY records of a matcher-written NDT dataset, in slot order: what dropping the tail of

@@ -4,6 +4,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "voxelmap_kernels.hpp"
+#include "voxelmatch_kernels.hpp"
 
 using namespace nosd;
 
@@ -417,6 +418,89 @@ int nos_voxel_map_snapshot(nos_voxel_map* vm, nos_ndt_map** out_map) {
   // the matcher's tables straight from the store's device-resident statistics; the map copies what it keeps
   return map_create_device(vm->ctx, vm->n_voxels, vm->view.mean, vm->view.sqrt_info, vm->view.valid, vm->search_radius_sq,
                            out_map);
+}
+
+int nos_voxel_map_match(nos_voxel_map* vm, nos_scan* scan, const double R[9], const double t[3], int max_neighbors, int dtype,
+                        nos_dataset** out_ds, size_t* n_matches) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!vm || !scan || !R || !t || !out_ds) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (vm->ctx != scan->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map and scan belong to different contexts");
+  if (dtype != NOS_F64 && dtype != NOS_F32) return fail(NOS_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
+  if (max_neighbors < 1 || max_neighbors > 2) return fail(NOS_ERR_UNSUPPORTED, "max_neighbors must be 1 or 2");
+  nos_ctx* ctx = vm->ctx;
+  if (ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "matching against a voxel store needs a single-device context");
+  const double radius = std::sqrt(vm->search_radius_sq);
+  if (2.0 * radius / vm->voxel_resolution + 2.0 > double(nos::kVoxelMatchMaxSpan))
+    return fail(NOS_ERR_UNSUPPORTED,
+                "the search ball spans more than %d voxel cells per axis (2 r / resolution + 2 = %g): match against a snapshot",
+                nos::kVoxelMatchMaxSpan, 2.0 * radius / vm->voxel_resolution + 2.0);
+  if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+  nos_dataset* made = nullptr;
+  nos_dataset* ds = nullptr;
+  int rc = dataset_new(ctx, kKindNdt, 2 * scan->n, dtype, &made, &ds);  // *out_ds is written on success only
+  if (rc != NOS_OK) return rc;
+  Shard& sh = ds->shards[0];
+  DeviceSlot& slot = ctx->slots[0];
+  hipStream_t st = slot.stream;
+  nos::PosePod pose;
+  for (int k = 0; k < 9; ++k) pose.R[k] = R[k];
+  for (int k = 0; k < 3; ++k) pose.t[k] = t[k];
+  const nos::VoxelStoreView& v = vm->view;
+  nos::VoxelMatchView view{};
+  view.table_key = v.table_key;
+  view.table_slot = v.table_slot;
+  view.mean = v.mean;
+  view.sqrt_info = v.sqrt_info;
+  view.valid = v.valid;
+  view.table_mask = v.table_mask;
+  view.inv_res = 1.0 / vm->voxel_resolution;  // what voxel_points_kernel is handed
+  view.reach = radius + nos::kVoxelMatchGuard * vm->voxel_resolution;
+  view.radius_sq = vm->search_radius_sq;
+  unsigned long long* d_count = reinterpret_cast<unsigned long long*>(vm->d_info + nos::kInfoMatches);
+  static_assert(nos::kInfoMatches % 2 == 0 && nos::kInfoMatches + 2 <= nos::kInfoWords, "info layout");
+  long launches = 0;
+  hipError_t e = hipSetDevice(slot.device);
+  if (e == hipSuccess) e = hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st);
+  if (e == hipSuccess) e = hipMemsetAsync(vm->d_info + nos::kInfoProbeError, 0, sizeof(unsigned int), st);
+  if (e == hipSuccess && scan->n > 0) {
+    const dim3 grid(unsigned((scan->n + 255) / 256));
+    const double* px = scan->d_planes;
+    const double* py = scan->d_planes + scan->n;
+    const double* pz = scan->d_planes + 2 * scan->n;
+    if (dtype == NOS_F64) {
+      hipLaunchKernelGGL((nos::voxel_match_kernel<double>), grid, dim3(256), 0, st, view, px, py, pz, uint64_t(scan->n), pose,
+                         max_neighbors, sh.layout, static_cast<double*>(sh.data), d_count, vm->d_info + nos::kInfoProbeError);
+      slot.last_kernel = reinterpret_cast<const void*>(&nos::voxel_match_kernel<double>);
+    } else {
+      hipLaunchKernelGGL((nos::voxel_match_kernel<float>), grid, dim3(256), 0, st, view, px, py, pz, uint64_t(scan->n), pose,
+                         max_neighbors, sh.layout, static_cast<float*>(sh.data), d_count, vm->d_info + nos::kInfoProbeError);
+      slot.last_kernel = reinterpret_cast<const void*>(&nos::voxel_match_kernel<float>);
+    }
+    e = hipGetLastError();
+    ++launches;
+  }
+  if (e == hipSuccess) {
+    rc = zero_pad(dtype, nos::kNdtStored, sh.layout, sh.data, st);  // the dataset's padding (no launch when there is none)
+    if (sh.layout.n_padded > sh.layout.n) ++launches;
+  }
+  // bracket profiling (nos_ctx_profile_begin with sample_every = 0): the count is SELF-REPORTED — this function tallies the
+  // launches it issues above, so a launch added to this call must be added to `launches` as well
+  if (slot.prof_on && slot.prof_every == 0) slot.prof_launches += launches;
+  unsigned long long count = 0;
+  unsigned int probe_error = 0;
+  if (e == hipSuccess && rc == NOS_OK) e = hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && rc == NOS_OK)
+    e = hipMemcpyAsync(&probe_error, vm->d_info + nos::kInfoProbeError, sizeof probe_error, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && rc == NOS_OK) e = hipStreamSynchronize(st);  // the one wait
+  if (e != hipSuccess || rc != NOS_OK || probe_error != 0) {
+    nos_dataset_destroy(ds);
+    if (rc != NOS_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "matching against the voxel store");
+    return fail(NOS_ERR_HIP, "matching against the voxel store failed: a table probe ran through the whole table");
+  }
+  if (n_matches) *n_matches = size_t(count);
+  *out_ds = ds;
+  return NOS_OK;
 }
 
 int nos_voxel_map_stats(nos_voxel_map* vm, nos_map_stats** out_stats) {

@@ -22,8 +22,10 @@ def _quat_vec_norm(R):
 def scan_to_map(ctx, ndt_map, scan, initial_pose=None, loss=("exponential", 1.0, 1.0), options=None,
                 max_outer_iterations=10, dof=6, dtype="f64", on_solve=None, indexed=False, keep_multiple=None,
                 device_loop=True):
-    """ndt_map: api.NdtMap, scan: api.Scan.  → (Pose, list of per-round dicts, outer_iter) — outer_iter as the
-    reference prints it (index of the round that met the stopping test, or max_outer_iterations).
+    """ndt_map: api.NdtMap, or an api.VoxelMap — every round then matches against the live store (VoxelMap.match, no
+    snapshot) and gives the pose, rounds and outer_iter of scan_to_map on its snapshot(), bit for bit; scan: api.Scan.
+    → (Pose, list of per-round dicts, outer_iter) — outer_iter as the reference prints it (index of the round that met
+    the stopping test, or max_outer_iterations).
 
     indexed=True: the matcher emits voxel ids instead of 120-byte records (nos_ndt_match_indexed) and the solver runs on
     the voxel-indexed layout — 2-3x less memory traffic per LM iteration for large scans (sort the scan by cell first:
@@ -38,6 +40,9 @@ def scan_to_map(ctx, ndt_map, scan, initial_pose=None, loss=("exponential", 1.0,
     if indexed and keep_multiple:
         raise ValueError("keep_multiple (the tail drop of the reference's classes) is implemented for the flat layout only: "
                          "a voxel-indexed dataset has no per-match records to clear (nos_dataset_drop_last_matches)")
+    if indexed and isinstance(ndt_map, VoxelMap):
+        raise ValueError("indexed=True needs an NdtMap: there is no live voxel-indexed match against a VoxelMap "
+                         "(take a snapshot() first)")
     pose = Pose() if initial_pose is None else Pose(initial_pose.R, initial_pose.t)
     last = Pose(pose.R, pose.t)
     options = options or Options()
@@ -106,7 +111,7 @@ def scan_to_map_batch(ctx, ndt_map, scans, initial_poses=None, loss=("exponentia
 
 
 def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, max_voxel_age=None, filter_voxel_size=None,
-             insert_filtered=False, **scan_to_map_kwargs):
+             insert_filtered=False, live_match=False, **scan_to_map_kwargs):
     """Scan-to-map odometry over a growing map (api.VoxelMap): for each scan, snapshot the store → scan_to_map from the
     previous scan's pose → insert the scan at the pose found (VoxelMap.insert_scan, warped on the device).  The harness's
     sequence UpdateNdtMap → OptimizePose → UpdateNdtMap (MDM/tests/simple_optimization_test.cc:236-281, 474-503) with the
@@ -118,6 +123,8 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
     and the filtered scan is registered, while the FULL scan is inserted — the harness builds its map from all points and
     registers the filtered ones (:81, :91-92); insert_filtered=True inserts the filtered scan instead.  The filtered scan
     is closed after the frame.  None: the scans are registered and inserted as they are.
+    live_match=True: no snapshot is taken; every round matches against the store itself (VoxelMap.match), so no step
+    of a frame passes over the whole map.  Same poses and rounds, bit for bit.
     → (list of Poses, list of per-scan round lists)."""
     pose = Pose() if initial_pose is None else Pose(initial_pose.R, initial_pose.t)
     windowed = window_half_extent is not None or max_voxel_age is not None
@@ -125,11 +132,12 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
     for scan in scans:
         registered = scan if filter_voxel_size is None else scan.filtered(filter_voxel_size)
         try:
-            ndt_map = voxel_map.snapshot()
+            ndt_map = voxel_map if live_match else voxel_map.snapshot()
             try:
                 pose, rounds, _ = scan_to_map(ctx, ndt_map, registered, initial_pose=pose, **scan_to_map_kwargs)
             finally:
-                ndt_map.close()
+                if not live_match:
+                    ndt_map.close()
             voxel_map.insert_scan(registered if insert_filtered else scan, pose.R, pose.t)
         finally:
             if registered is not scan:
