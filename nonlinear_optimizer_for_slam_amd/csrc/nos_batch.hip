@@ -26,32 +26,6 @@ struct BatchCall {
   nos_lm_report* reports;
 };
 
-// Item parameters of one problem, filled as launch_assemble_inner fills them for the lone solve (nos_core.hip).
-template <typename T>
-void fill_params(nos::Ndt6Params<T>& P, const Request& rq, const nos_dataset*) {
-  for (int k = 0; k < 9; ++k) P.R[k] = T(rq.R[k]);
-  for (int k = 0; k < 3; ++k) P.t[k] = T(rq.t[k]);
-  fill_loss(&rq.loss, P.la, P.lb, P.lc);
-}
-template <typename T>
-void fill_params(nos::Ndt3Params<T>& P, const Request& rq, const nos_dataset*) {
-  for (int k = 0; k < 4; ++k) P.R2[k] = T(rq.R[k]);
-  for (int k = 0; k < 2; ++k) P.t2[k] = T(rq.t[k]);
-  fill_loss(&rq.loss, P.la, P.lb, P.lc);
-}
-template <typename T>
-void fill_params(nos::ReprojParams<T>& P, const Request& rq, const nos_dataset* ds) {
-  for (int k = 0; k < 9; ++k) P.R[k] = T(rq.R[k]);
-  for (int k = 0; k < 3; ++k) P.t[k] = T(rq.t[k]);
-  P.inv_fx = T(rq.intr[0]);
-  P.inv_fy = T(rq.intr[1]);
-  P.cx = T(rq.intr[2]);
-  P.cy = T(rq.intr[3]);
-  P.min_depth = T(rq.min_depth);
-  nos::set_reproj_rules(P, ds->simd_class != 0);  // per dataset: each problem follows its own simd_class
-  fill_loss(&rq.loss, P.la, P.lb, P.lc);
-}
-
 template <typename Problem, typename T>
 int launch_batch_kernel(uint32_t n_blocks, const void* d_descs, nos::BatchResult* d_results, double* d_history,
                         int history_stride, hipStream_t stream, const void** kernel_out) {
@@ -97,14 +71,7 @@ int run_batch(const BatchCall& c, const std::vector<Request>& rq, const std::vec
     d.L = ds->shards[0].layout;
     fill_params(d.P, rq[size_t(i)], ds);
     d.n_chunks = uint32_t((std::max<uint64_t>(d.L.n, 1) + kBatchBlock - 1) / kBatchBlock);
-    // what lm_solve hands lm_init_kernel
-    for (int k = 0; k < c.nR; ++k) d.init.R[k] = c.R[size_t(i) * c.nR + k];
-    for (int k = 0; k < c.nt; ++k) d.init.t[k] = c.t[size_t(i) * c.nt + k];
-    d.init.settings.max_iterations = max_it;
-    d.init.settings.gradient_tolerance = c.opt->gradient_tolerance;
-    d.init.settings.parameter_tolerance = c.opt->parameter_tolerance;
-    d.init.settings.float_schedule = (ds->simd_class != 0 && ds->kind != kKindReproj) ? 1 : 0;
-    d.init.dof = c.problem == 3 ? 3 : 6;
+    d.init = make_lm_init(ds, rq[size_t(i)], c.opt, c.R + size_t(i) * c.nR, c.nR, c.t + size_t(i) * c.nt, c.nt);  // as lm_solve
   }
 
   void* dev = nullptr;

@@ -1,152 +1,12 @@
-// nos_core.hip — contexts, flat datasets, the accumulate entry points, RCCL hook (C ABI of include/nos.h).
+// nos_core.hip — launch selection, the accumulate entry points and the device-resident LM loop (C ABI of include/nos.h).
 //
-// Owns contexts (per-device stream + workspaces), device-resident tiled-SoA datasets and the launch logic around
-// the kernels in assemble_kernels.hpp.  There is no CPU fallback: without a usable HIP device every entry point
-// fails with NOS_ERR_NO_DEVICE / NOS_ERR_HIP.
+// The launch logic around the kernels in assemble_kernels.hpp.  There is no CPU fallback: without a usable HIP device
+// every entry point fails with NOS_ERR_NO_DEVICE / NOS_ERR_HIP.
 #include "nos_internal.hpp"
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-#include <emmintrin.h>  // full-line non-temporal stores of the host-pack ingestion
-#endif
-
-#include <cxxabi.h>
 
 namespace nosd {
 
-namespace {
-thread_local std::string g_last_error;
-}
-
-int fail(int status, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_last_error = buf;
-  return status;
-}
-
-const char* last_error_text() { return g_last_error.c_str(); }
-void clear_last_error() { g_last_error.clear(); }
-
-// Directory of the shared object that provides `symbol` in this process ("" if unknown).
-static std::string dir_of_symbol(const void* symbol, std::string* file_out = nullptr) {
-  Dl_info info{};
-  if (symbol == nullptr || dladdr(symbol, &info) == 0 || info.dli_fname == nullptr) return std::string();
-  char resolved[PATH_MAX];
-  std::string file = realpath(info.dli_fname, resolved) ? std::string(resolved) : std::string(info.dli_fname);
-  if (file_out) *file_out = file;
-  const size_t slash = file.rfind('/');
-  return slash == std::string::npos ? std::string() : file.substr(0, slash);
-}
-
-// librccl is bound with dlopen on first use.  Search order: $NOS_RCCL_PATH, then the librccl that sits NEXT TO the HIP
-// runtime already mapped into the process (so runtime and collectives always come from one ROCm tree — a process that
-// imported torch first runs on torch's bundled runtime and gets torch's bundled librccl; one that did not gets the
-// system pair), then the loader's default search.
-namespace {
-void LoadRccl(RcclApi& api) {
-  std::vector<std::string> names;
-  if (const char* forced = getenv("NOS_RCCL_PATH")) names.push_back(forced);
-  const std::string hip_dir = dir_of_symbol(reinterpret_cast<const void*>(&hipGetDeviceCount));
-  if (!hip_dir.empty()) {
-    names.push_back(hip_dir + "/librccl.so.1");
-    names.push_back(hip_dir + "/librccl.so");
-  }
-  names.push_back("librccl.so.1");
-  names.push_back("librccl.so");
-  names.push_back("/opt/rocm/lib/librccl.so.1");
-  for (const std::string& n : names) {
-    api.handle = dlopen(n.c_str(), RTLD_NOW | RTLD_LOCAL);
-    if (api.handle) break;
-  }
-  if (!api.handle) return;
-  api.GetUniqueId = reinterpret_cast<decltype(api.GetUniqueId)>(dlsym(api.handle, "ncclGetUniqueId"));
-  api.CommInitRank = reinterpret_cast<decltype(api.CommInitRank)>(dlsym(api.handle, "ncclCommInitRank"));
-  api.CommDestroy = reinterpret_cast<decltype(api.CommDestroy)>(dlsym(api.handle, "ncclCommDestroy"));
-  api.AllReduce = reinterpret_cast<decltype(api.AllReduce)>(dlsym(api.handle, "ncclAllReduce"));
-  api.GetErrorString = reinterpret_cast<decltype(api.GetErrorString)>(dlsym(api.handle, "ncclGetErrorString"));
-  api.CommCount = reinterpret_cast<decltype(api.CommCount)>(dlsym(api.handle, "ncclCommCount"));
-  api.GetVersion = reinterpret_cast<decltype(api.GetVersion)>(dlsym(api.handle, "ncclGetVersion"));
-  api.ok = api.GetUniqueId && api.CommInitRank && api.CommDestroy && api.AllReduce && api.GetErrorString;
-  if (api.ok) dir_of_symbol(reinterpret_cast<const void*>(api.AllReduce), &api.path);
-}
-}  // namespace
-
-// Process-wide, bound once: two threads that each own a context may get here at the same time (std::call_once).
-RcclApi* Rccl() {
-  static RcclApi api;
-  static std::once_flag once;
-  std::call_once(once, [] { LoadRccl(api); });
-  return &api;
-}
-
-
-// Default layout by element type (-1 = this rule; NOS_TILE_LOG2 / the "tile_log2" option / nos_ctx_set_layout override it):
-//   fp64: planar planes with a skew (measured best and robust across sizes);
-//   fp32: tiles of 1024 correspondences — one kernel chunk (512 lanes x 2) is one contiguous 60 KB block of memory;
-//         measured at 10 M: planar 16-byte loads 6.37 TB/s, tiled 8-byte loads with the next chunk prefetched 6.94 TB/s
-//         (profiles/r02_tune_f32_layout.txt).
-constexpr int kDefaultTileLog2 = -1;
-constexpr int kDefaultTileLog2F32 = 10;
-
-size_t elem_size(int dtype) { return dtype == NOS_F32 ? sizeof(float) : sizeof(double); }
-
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  if (!v || !*v) return dflt;
-  return atoi(v);
-}
-
-// ------------------------------------------------------------------ layout
-
-// n_fields: stored planes.  Flat NDT (nos::kNdtStored = 21): the 12 streamed planes (p, mu, A) in the layout below, the 9
-// planes of S behind them in a region of the same shape (nos::TiledLayout) — planar with the plane skew for fp64, tiles of
-// 2^10 items whose 12 streamed fields are contiguous for fp32.
-nos::TiledLayout make_layout(size_t n, int n_fields, int tile_log2, int plane_skew) {
-  const int stored = n_fields;
-  if (n_fields == nos::kNdtStored) n_fields = nos::kNdtStreamed;
-  nos::TiledLayout L{};
-  L.n = n;
-  if (tile_log2 <= 0) {
-    // planar: pad to the largest chunk any kernel variant uses
-    const size_t pad = 4096;
-    L.n_padded = ((n + pad - 1) / pad) * pad;
-    if (L.n_padded == 0) L.n_padded = pad;
-    L.tile_stride = 0;
-    // planes are skewed against each other so that the 15 concurrent streams of a block never start at the same
-    // offset modulo a large power of two (n_padded itself often is one)
-    L.field_stride = L.n_padded + size_t(plane_skew);
-    L.tile_shift = 40;
-    L.tile_mask = 0xFFFFFFFFu;
-  } else {
-    const size_t tile = size_t(1) << tile_log2;
-    L.n_padded = ((n + tile - 1) / tile) * tile;
-    if (L.n_padded == 0) L.n_padded = tile;
-    L.tile_stride = tile * size_t(n_fields);
-    L.field_stride = tile;
-    L.tile_shift = uint32_t(tile_log2);
-    L.tile_mask = uint32_t(tile - 1);
-  }
-  if (stored == nos::kNdtStored) {
-    L.s_offset = (L.tile_stride == 0 ? L.field_stride : L.n_padded) * size_t(nos::kNdtStreamed);
-    L.s_tile_stride = L.tile_stride == 0 ? 0 : L.field_stride * size_t(nos::kNdtStored - nos::kNdtStreamed);
-  }
-  return L;
-}
-
-// planes a dataset stores (flat NDT: 21, see make_layout); ds->n_fields are the planes of the caller's view (nos.h)
-int stored_planes(const nos_dataset* ds) { return ds->kind == kKindNdt ? nos::kNdtStored : ds->n_fields; }
-
-size_t layout_elems(const nos::TiledLayout& L, int n_fields) {
-  return (L.tile_stride == 0 ? L.field_stride : L.n_padded) * size_t(n_fields);
-}
-
 // ------------------------------------------------------------------ launch variants
-
-// Number of compiled geometry variants per dtype (see the NOS_CASE tables below; index 0
-// is the default).
-constexpr int kNumVariants = 14;
 
 // Host function of the hot-path kernel the current thread launched last (launch_variant / launch_single); copied into
 // the device slot by launch_assemble_raw so that nos_ctx_last_kernel can name the instantiation that actually ran.
@@ -384,9 +244,41 @@ bool use_nontemporal(const nos_dataset* ds, const Shard& sh) {
   return sh.bytes > (size_t(192) << 20);
 }
 
+// One flat problem in one element type: its item parameters from the request, then the launch by loss.
+template <template <typename, int> class ProblemT, typename T>
+int launch_flat(const nos_dataset* ds, const Shard& sh, const Request& rq, double* partials, const nos::FusedFinal& fin,
+                hipStream_t stream, int* rows_out, const SingleBlockArgs* single) {
+  const nos_ctx* ctx = ds->ctx;
+  typename ProblemT<T, nos::kLossNone>::Params P{};
+  fill_params(P, rq, ds);
+  return launch_by_loss<ProblemT, T>(rq.loss_kind, ctx->variant, ctx->blocks_per_cu, ctx->slots[sh.slot].num_cus, sh.layout, P,
+                                     use_nontemporal(ds, sh), partials, fin, stream, rows_out, single);
+}
+
+int launch_assemble_inner(const nos_dataset* ds, const Shard& sh, const Request& rq, double* partials,
+                          const nos::FusedFinal& fin_in, hipStream_t stream, int* rows_out, const SingleBlockArgs* single) {
+  nos::FusedFinal fin = fin_in;
+  fin.write_through = ds->ctx->settings.sc1;  // "allowed"; the launcher keeps it only for the geometry it is valid for
+  if (ds->kind == kKindNdtIndexed) return launch_indexed(ds, sh, rq, partials, fin, stream, rows_out);
+  const bool f64 = ds->dtype == NOS_F64;
+  if (rq.problem == 6)
+    return f64 ? launch_flat<nos::Ndt6Problem, double>(ds, sh, rq, partials, fin, stream, rows_out, single)
+               : launch_flat<nos::Ndt6Problem, float>(ds, sh, rq, partials, fin, stream, rows_out, single);
+  if (rq.problem == 3)
+    return f64 ? launch_flat<nos::Ndt3Problem, double>(ds, sh, rq, partials, fin, stream, rows_out, single)
+               : launch_flat<nos::Ndt3Problem, float>(ds, sh, rq, partials, fin, stream, rows_out, single);
+  return f64 ? launch_flat<nos::ReprojProblem, double>(ds, sh, rq, partials, fin, stream, rows_out, single)
+             : launch_flat<nos::ReprojProblem, float>(ds, sh, rq, partials, fin, stream, rows_out, single);
+}
+
 int launch_assemble_raw(const nos_dataset* ds, const Shard& sh, const Request& rq, double* partials,
-                        const nos::FusedFinal& fin, hipStream_t stream, int* rows_out,
-                        const SingleBlockArgs* single = nullptr);
+                        const nos::FusedFinal& fin_in, hipStream_t stream, int* rows_out,
+                        const SingleBlockArgs* single = nullptr) {
+  t_last_kernel = nullptr;
+  const int rc = launch_assemble_inner(ds, sh, rq, partials, fin_in, stream, rows_out, single);
+  if (rc == NOS_OK && t_last_kernel != nullptr) ds->ctx->slots[sh.slot].last_kernel = t_last_kernel;
+  return rc;
+}
 
 // Launches the assemble kernel; with profiling on, brackets it with an event pair on the
 // same stream so its device duration can be read back later without perturbing the loop.
@@ -404,87 +296,6 @@ int launch_assemble(const nos_dataset* ds, const Shard& sh, const Request& rq, d
     slot.prof_used += 2;
   }
   return NOS_OK;
-}
-
-int launch_assemble_inner(const nos_dataset* ds, const Shard& sh, const Request& rq, double* partials,
-                          const nos::FusedFinal& fin_in, hipStream_t stream, int* rows_out, const SingleBlockArgs* single);
-
-int launch_assemble_raw(const nos_dataset* ds, const Shard& sh, const Request& rq, double* partials,
-                        const nos::FusedFinal& fin_in, hipStream_t stream, int* rows_out, const SingleBlockArgs* single) {
-  t_last_kernel = nullptr;
-  const int rc = launch_assemble_inner(ds, sh, rq, partials, fin_in, stream, rows_out, single);
-  if (rc == NOS_OK && t_last_kernel != nullptr) ds->ctx->slots[sh.slot].last_kernel = t_last_kernel;
-  return rc;
-}
-
-int launch_assemble_inner(const nos_dataset* ds, const Shard& sh, const Request& rq, double* partials,
-                          const nos::FusedFinal& fin_in, hipStream_t stream, int* rows_out, const SingleBlockArgs* single) {
-  const nos_ctx* ctx = ds->ctx;
-  nos::FusedFinal fin = fin_in;
-  fin.write_through = ctx->settings.sc1;  // "allowed"; the launcher keeps it only for the geometry it is valid for
-  if (ds->kind == kKindNdtIndexed) return launch_indexed(ds, sh, rq, partials, fin, stream, rows_out);
-  const DeviceSlot& slot = ctx->slots[sh.slot];
-  const bool nt = use_nontemporal(ds, sh);
-  const int variant = ctx->variant;
-  const int bpc = ctx->blocks_per_cu;
-  if (rq.problem == 6) {
-    if (ds->dtype == NOS_F64) {
-      nos::Ndt6Params<double> P;
-      for (int k = 0; k < 9; ++k) P.R[k] = rq.R[k];
-      for (int k = 0; k < 3; ++k) P.t[k] = rq.t[k];
-      fill_loss(&rq.loss, P.la, P.lb, P.lc);
-      return launch_by_loss<nos::Ndt6Problem, double>(rq.loss_kind, variant, bpc, slot.num_cus, sh.layout, P, nt,
-                                                      partials, fin, stream, rows_out, single);
-    }
-    nos::Ndt6Params<float> P;
-    for (int k = 0; k < 9; ++k) P.R[k] = float(rq.R[k]);
-    for (int k = 0; k < 3; ++k) P.t[k] = float(rq.t[k]);
-    fill_loss(&rq.loss, P.la, P.lb, P.lc);
-    return launch_by_loss<nos::Ndt6Problem, float>(rq.loss_kind, variant, bpc, slot.num_cus, sh.layout, P, nt,
-                                                   partials, fin, stream, rows_out, single);
-  }
-  if (rq.problem == 3) {
-    if (ds->dtype == NOS_F64) {
-      nos::Ndt3Params<double> P;
-      for (int k = 0; k < 4; ++k) P.R2[k] = rq.R[k];
-      for (int k = 0; k < 2; ++k) P.t2[k] = rq.t[k];
-      fill_loss(&rq.loss, P.la, P.lb, P.lc);
-      return launch_by_loss<nos::Ndt3Problem, double>(rq.loss_kind, variant, bpc, slot.num_cus, sh.layout, P, nt,
-                                                      partials, fin, stream, rows_out, single);
-    }
-    nos::Ndt3Params<float> P;
-    for (int k = 0; k < 4; ++k) P.R2[k] = float(rq.R[k]);
-    for (int k = 0; k < 2; ++k) P.t2[k] = float(rq.t[k]);
-    fill_loss(&rq.loss, P.la, P.lb, P.lc);
-    return launch_by_loss<nos::Ndt3Problem, float>(rq.loss_kind, variant, bpc, slot.num_cus, sh.layout, P, nt,
-                                                   partials, fin, stream, rows_out, single);
-  }
-  if (ds->dtype == NOS_F64) {
-    nos::ReprojParams<double> P;
-    for (int k = 0; k < 9; ++k) P.R[k] = rq.R[k];
-    for (int k = 0; k < 3; ++k) P.t[k] = rq.t[k];
-    P.inv_fx = rq.intr[0];
-    P.inv_fy = rq.intr[1];
-    P.cx = rq.intr[2];
-    P.cy = rq.intr[3];
-    P.min_depth = rq.min_depth;
-    nos::set_reproj_rules(P, ds->simd_class != 0);
-    fill_loss(&rq.loss, P.la, P.lb, P.lc);
-    return launch_by_loss<nos::ReprojProblem, double>(rq.loss_kind, variant, bpc, slot.num_cus, sh.layout, P, nt,
-                                                      partials, fin, stream, rows_out, single);
-  }
-  nos::ReprojParams<float> P;
-  for (int k = 0; k < 9; ++k) P.R[k] = float(rq.R[k]);
-  for (int k = 0; k < 3; ++k) P.t[k] = float(rq.t[k]);
-  P.inv_fx = float(rq.intr[0]);
-  P.inv_fy = float(rq.intr[1]);
-  P.cx = float(rq.intr[2]);
-  P.cy = float(rq.intr[3]);
-  P.min_depth = float(rq.min_depth);
-  nos::set_reproj_rules(P, ds->simd_class != 0);
-  fill_loss(&rq.loss, P.la, P.lb, P.lc);
-  return launch_by_loss<nos::ReprojProblem, float>(rq.loss_kind, variant, bpc, slot.num_cus, sh.layout, P, nt,
-                                                   partials, fin, stream, rows_out, single);
 }
 
 int launch_final(int n_out, const double* partials, int rows, double* out, hipStream_t stream) {
@@ -561,23 +372,29 @@ int check_mailbox_error(const nos_ctx* ctx, DeviceSlot& slot) {
   return NOS_OK;
 }
 
-// Spin on the host-mapped sequence word the last block stores after the result; falls back
-// to a stream synchronise if the word has not arrived after a generous bound, so a protocol
-// error can never hang the caller.
-int wait_for_sequence(DeviceSlot& slot, unsigned long long want) {
+// Spins on the host-mapped sequence word the last block stores after the result, for at most max_spins looks at it; true
+// once the word has reached `want` (with the acquire fence that makes what the launch wrote before it visible).
+bool spin_for_sequence(DeviceSlot& slot, unsigned long long want, long max_spins) {
   volatile unsigned long long* seq = reinterpret_cast<volatile unsigned long long*>(slot.h_out + kSeqSlot);
-  for (long spins = 0; *seq < want; ++spins) {
-    if (spins > 2000000) {
-      NOS_HIP_CHECK(hipSetDevice(slot.device));
-      NOS_HIP_CHECK(hipStreamSynchronize(slot.stream));
-      if (*seq < want) return fail(NOS_ERR_HIP, "fused final reduce did not publish its sequence word");
-      break;
+  for (long spins = 0; spins < max_spins; ++spins) {
+    if (*seq >= want) {
+      __atomic_thread_fence(__ATOMIC_ACQUIRE);
+      return true;
     }
 #if defined(__x86_64__)
     __builtin_ia32_pause();
 #endif
   }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  return false;
+}
+
+// Falls back to a stream synchronise if the word has not arrived after a generous bound, so a protocol
+// error can never hang the caller.
+int wait_for_sequence(DeviceSlot& slot, unsigned long long want) {
+  if (spin_for_sequence(slot, want, 2000000)) return NOS_OK;
+  NOS_HIP_CHECK(hipSetDevice(slot.device));
+  NOS_HIP_CHECK(hipStreamSynchronize(slot.stream));
+  if (!spin_for_sequence(slot, want, 1)) return fail(NOS_ERR_HIP, "fused final reduce did not publish its sequence word");
   return NOS_OK;
 }
 int wait_for_sequence(DeviceSlot& slot) { return wait_for_sequence(slot, slot.seq); }
@@ -709,87 +526,102 @@ int time_kernel(nos_dataset* ds, const Request& rq, int repeats, double* kernel_
   return NOS_OK;
 }
 
-// Device-resident Levenberg-Marquardt loop (see nos::LmDevice).  The host keeps `window` launches in flight and
-// reads one pinned log entry per finished iteration; nothing on the host sits between two consecutive kernels.
-// With an RCCL communicator every launch is followed by the all-reduce of its sums and a one-wave step kernel, so
-// all ranks advance identical states in lock-step without host synchronisation either.
-int lm_solve(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, double* R, int nR, double* t, int nt,
-             nos_lm_report* report) {
-  if (!opt) return fail(NOS_ERR_INVALID_ARGUMENT, "options pointer is NULL");
-  if (ds->shards.size() != 1)
-    return fail(NOS_ERR_UNSUPPORTED, "the device-resident loop needs a single-device context (use the host loop)");
-  if (opt->max_iterations < 0) return fail(NOS_ERR_INVALID_ARGUMENT, "max_iterations < 0");
+// ------------------------------------------------------------------ device-resident LM loop (nos_*_solve)
+
+// Host mirror of the loop state and the device's copy of it (lm_init_kernel), both from the same arguments.
+int lm_init(DeviceSlot& slot, const nos::LmInitArgs& init, nos_host::LmState* st) {
+  if (init.dof == 6)
+    nos_host::LmInit6(st, init.R, init.t, init.settings.max_iterations, init.settings.float_schedule);
+  else
+    nos_host::LmInit3(st, init.R, init.t, init.settings.max_iterations, init.settings.float_schedule);
+  hipLaunchKernelGGL(nos::lm_init_kernel, dim3(1), dim3(1), 0, slot.stream, slot.d_lm, init);
+  NOS_HIP_CHECK(hipGetLastError());
+  return NOS_OK;
+}
+
+// The loop state a pinned log entry carries (layout: assemble_loop.hpp).
+void read_log_entry(const double* e, nos_host::LmState* st) {
+  for (int k = 0; k < 9; ++k) st->R[k] = e[nos::kLogR + k];
+  for (int k = 0; k < 3; ++k) st->t[k] = e[nos::kLogT + k];
+  st->lambda = e[nos::kLogLambda];
+  st->previous_cost = e[nos::kLogPrevCost];
+  st->cost = e[nos::kLogCost];
+  st->iteration = int(e[nos::kLogIteration]);
+  st->done = int(e[nos::kLogDone]);
+  st->ok = int(e[nos::kLogOk]);
+}
+
+// Cost history of a one-launch form: the kernel wrote one cost per executed iteration into the pinned history block.
+void copy_history(const nos_lm_options* opt, const DeviceSlot& slot, int executed) {
+  if (opt->cost_history != nullptr)
+    for (int k = 0; k < executed && k < opt->max_iterations; ++k) opt->cost_history[k] = slot.h_hist[k];
+}
+
+void write_report(nos_lm_report* report, const nos_host::LmState& st, int launches, int fallback) {
+  if (!report) return;
+  report->iterations = st.iteration;
+  report->ok = st.ok;
+  report->launches = launches;
+  report->fallback = fallback;
+  report->printed_cost = st.previous_cost;
+  report->last_cost = st.cost;
+  report->final_lambda = st.lambda;
+}
+
+// Small problems: the whole loop in one workgroup and one launch (see nos::solve_single_block_kernel)
+bool single_block_eligible(const nos_dataset* ds, const nos_lm_options* opt) {
+  const nos_ctx* ctx = ds->ctx;
+  const Shard& sh = ds->shards[0];
+  const bool with_comm = ctx->comm != nullptr;
+  return ds->kind != kKindNdtIndexed && !with_comm && ctx->shm_dev == nullptr && opt->max_iterations > 0 &&
+         sh.layout.n * size_t(ds->n_fields) <= nos::kSingleBlockMaxElements && ctx->settings.lm_single != 0 &&
+         (opt->cost_history == nullptr || opt->max_iterations <= kHistCapacity);
+}
+
+int solve_single_block(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, nos_host::LmState* st) {
+  const Shard& sh = ds->shards[0];
+  DeviceSlot& slot = ds->ctx->slots[sh.slot];
+  SingleBlockArgs single{};
+  single.lm = slot.d_lm;
+  single.history = opt->cost_history ? slot.h_hist_dev : nullptr;
+  single.history_capacity = kHistCapacity;
+  single.entry = slot.h_log_dev;
+  single.seq_host = reinterpret_cast<unsigned long long*>(slot.h_out_dev + kSeqSlot);
+  single.seq = ++slot.seq;
+  int rows = 0;
+  int rc = launch_assemble_raw(ds, sh, rq, slot.partials, nos::FusedFinal{}, slot.stream, &rows, &single);
+  if (rc != NOS_OK) return rc;
+  rc = wait_for_sequence(slot, single.seq);
+  if (rc != NOS_OK) return rc;
+  const double* e = slot.h_log;
+  read_log_entry(e, st);
+  const int executed = int(e[nos::kLogExecuted]);
+  if (slot.prof_on && slot.prof_every == 0) slot.prof_launches += executed;  // bracket profiling counts passes over the data
+  copy_history(opt, slot, executed);
+  return NOS_OK;
+}
+
+// Whether this solve may try the one-launch cluster form, given its geometry (solve_cluster).
+bool cluster_eligible(const nos_dataset* ds, const nos_lm_options* opt, bool mailbox_in_launch, size_t cluster_blocks,
+                      bool resident_fits, bool stream_form, bool paused) {
+  const nos_ctx* ctx = ds->ctx;
+  const bool with_comm = ctx->comm != nullptr;
+  return ds->kind != kKindNdtIndexed && !with_comm && (ctx->shm_dev == nullptr || mailbox_in_launch) && opt->max_iterations > 0 &&
+         cluster_blocks >= 1 && (resident_fits || stream_form) && !paused &&
+         ctx->settings.lm_cluster != 0 && (opt->cost_history == nullptr || opt->max_iterations <= kHistCapacity);
+}
+
+// Mid-size problems: one chunk per workgroup, every workgroup resident, the whole loop in one launch
+// (nos::solve_cluster_kernel).  If a wait inside times out (grid not fully resident, e.g. the GPU is shared) the
+// launch gives up and lm_solve runs the loop with one launch per iteration instead.
+// *finished: the launch ran the loop to its end and *st is its result; otherwise the form was not eligible, or it gave up
+// (*fell_back = 1) and left the device state re-initialised for the launch-per-iteration loop.
+int solve_cluster(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, const nos::LmInitArgs& init,
+                  nos_host::LmState* st, bool* finished, int* fell_back) {
   nos_ctx* ctx = ds->ctx;
   const Shard& sh = ds->shards[0];
   DeviceSlot& slot = ctx->slots[sh.slot];
-  NOS_HIP_CHECK(hipSetDevice(slot.device));
-  const bool with_comm = ctx->comm != nullptr;
-  const bool step_in_launch = !with_comm && ctx->settings.lm_fused != 0;
-  int window = opt->launches_in_flight > 0 ? opt->launches_in_flight : ctx->settings.lm_window;
-  window = std::max(1, std::min(window, kLogSlots - 2));
-
-  nos::LmInitArgs init{};
-  for (int k = 0; k < nR; ++k) init.R[k] = R[k];
-  for (int k = 0; k < nt; ++k) init.t[k] = t[k];
-  init.settings.max_iterations = opt->max_iterations;
-  init.settings.gradient_tolerance = opt->gradient_tolerance;
-  init.settings.parameter_tolerance = opt->parameter_tolerance;
-  init.dof = rq.n_out == 28 ? 6 : 3;
-  init.settings.float_schedule = (ds->simd_class != 0 && ds->kind != kKindReproj) ? 1 : 0;
-  nos_host::LmState st;  // host mirror: what the log says after the last finished iteration
-  if (init.dof == 6)
-    nos_host::LmInit6(&st, init.R, init.t, opt->max_iterations, init.settings.float_schedule);
-  else
-    nos_host::LmInit3(&st, init.R, init.t, opt->max_iterations, init.settings.float_schedule);
-  hipLaunchKernelGGL(nos::lm_init_kernel, dim3(1), dim3(1), 0, slot.stream, slot.d_lm, init);
-  NOS_HIP_CHECK(hipGetLastError());
-
-  unsigned long long* seq_dev = reinterpret_cast<unsigned long long*>(slot.h_out_dev + kSeqSlot);
-  // Small problems: the whole loop in one workgroup and one launch (see nos::solve_single_block_kernel)
-  if (ds->kind != kKindNdtIndexed && !with_comm && ctx->shm_dev == nullptr && opt->max_iterations > 0 &&
-      sh.layout.n * size_t(ds->n_fields) <= nos::kSingleBlockMaxElements && ctx->settings.lm_single != 0 &&
-      (opt->cost_history == nullptr || opt->max_iterations <= kHistCapacity)) {
-    SingleBlockArgs single{};
-    single.lm = slot.d_lm;
-    single.history = opt->cost_history ? slot.h_hist_dev : nullptr;
-    single.history_capacity = kHistCapacity;
-    single.entry = slot.h_log_dev;
-    single.seq_host = seq_dev;
-    single.seq = ++slot.seq;
-    int rows = 0;
-    int rc = launch_assemble_raw(ds, sh, rq, slot.partials, nos::FusedFinal{}, slot.stream, &rows, &single);
-    if (rc != NOS_OK) return rc;
-    rc = wait_for_sequence(slot, single.seq);
-    if (rc != NOS_OK) return rc;
-    const double* e = slot.h_log;
-    for (int k = 0; k < 9; ++k) st.R[k] = e[nos::kLogR + k];
-    for (int k = 0; k < 3; ++k) st.t[k] = e[nos::kLogT + k];
-    st.lambda = e[nos::kLogLambda];
-    st.previous_cost = e[nos::kLogPrevCost];
-    st.cost = e[nos::kLogCost];
-    st.iteration = int(e[nos::kLogIteration]);
-    st.done = int(e[nos::kLogDone]);
-    st.ok = int(e[nos::kLogOk]);
-    const int executed = int(e[nos::kLogExecuted]);
-    if (slot.prof_on && slot.prof_every == 0) slot.prof_launches += executed;  // bracket profiling counts passes over the data
-    if (opt->cost_history != nullptr)
-      for (int k = 0; k < executed && k < opt->max_iterations; ++k) opt->cost_history[k] = slot.h_hist[k];
-    for (int k = 0; k < nR; ++k) R[k] = st.R[k];
-    for (int k = 0; k < nt; ++k) t[k] = st.t[k];
-    if (report) {
-      report->iterations = st.iteration;
-      report->ok = st.ok;
-      report->launches = 1;
-      report->fallback = 0;
-      report->printed_cost = st.previous_cost;
-      report->last_cost = st.cost;
-      report->final_lambda = st.lambda;
-    }
-    return NOS_OK;
-  }
-  // Mid-size problems: one chunk per workgroup, every workgroup resident, the whole loop in one launch
-  // (nos::solve_cluster_kernel).  If a wait inside times out (grid not fully resident, e.g. the GPU is shared) the
-  // launch gives up and the code below runs the loop with one launch per iteration instead.
+  *finished = false;
   // One 512-thread workgroup per CU at most (all of them must be resident at once); every lane keeps items_per_lane
   // correspondences in registers + LDS.  lm_cluster: 0 off, 1 on, 2 = only the one-item-per-lane form of round 1.
   // lm_cluster_max_blocks: rehearsals of several ranks on ONE GPU give every rank its share of the CUs (all workgroups of
@@ -800,7 +632,6 @@ int lm_solve(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, doub
   // (solve_cluster_kernel).  RCCL and the host-memory mailbox run one launch per iteration, as before.
   const bool mailbox_in_launch = ctx->shm_dev != nullptr && ctx->d_peers != nullptr && ctx->d_mail != nullptr &&
                                  ds->kind != kKindNdtIndexed;
-  int fell_back = 0;
   const size_t cluster_blocks = std::min<size_t>(max_blocks, (sh.layout.n + 511) / 512);
   const size_t items_per_lane = cluster_blocks > 0 ? (sh.layout.n + cluster_blocks * 512 - 1) / (cluster_blocks * 512) : 0;
   const size_t resident_capacity = ctx->settings.lm_cluster == 2 ? 1 : resident_items_per_lane(ds->n_fields, ds->dtype);
@@ -821,125 +652,102 @@ int lm_solve(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, doub
       slot.cluster_gave_up = false;  // try the one-launch form again
     paused = slot.cluster_gave_up;
   }
-  if (ds->kind != kKindNdtIndexed && !with_comm && (ctx->shm_dev == nullptr || mailbox_in_launch) && opt->max_iterations > 0 &&
-      cluster_blocks >= 1 && (resident_fits || stream_form) && !paused &&
-      ctx->settings.lm_cluster != 0 && (opt->cost_history == nullptr || opt->max_iterations <= kHistCapacity)) {
-    SingleBlockArgs cl{};
-    cl.cluster_blocks = int(cluster_blocks);
-    cl.items_per_lane = int(items_per_lane);
-    if (stream_form) {
-      cl.items_per_lane = 0;
-      cl.stream_chunks = int(sh.layout.n_padded / stream_chunk);
-      cl.nt = use_nontemporal(ds, sh);
-      cl.stream_lds_chunks = ctx->settings.stream_lds_chunks;
-      cl.stream_reg_rounds = ctx->settings.stream_reg_rounds;
-    }
-    cl.stage1_sc1 = ctx->settings.lm_cluster == 5;
-    cl.mail = mailbox_in_launch ? ctx->d_mail : nullptr;
-    cl.partials = slot.partials;
-    cl.ctl = slot.d_cluster;
-    cl.lm = slot.d_lm;
-    cl.history = opt->cost_history ? slot.h_hist_dev : nullptr;
-    cl.history_capacity = kHistCapacity;
-    cl.entry = slot.h_log_dev;
-    cl.seq_host = seq_dev;
-    cl.seq = ++slot.seq;
-    // arrival counters and the abort word start every launch at zero
-    NOS_HIP_CHECK(hipMemsetAsync(slot.d_cluster, 0, sizeof(nos::ClusterCtl), slot.stream));
-    if (ctx->settings.debug_cluster_abort != 0) {  // test hook (nos_ctx_set_option): the launch finds `abort` already raised and gives up
-      const unsigned int raised = 1u;
-      NOS_HIP_CHECK(hipMemcpyAsync(&slot.d_cluster->abort, &raised, sizeof raised, hipMemcpyHostToDevice, slot.stream));
-      NOS_HIP_CHECK(hipStreamSynchronize(slot.stream));
-    }
-    int rows = 0;
-    // A launch the device cannot take (the LDS grant refused: NOS_ERR_UNSUPPORTED) is replaced by the loop below; any other
-    // failure — a layout / argument error, a sticky HIP error — is the caller's to see, not a reason to run slower.
-    const int rc_launch = launch_assemble_raw(ds, sh, rq, slot.partials, nos::FusedFinal{}, slot.stream, &rows, &cl);
-    if (rc_launch != NOS_OK && rc_launch != NOS_ERR_UNSUPPORTED) return rc_launch;
-    const bool launched_ok = rc_launch == NOS_OK;
-    // spin on the sequence word; a launch that gave up never writes it
-    volatile unsigned long long* seqw = reinterpret_cast<volatile unsigned long long*>(slot.h_out + kSeqSlot);
-    bool finished = false;
-    for (long spins = 0; launched_ok && spins < 4000000; ++spins) {
-      if (*seqw >= cl.seq) {
-        finished = true;
-        break;
-      }
-#if defined(__x86_64__)
-      __builtin_ia32_pause();
-#endif
-    }
-    if (!finished) {
-      NOS_HIP_CHECK(hipStreamSynchronize(slot.stream));
-      finished = *seqw >= cl.seq;
-    }
-    if (finished) {
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-      slot.cluster_next_pause = 64;
-      const double* e = slot.h_log;
-      for (int k = 0; k < 9; ++k) st.R[k] = e[nos::kLogR + k];
-      for (int k = 0; k < 3; ++k) st.t[k] = e[nos::kLogT + k];
-      st.lambda = e[nos::kLogLambda];
-      st.previous_cost = e[nos::kLogPrevCost];
-      st.cost = e[nos::kLogCost];
-      st.iteration = int(e[nos::kLogIteration]);
-      st.done = int(e[nos::kLogDone]);
-      st.ok = int(e[nos::kLogOk]);
-      const int executed = int(e[nos::kLogExecuted]);
-#ifdef NOS_LM_TIMING
-      fprintf(stderr, "[resident-timing] %d blocks x %d items/lane (0 = streamed), %d iterations; workgroup 0, us per iteration: item math %.2f, "
-              "block reduce %.2f, drain+arrive+wait %.2f, rows->sums %.2f, LM step+barrier %.2f\n", cl.cluster_blocks,
-              cl.items_per_lane, executed, e[50] * 0.01, e[51] * 0.01, e[52] * 0.01, e[53] * 0.01, e[54] * 0.01);
-      fprintf(stderr, "[resident-timing]    inside the step, shader-clock cycles per iteration: elimination %.0f, back substitution %.0f, "
-              "lane 0 (pose update, tests, schedule) %.0f\n", e[56], e[57], e[58]);
-#endif
-      if (slot.prof_on && slot.prof_every == 0) slot.prof_launches += executed;  // bracket profiling counts passes over the data
-      if (opt->cost_history != nullptr)
-        for (int k = 0; k < executed && k < opt->max_iterations; ++k) opt->cost_history[k] = slot.h_hist[k];
-      for (int k = 0; k < nR; ++k) R[k] = st.R[k];
-      for (int k = 0; k < nt; ++k) t[k] = st.t[k];
-      if (report) {
-        report->iterations = st.iteration;
-        report->ok = st.ok;
-        report->launches = 1;
-        report->fallback = 0;
-        report->printed_cost = st.previous_cost;
-        report->last_cost = st.cost;
-        report->final_lambda = st.lambda;
-      }
-      return NOS_OK;
-    }
-    // gave up: put the shared words back in order and fall through to the launch-per-iteration loop from the start
-    // (reported as nos_lm_report::fallback).  A launch that ran and timed out means the GPU is shared: remember it for a
-    // while, so the next solves on this device do not each pay the bounded wait before falling back ("lm_cluster_retry_ms";
-    // debug_cluster_abort = 2 is the test hook that leaves this latch active).  A launch the device refused sets no latch,
-    // and the text of its refusal is dropped: the call goes on to succeed.
-    fell_back = 1;
-    if (launched_ok && ctx->settings.debug_cluster_abort != 1) {
-      if (mailbox_in_launch) {
-        slot.cluster_paused_solves = slot.cluster_next_pause;
-        slot.cluster_next_pause = std::min(slot.cluster_next_pause * 2, 65536);
-      } else {
-        slot.cluster_gave_up = true;
-        slot.cluster_gave_up_at = std::chrono::steady_clock::now();
-      }
-    }
-    if (!launched_ok) clear_last_error();
-    if (mailbox_in_launch) {
-      // every rank gives up together (a rank that cannot go on tells its peers); the exchange rounds the abandoned launch
-      // may have used are skipped on every rank, so that no later round finds their granules
-      hipLaunchKernelGGL(nos::mailbox_skip_rounds_kernel, dim3(1), dim3(1), 0, slot.stream, ctx->d_round,
-                         (unsigned long long)opt->max_iterations + 1ull);
-      NOS_HIP_CHECK(hipGetLastError());
-    }
-    NOS_HIP_CHECK(hipMemsetAsync(slot.d_cluster, 0, sizeof(nos::ClusterCtl), slot.stream));
-    hipLaunchKernelGGL(nos::lm_init_kernel, dim3(1), dim3(1), 0, slot.stream, slot.d_lm, init);
-    NOS_HIP_CHECK(hipGetLastError());
-    if (init.dof == 6)
-      nos_host::LmInit6(&st, init.R, init.t, opt->max_iterations, init.settings.float_schedule);
-    else
-      nos_host::LmInit3(&st, init.R, init.t, opt->max_iterations, init.settings.float_schedule);
+  if (!cluster_eligible(ds, opt, mailbox_in_launch, cluster_blocks, resident_fits, stream_form, paused)) return NOS_OK;
+  SingleBlockArgs cl{};
+  cl.cluster_blocks = int(cluster_blocks);
+  cl.items_per_lane = int(items_per_lane);
+  if (stream_form) {
+    cl.items_per_lane = 0;
+    cl.stream_chunks = int(sh.layout.n_padded / stream_chunk);
+    cl.nt = use_nontemporal(ds, sh);
+    cl.stream_lds_chunks = ctx->settings.stream_lds_chunks;
+    cl.stream_reg_rounds = ctx->settings.stream_reg_rounds;
   }
+  cl.stage1_sc1 = ctx->settings.lm_cluster == 5;
+  cl.mail = mailbox_in_launch ? ctx->d_mail : nullptr;
+  cl.partials = slot.partials;
+  cl.ctl = slot.d_cluster;
+  cl.lm = slot.d_lm;
+  cl.history = opt->cost_history ? slot.h_hist_dev : nullptr;
+  cl.history_capacity = kHistCapacity;
+  cl.entry = slot.h_log_dev;
+  cl.seq_host = reinterpret_cast<unsigned long long*>(slot.h_out_dev + kSeqSlot);
+  cl.seq = ++slot.seq;
+  // arrival counters and the abort word start every launch at zero
+  NOS_HIP_CHECK(hipMemsetAsync(slot.d_cluster, 0, sizeof(nos::ClusterCtl), slot.stream));
+  if (ctx->settings.debug_cluster_abort != 0) {  // test hook (nos_ctx_set_option): the launch finds `abort` already raised and gives up
+    const unsigned int raised = 1u;
+    NOS_HIP_CHECK(hipMemcpyAsync(&slot.d_cluster->abort, &raised, sizeof raised, hipMemcpyHostToDevice, slot.stream));
+    NOS_HIP_CHECK(hipStreamSynchronize(slot.stream));
+  }
+  int rows = 0;
+  // A launch the device cannot take (the LDS grant refused: NOS_ERR_UNSUPPORTED) is replaced by the launch-per-iteration
+  // loop; any other failure — a layout / argument error, a sticky HIP error — is the caller's to see, not a reason to run slower.
+  const int rc_launch = launch_assemble_raw(ds, sh, rq, slot.partials, nos::FusedFinal{}, slot.stream, &rows, &cl);
+  if (rc_launch != NOS_OK && rc_launch != NOS_ERR_UNSUPPORTED) return rc_launch;
+  const bool launched_ok = rc_launch == NOS_OK;
+  // spin on the sequence word; a launch that gave up never writes it
+  *finished = launched_ok && spin_for_sequence(slot, cl.seq, 4000000);
+  if (!*finished) {
+    NOS_HIP_CHECK(hipStreamSynchronize(slot.stream));
+    *finished = spin_for_sequence(slot, cl.seq, 1);
+  }
+  if (*finished) {
+    slot.cluster_next_pause = 64;
+    const double* e = slot.h_log;
+    read_log_entry(e, st);
+    const int executed = int(e[nos::kLogExecuted]);
+#ifdef NOS_LM_TIMING
+    fprintf(stderr, "[resident-timing] %d blocks x %d items/lane (0 = streamed), %d iterations; workgroup 0, us per iteration: item math %.2f, "
+            "block reduce %.2f, drain+arrive+wait %.2f, rows->sums %.2f, LM step+barrier %.2f\n", cl.cluster_blocks,
+            cl.items_per_lane, executed, e[50] * 0.01, e[51] * 0.01, e[52] * 0.01, e[53] * 0.01, e[54] * 0.01);
+    fprintf(stderr, "[resident-timing]    inside the step, shader-clock cycles per iteration: elimination %.0f, back substitution %.0f, "
+            "lane 0 (pose update, tests, schedule) %.0f\n", e[56], e[57], e[58]);
+#endif
+    if (slot.prof_on && slot.prof_every == 0) slot.prof_launches += executed;  // bracket profiling counts passes over the data
+    copy_history(opt, slot, executed);
+    return NOS_OK;
+  }
+  // gave up: put the shared words back in order and leave the solve to the launch-per-iteration loop from the start
+  // (reported as nos_lm_report::fallback).  A launch that ran and timed out means the GPU is shared: remember it for a
+  // while, so the next solves on this device do not each pay the bounded wait before falling back ("lm_cluster_retry_ms";
+  // debug_cluster_abort = 2 is the test hook that leaves this latch active).  A launch the device refused sets no latch,
+  // and the text of its refusal is dropped: the call goes on to succeed.
+  *fell_back = 1;
+  if (launched_ok && ctx->settings.debug_cluster_abort != 1) {
+    if (mailbox_in_launch) {
+      slot.cluster_paused_solves = slot.cluster_next_pause;
+      slot.cluster_next_pause = std::min(slot.cluster_next_pause * 2, 65536);
+    } else {
+      slot.cluster_gave_up = true;
+      slot.cluster_gave_up_at = std::chrono::steady_clock::now();
+    }
+  }
+  if (!launched_ok) clear_last_error();
+  if (mailbox_in_launch) {
+    // every rank gives up together (a rank that cannot go on tells its peers); the exchange rounds the abandoned launch
+    // may have used are skipped on every rank, so that no later round finds their granules
+    hipLaunchKernelGGL(nos::mailbox_skip_rounds_kernel, dim3(1), dim3(1), 0, slot.stream, ctx->d_round,
+                       (unsigned long long)opt->max_iterations + 1ull);
+    NOS_HIP_CHECK(hipGetLastError());
+  }
+  NOS_HIP_CHECK(hipMemsetAsync(slot.d_cluster, 0, sizeof(nos::ClusterCtl), slot.stream));
+  return lm_init(slot, init, st);
+}
+
+// Any size, any communicator: one launch per iteration.  The host keeps `window` launches in flight and reads one pinned
+// log entry per finished iteration; nothing on the host sits between two consecutive kernels.  With an RCCL communicator
+// every launch is followed by the all-reduce of its sums and a one-wave step kernel, so all ranks advance identical states
+// in lock-step without host synchronisation either.
+int solve_per_iteration(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, nos_host::LmState* st, int* launches) {
+  nos_ctx* ctx = ds->ctx;
+  const Shard& sh = ds->shards[0];
+  DeviceSlot& slot = ctx->slots[sh.slot];
+  const bool with_comm = ctx->comm != nullptr;
+  const bool step_in_launch = !with_comm && ctx->settings.lm_fused != 0;
+  int window = opt->launches_in_flight > 0 ? opt->launches_in_flight : ctx->settings.lm_window;
+  window = std::max(1, std::min(window, kLogSlots - 2));
+  unsigned long long* seq_dev = reinterpret_cast<unsigned long long*>(slot.h_out_dev + kSeqSlot);
   const unsigned long long base_seq2 = slot.seq;
   int launched = 0, completed = 0;
   auto launch_one = [&]() -> int {
@@ -980,17 +788,10 @@ int lm_solve(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, doub
     rc = wait_for_sequence(slot, base_seq2 + completed + 1);
     if (rc == NOS_OK) rc = check_mailbox_error(ctx, slot);
     if (rc != NOS_OK) break;
-    if (!st.done) {
+    if (!st->done) {
       const double* e = slot.h_log + size_t(completed % kLogSlots) * nos::kLogEntryDoubles;
       if (opt->cost_history != nullptr && completed < opt->max_iterations) opt->cost_history[completed] = e[rq.n_out - 1];
-      for (int k = 0; k < 9; ++k) st.R[k] = e[nos::kLogR + k];
-      for (int k = 0; k < 3; ++k) st.t[k] = e[nos::kLogT + k];
-      st.lambda = e[nos::kLogLambda];
-      st.previous_cost = e[nos::kLogPrevCost];
-      st.cost = e[nos::kLogCost];
-      st.iteration = int(e[nos::kLogIteration]);
-      st.done = int(e[nos::kLogDone]);
-      st.ok = int(e[nos::kLogOk]);
+      read_log_entry(e, st);
 #ifdef NOS_LM_TIMING
       // wall_clock64 ticks (10 ns): start of the finishing workgroup, its ticket, step begin, step done, log written
       fprintf(stderr, "[lm-timing] it %d: loop+ticket %.2f us, rows->sums %.2f us, step %.2f us, log %.2f us\n", completed,
@@ -1005,528 +806,52 @@ int lm_solve(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, doub
 #endif
     }
     ++completed;
-    if (!st.done && launched < opt->max_iterations) rc = launch_one();
+    if (!st->done && launched < opt->max_iterations) rc = launch_one();
   }
-  if (rc != NOS_OK) {
-    (void)hipStreamSynchronize(slot.stream);  // leave nothing in flight behind an error
-    return rc;
+  if (rc != NOS_OK) (void)hipStreamSynchronize(slot.stream);  // leave nothing in flight behind an error
+  *launches = launched;
+  return rc;
+}
+
+// Device-resident Levenberg-Marquardt loop (see nos::LmDevice) in the first form the solve is eligible for: the single
+// workgroup, the one-launch cluster (resident or streamed), one launch per iteration.
+int lm_solve(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, double* R, int nR, double* t, int nt,
+             nos_lm_report* report) {
+  if (!opt) return fail(NOS_ERR_INVALID_ARGUMENT, "options pointer is NULL");
+  if (ds->shards.size() != 1)
+    return fail(NOS_ERR_UNSUPPORTED, "the device-resident loop needs a single-device context (use the host loop)");
+  if (opt->max_iterations < 0) return fail(NOS_ERR_INVALID_ARGUMENT, "max_iterations < 0");
+  DeviceSlot& slot = ds->ctx->slots[ds->shards[0].slot];
+  NOS_HIP_CHECK(hipSetDevice(slot.device));
+  const nos::LmInitArgs init = make_lm_init(ds, rq, opt, R, nR, t, nt);
+  nos_host::LmState st;  // host mirror: what the log says after the last finished iteration
+  int rc = lm_init(slot, init, &st);
+  if (rc != NOS_OK) return rc;
+  int launches = 1, fell_back = 0;
+  if (single_block_eligible(ds, opt)) {
+    rc = solve_single_block(ds, rq, opt, &st);
+  } else {
+    bool finished = false;
+    rc = solve_cluster(ds, rq, opt, init, &st, &finished, &fell_back);
+    if (rc == NOS_OK && !finished) rc = solve_per_iteration(ds, rq, opt, &st, &launches);
   }
+  if (rc != NOS_OK) return rc;
   for (int k = 0; k < nR; ++k) R[k] = st.R[k];
   for (int k = 0; k < nt; ++k) t[k] = st.t[k];
-  if (report) {
-    report->iterations = st.iteration;
-    report->ok = st.ok;
-    report->launches = launched;
-    report->fallback = fell_back;
-    report->printed_cost = st.previous_cost;
-    report->last_cost = st.cost;
-    report->final_lambda = st.lambda;
-  }
+  write_report(report, st, launches, fell_back);
   return NOS_OK;
 }
 
-// ------------------------------------------------------------------ dataset construction
-
-// Pool limits: at most 8 parked buffers and 16 GiB per device; a parked buffer serves a request if it is large
-// enough and not more than twice (+1 MiB) the size asked for.  The caller has selected the slot's device.
-constexpr size_t kPoolMaxEntries = 8;
-constexpr size_t kPoolMaxBytes = size_t(16) << 30;
-
-int pool_alloc(DeviceSlot& slot, size_t bytes, void** ptr, size_t* capacity) {
-  if (bytes == 0) bytes = 8;
-  int best = -1;
-  for (int i = 0; i < int(slot.pool.size()); ++i) {
-    const size_t have = slot.pool[i].bytes;
-    if (have >= bytes && have <= 2 * bytes + (size_t(1) << 20) && (best < 0 || have < slot.pool[best].bytes)) best = i;
-  }
-  if (best >= 0) {
-    *ptr = slot.pool[best].ptr;
-    *capacity = slot.pool[best].bytes;
-    slot.pool_bytes -= slot.pool[best].bytes;
-    slot.pool.erase(slot.pool.begin() + best);
-    return NOS_OK;
-  }
-  hipError_t e = hipMalloc(ptr, bytes);
-  if (e == hipErrorOutOfMemory && !slot.pool.empty()) {  // give the parked buffers back and try once more
-    for (auto& pe : slot.pool) (void)hipFree(pe.ptr);
-    slot.pool.clear();
-    slot.pool_bytes = 0;
-    e = hipMalloc(ptr, bytes);
-  }
-  if (e != hipSuccess)
-    return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", bytes,
-                hipGetErrorString(e));
-  *capacity = bytes;
-  return NOS_OK;
-}
-
-void pool_release(DeviceSlot& slot, void* ptr, size_t capacity) {
-  if (!ptr) return;
-  if (!slot.pool_enabled || capacity > kPoolMaxBytes) {
-    (void)hipFree(ptr);
-    return;
-  }
-  slot.pool.push_back({ptr, capacity});
-  slot.pool_bytes += capacity;
-  while (slot.pool.size() > kPoolMaxEntries || slot.pool_bytes > kPoolMaxBytes) {  // oldest first
-    (void)hipFree(slot.pool.front().ptr);
-    slot.pool_bytes -= slot.pool.front().bytes;
-    slot.pool.erase(slot.pool.begin());
-  }
-}
-
-int dataset_tile_log2(const nos_ctx* ctx, int dtype) {
-  const int tile_log2 = ctx->tile_log2 >= 0 ? ctx->tile_log2 : ctx->settings.tile_log2;
-  return tile_log2 < 0 ? (dtype == NOS_F32 ? kDefaultTileLog2F32 : 0) : tile_log2;
-}
-
-int alloc_shards(nos_ctx* ctx, nos_dataset* ds) {
-  const int n_shards = int(ctx->slots.size());
-  const size_t n = ds->n;
-  const size_t per = (n + n_shards - 1) / size_t(n_shards);  // contiguous equal ranges
-  const int tile_log2 = dataset_tile_log2(ctx, ds->dtype);
-  if (tile_log2 != 0 && (tile_log2 < 10 || tile_log2 > 24)) return fail(NOS_ERR_INVALID_ARGUMENT, "tile_log2 out of range");
-  ds->tile = tile_log2 > 0 ? (size_t(1) << tile_log2) : 0;
-  ds->shards.resize(n_shards);
-  size_t begin = 0;
-  for (int s = 0; s < n_shards; ++s) {
-    const size_t cnt = begin < n ? std::min(per, n - begin) : 0;
-    Shard& sh = ds->shards[s];
-    sh.slot = s;
-    sh.layout = make_layout(cnt, stored_planes(ds), tile_log2, ctx->settings.plane_skew);
-    sh.bytes = layout_elems(sh.layout, stored_planes(ds)) * elem_size(ds->dtype);
-    NOS_HIP_CHECK(hipSetDevice(ctx->slots[s].device));
-    int prc = pool_alloc(ctx->slots[s], sh.bytes, &sh.data, &sh.capacity);
-    if (prc != NOS_OK) return prc;
-    sh.pooled = true;
-    sh.layout.base = sh.data;
-    begin += cnt;
-  }
-  return NOS_OK;
-}
-
-template <typename SRC>
-int retile_dispatch(const nos::PlanePtrs& src, int n_fields, const nos::TiledLayout& L, void* dst, int dtype,
-                    hipStream_t stream) {
-  if (n_fields == NOS_NDT_PLANES) {  // flat NDT: one item per thread, its U planes computed on the way
-    const dim3 grid1(unsigned((L.n_padded + 255) / 256));
-    if (dtype == NOS_F64)
-      hipLaunchKernelGGL((nos::retile_ndt_kernel<SRC, double>), grid1, dim3(256), 0, stream, src, L, static_cast<double*>(dst));
-    else
-      hipLaunchKernelGGL((nos::retile_ndt_kernel<SRC, float>), grid1, dim3(256), 0, stream, src, L, static_cast<float*>(dst));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(NOS_ERR_HIP, "retile launch failed: %s", hipGetErrorString(e));
-    return NOS_OK;
-  }
-  dim3 grid(unsigned((L.n_padded + 255) / 256), unsigned(n_fields));
-  if (dtype == NOS_F64)
-    hipLaunchKernelGGL((nos::retile_kernel<SRC, double>), grid, dim3(256), 0, stream, src, n_fields, L,
-                       static_cast<double*>(dst));
-  else
-    hipLaunchKernelGGL((nos::retile_kernel<SRC, float>), grid, dim3(256), 0, stream, src, n_fields, L,
-                       static_cast<float*>(dst));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(NOS_ERR_HIP, "retile launch failed: %s", hipGetErrorString(e));
-  return NOS_OK;
-}
-
-int dataset_new(nos_ctx* ctx, int kind, size_t n, int dtype, nos_dataset** out, nos_dataset** made) {
-  if (!ctx || !out) return fail(NOS_ERR_INVALID_ARGUMENT, "ctx / out pointer is NULL");
-  if (dtype != NOS_F64 && dtype != NOS_F32) return fail(NOS_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
-  *out = nullptr;
-  nos_dataset* ds = new (std::nothrow) nos_dataset();
-  if (!ds) return fail(NOS_ERR_OUT_OF_MEMORY, "host allocation failed");
-  ds->ctx = ctx;
-  ds->kind = kind;
-  ds->dtype = dtype;
-  ds->n_fields = (kind == kKindNdt) ? NOS_NDT_PLANES : NOS_REPROJ_PLANES;
-  ds->n = n;
-  int rc = alloc_shards(ctx, ds);
-  if (rc != NOS_OK) {
-    nos_dataset_destroy(ds);
-    return rc;
-  }
-  *made = ds;
-  return NOS_OK;
-}
-
-int create_from_host_planes(nos_ctx* ctx, int kind, size_t n, const double* const* planes, int dtype,
-                            nos_dataset** out) {
-  if (!planes) return fail(NOS_ERR_INVALID_ARGUMENT, "planes is NULL");
-  nos_dataset* ds = nullptr;
-  int rc = dataset_new(ctx, kind, n, dtype, out, &ds);
+// What the accumulate / solve / time entry points share: one call at a time per context, the request built and checked
+// (its failure is reported before anything `run` checks), then the call itself.
+template <typename Run>
+int with_request(int problem, nos_dataset* ds, const double* R, int nR, const double* t, int nt, const double* intr,
+                 double min_depth, const nos_loss* loss, Run run) {
+  CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  Request rq;
+  const int rc = build_request(problem, ds, R, nR, t, nt, intr, min_depth, loss, &rq);
   if (rc != NOS_OK) return rc;
-  for (int f = 0; f < ds->n_fields; ++f)
-    if (!planes[f] && n > 0) {
-      nos_dataset_destroy(ds);
-      return fail(NOS_ERR_INVALID_ARGUMENT, "plane %d is NULL", f);
-    }
-  size_t begin = 0;
-  for (Shard& sh : ds->shards) {
-    DeviceSlot& slot = ctx->slots[sh.slot];
-    const size_t cnt = sh.layout.n;
-    hipError_t e = hipSetDevice(slot.device);
-    void* staging = nullptr;
-    const size_t plane_bytes = cnt * sizeof(double);
-    if (e == hipSuccess && cnt > 0) e = hipMalloc(&staging, plane_bytes * ds->n_fields);
-    nos::PlanePtrs src{};
-    for (int f = 0; f < ds->n_fields && e == hipSuccess && cnt > 0; ++f) {
-      char* d = static_cast<char*>(staging) + plane_bytes * f;
-      e = hipMemcpyAsync(d, planes[f] + begin, plane_bytes, hipMemcpyHostToDevice, slot.stream);
-      src.p[f] = d;
-    }
-    if (e == hipSuccess) {
-      rc = retile_dispatch<double>(src, ds->n_fields, sh.layout, sh.data, dtype, slot.stream);
-      if (rc == NOS_OK) e = hipStreamSynchronize(slot.stream);
-    }
-    if (staging) (void)hipFree(staging);
-    if (e != hipSuccess || rc != NOS_OK) {
-      nos_dataset_destroy(ds);
-      if (rc != NOS_OK) return rc;
-      return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "dataset upload failed: %s",
-                  hipGetErrorString(e));
-    }
-    begin += cnt;
-  }
-  *out = ds;
-  return NOS_OK;
-}
-
-int create_from_device_planes(nos_ctx* ctx, int kind, size_t n, const void* const* d_planes, int src_dtype,
-                              int dtype, nos_dataset** out) {
-  if (!d_planes) return fail(NOS_ERR_INVALID_ARGUMENT, "d_planes is NULL");
-  if (!ctx || ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "from_device needs a single-device context");
-  if (src_dtype != NOS_F64 && src_dtype != NOS_F32) return fail(NOS_ERR_INVALID_ARGUMENT, "unknown src dtype");
-  nos_dataset* ds = nullptr;
-  int rc = dataset_new(ctx, kind, n, dtype, out, &ds);
-  if (rc != NOS_OK) return rc;
-  Shard& sh = ds->shards[0];
-  DeviceSlot& slot = ctx->slots[0];
-  nos::PlanePtrs src{};
-  for (int f = 0; f < ds->n_fields; ++f) {
-    if (!d_planes[f] && n > 0) {
-      nos_dataset_destroy(ds);
-      return fail(NOS_ERR_INVALID_ARGUMENT, "device plane %d is NULL", f);
-    }
-    src.p[f] = d_planes[f];
-  }
-  rc = (src_dtype == NOS_F64) ? retile_dispatch<double>(src, ds->n_fields, sh.layout, sh.data, dtype, slot.stream)
-                              : retile_dispatch<float>(src, ds->n_fields, sh.layout, sh.data, dtype, slot.stream);
-  hipError_t e = (rc == NOS_OK) ? hipStreamSynchronize(slot.stream) : hipSuccess;
-  if (rc != NOS_OK || e != hipSuccess) {
-    nos_dataset_destroy(ds);
-    if (rc != NOS_OK) return rc;
-    return fail(NOS_ERR_HIP, "retile failed: %s", hipGetErrorString(e));
-  }
-  *out = ds;
-  return NOS_OK;
-}
-
-template <typename DST>
-int unpack_launch(const unsigned char* d_rec, size_t stride, const nos::FieldOffsets& fo, int n_fields, size_t first,
-                  size_t count, const nos::TiledLayout& L, void* dst, hipStream_t stream) {
-  hipLaunchKernelGGL((nos::unpack_records_kernel<DST>), dim3(unsigned((count + 255) / 256)), dim3(256), 0, stream,
-                     d_rec, uint64_t(stride), fo, n_fields, uint64_t(first), uint64_t(count), L,
-                     static_cast<DST*>(dst));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(NOS_ERR_HIP, "unpack launch failed: %s", hipGetErrorString(e));
-  return NOS_OK;
-}
-
-template <typename DST>
-int zero_pad_launch(int n_fields, const nos::TiledLayout& L, void* dst, hipStream_t stream) {
-  const size_t pads = L.n_padded - L.n;
-  if (pads == 0) return NOS_OK;
-  hipLaunchKernelGGL((nos::zero_pad_kernel<DST>), dim3(unsigned((pads + 255) / 256)), dim3(256), 0, stream, n_fields, L,
-                     static_cast<DST*>(dst));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(NOS_ERR_HIP, "zero-pad launch failed: %s", hipGetErrorString(e));
-  return NOS_OK;
-}
-
-// AoS ingestion: records are streamed in chunks through two device staging buffers so
-// the H2D copy of chunk k+1 overlaps the unpack kernel of chunk k.
-// Host-pack ingestion (first form: AoS → pinned SoA → H2D, double buffered): T host threads gather
-// the n_fields used doubles out of every record into a pinned planar chunk (converted to the dataset's element type),
-// the chunk's planes are copied straight into their final place in the planar layout while the threads pack the next
-// chunk.  Moves 120 (60) instead of 304 bytes per NDT record over PCIe; pays when there are enough host threads, so it
-// is chosen for large inputs only (see create_from_records).  Planar planes and tiled layouts alike.
-// `pinned` is the staging image of one chunk: planar (tile_log2 = 0: field f of record j at f * chunk + j) or in the
-// dataset's tiled order (record j of the chunk at (j >> T) * n_fields * 2^T + f * 2^T + (j mod 2^T); chunks start on
-// tile boundaries), so that the image is one contiguous piece of the dataset.  [lo, lo + count) = this thread's records.
-// Flat NDT in tiles (ndt): the image has the two regions of the stored layout — [tiles][12][2^T] with p, mu in fields 0-5
-// (the A fields are computed on the device afterwards), then at 12 * chunk [tiles][9][2^T] of S — each one contiguous piece.
-// Records are taken a cache line of OUTPUT at a time (8 doubles / 16 floats per field): the line's worth of every field is
-// gathered into a small block first and leaves with full-line non-temporal stores — the staging image is written once and
-// read only by the copy engine, so the destination lines need not be fetched for ownership first (4.2 instead of 5.4 GB of
-// host memory traffic per 10 M NDT records) and 15 interleaved 8-byte store streams do not fight over the core's
-// write-combining buffers.
-template <typename T>
-void pack_range(const unsigned char* host, size_t stride, const nos::FieldOffsets& fo, int n_fields, bool ndt, size_t first,
-                size_t lo, size_t count, size_t chunk, int tile_log2, T* pinned) {
-  const size_t tile = size_t(1) << tile_log2, mask = tile - 1;
-  [[maybe_unused]] const size_t pitch = tile_log2 == 0 ? chunk : tile;
-  auto dst_of = [&](size_t j, int f) -> T* {
-    if (tile_log2 == 0) return pinned + size_t(f) * chunk + j;
-    if (ndt && f >= 6)
-      return pinned + size_t(nos::kNdtStreamed) * chunk + (j >> tile_log2) * (tile * size_t(nos::kNdtStored - nos::kNdtStreamed)) +
-             size_t(f - 6) * tile + (j & mask);
-    const size_t tile_fields = ndt ? size_t(nos::kNdtStreamed) : size_t(n_fields);
-    return pinned + (j >> tile_log2) * (tile * tile_fields) + size_t(f) * tile + (j & mask);
-  };
-  auto one = [&](size_t j) {
-    const unsigned char* rec = host + (first + j) * stride;
-    for (int f = 0; f < n_fields; ++f) {
-      double v;
-      memcpy(&v, rec + fo.off[f], sizeof v);
-      *dst_of(j, f) = T(v);
-    }
-  };
-  [[maybe_unused]] constexpr size_t kLine = 64 / sizeof(T);  // records per output cache line
-  size_t j = lo;
-  const size_t end = lo + count;
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-  if (n_fields <= 16 && (reinterpret_cast<uintptr_t>(pinned) & 63u) == 0 && pitch % kLine == 0) {
-    for (; j < end && (j % kLine) != 0; ++j) one(j);  // up to the next line boundary of the image
-    alignas(64) T block[16][kLine];
-    for (; j + kLine <= end; j += kLine) {
-      for (size_t r = 0; r < kLine; ++r) {
-        const unsigned char* rec = host + (first + j + r) * stride;
-        for (int f = 0; f < n_fields; ++f) {
-          double v;
-          memcpy(&v, rec + fo.off[f], sizeof v);
-          block[f][r] = T(v);
-        }
-      }
-      for (int f = 0; f < n_fields; ++f) {  // a line never straddles a tile: tiles are multiples of 1 024 records
-        const __m128d* src = reinterpret_cast<const __m128d*>(block[f]);
-        double* line = reinterpret_cast<double*>(dst_of(j, f));
-        _mm_stream_pd(line + 0, src[0]);
-        _mm_stream_pd(line + 2, src[1]);
-        _mm_stream_pd(line + 4, src[2]);
-        _mm_stream_pd(line + 6, src[3]);
-      }
-    }
-    _mm_sfence();  // the non-temporal stores are globally visible before this thread reports the chunk packed
-  }
-#endif
-  for (; j < end; ++j) one(j);
-}
-
-int ingest_host_pack(nos_ctx* ctx, nos_dataset* ds, Shard& sh, const unsigned char* host, size_t stride,
-                     const nos::FieldOffsets& fo, int threads) {
-  DeviceSlot& slot = ctx->slots[sh.slot];
-  const size_t cnt = sh.layout.n;
-  const size_t es = elem_size(ds->dtype);
-  const size_t chunk = size_t(256) << 10;  // records per chunk: 31 MB of fp64 planes
-  const bool ndt = ds->kind == kKindNdt;
-  const int tile_log2 = sh.layout.tile_stride == 0 ? 0 : int(sh.layout.tile_shift);  // 0 = planar planes
-  // image of one chunk: the planes as given (planar), or the stored layout's tiles (flat NDT: 21 fields, A left to the device)
-  const size_t need = chunk * size_t(ndt && tile_log2 != 0 ? nos::kNdtStored : ds->n_fields) * es;
-  hipError_t e = hipSetDevice(slot.device);
-  if (e == hipSuccess && slot.copy_stream == nullptr) e = hipStreamCreateWithFlags(&slot.copy_stream, hipStreamNonBlocking);
-  for (int b = 0; b < 2 && e == hipSuccess; ++b)
-    if (slot.pack_done[b] == nullptr) e = hipEventCreateWithFlags(&slot.pack_done[b], hipEventDisableTiming);
-  if (e == hipSuccess && slot.pack_bytes < need) {
-    for (int b = 0; b < 2; ++b) {
-      if (slot.pack_pinned[b]) (void)hipHostFree(slot.pack_pinned[b]);
-      slot.pack_pinned[b] = nullptr;
-    }
-    slot.pack_bytes = 0;
-    for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipHostMalloc(&slot.pack_pinned[b], need, hipHostMallocDefault);
-    if (e == hipSuccess) slot.pack_bytes = need;
-  }
-  // Worker threads live for the whole call; per chunk they are released by `go` (chunk number) and report through
-  // `arrived`.  The calling thread waits for the pinned buffer to be free, releases the workers, waits for them, enqueues
-  // the chunk's plane copies and moves on while those copies run.
-  const size_t n_chunks = (cnt + chunk - 1) / chunk;
-  std::atomic<long> go{-1};
-  std::atomic<int> arrived{0};
-  void* const pinned2[2] = {slot.pack_pinned[0], slot.pack_pinned[1]};
-  const int n_fields = ds->n_fields;
-  const bool f64 = ds->dtype == NOS_F64;
-  std::vector<std::thread> pool;
-  const int n_workers = (e == hipSuccess && n_chunks > 0) ? threads : 0;
-  for (int w = 0; w < n_workers; ++w) {
-    pool.emplace_back([&, w]() {
-      for (size_t c = 0; c < n_chunks; ++c) {
-        while (go.load(std::memory_order_acquire) < long(c)) std::this_thread::yield();
-        if (go.load(std::memory_order_acquire) == LONG_MAX) return;  // the caller gave up
-        const size_t first = c * chunk, count = std::min(chunk, cnt - first);
-        const size_t per = (count + size_t(n_workers) - 1) / size_t(n_workers);
-        const size_t lo = std::min(count, size_t(w) * per), hi = std::min(count, lo + per);
-        if (lo < hi) {
-          if (f64)
-            pack_range<double>(host, stride, fo, n_fields, ndt, first, lo, hi - lo, chunk, tile_log2,
-                               static_cast<double*>(pinned2[c & 1]));
-          else
-            pack_range<float>(host, stride, fo, n_fields, ndt, first, lo, hi - lo, chunk, tile_log2,
-                              static_cast<float*>(pinned2[c & 1]));
-        }
-        arrived.fetch_add(1, std::memory_order_release);
-      }
-    });
-  }
-  bool used[2] = {false, false};
-  for (size_t c = 0; c < n_chunks && e == hipSuccess; ++c) {
-    const int buf = int(c & 1);
-    const size_t first = c * chunk, count = std::min(chunk, cnt - first);
-    if (used[buf]) e = hipEventSynchronize(slot.pack_done[buf]);  // its previous copies have left the pinned buffer
-    if (e != hipSuccess) break;
-    go.store(long(c), std::memory_order_release);
-    while (arrived.load(std::memory_order_acquire) < int(c + 1) * n_workers) std::this_thread::yield();
-    if (tile_log2 == 0) {
-      for (int f = 0; f < n_fields && e == hipSuccess; ++f) {
-        char* dst = static_cast<char*>(sh.data) + nos::plane_offset(sh.layout, first, ndt ? nos::ndt_stored_plane(f) : f) * es;
-        const char* src = static_cast<const char*>(slot.pack_pinned[buf]) + size_t(f) * chunk * es;
-        e = hipMemcpyAsync(dst, src, count * es, hipMemcpyHostToDevice, slot.copy_stream);
-      }
-    } else {  // the chunk's tiles are one contiguous piece of the dataset (the pads of the last tile are zeroed below)
-      const size_t tile = size_t(1) << tile_log2;
-      const size_t tiles = (count + tile - 1) / tile;
-      char* dst = static_cast<char*>(sh.data) + (first >> tile_log2) * sh.layout.tile_stride * es;
-      e = hipMemcpyAsync(dst, slot.pack_pinned[buf], tiles * sh.layout.tile_stride * es, hipMemcpyHostToDevice, slot.copy_stream);
-      if (ndt && e == hipSuccess) {  // the S region's tiles of the chunk
-        char* dst_s = static_cast<char*>(sh.data) + (sh.layout.s_offset + (first >> tile_log2) * sh.layout.s_tile_stride) * es;
-        const char* src_s = static_cast<const char*>(slot.pack_pinned[buf]) + size_t(nos::kNdtStreamed) * chunk * es;
-        e = hipMemcpyAsync(dst_s, src_s, tiles * sh.layout.s_tile_stride * es, hipMemcpyHostToDevice, slot.copy_stream);
-      }
-    }
-    if (e == hipSuccess) e = hipEventRecord(slot.pack_done[buf], slot.copy_stream);
-    used[buf] = true;
-  }
-  go.store(LONG_MAX, std::memory_order_release);  // releases workers still waiting (error path); no-op otherwise
-  for (std::thread& th : pool) th.join();
-  if (e == hipSuccess) e = hipStreamSynchronize(slot.copy_stream);
-  if (e != hipSuccess)
-    return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "host-pack ingestion failed: %s", hipGetErrorString(e));
-  if (ndt && cnt > 0) {  // U (S = QU) from the S just copied, in the dataset's element type
-    const dim3 grid(unsigned((cnt + 255) / 256));
-    if (f64)
-      hipLaunchKernelGGL((nos::ndt_u_planes_kernel<double>), grid, dim3(256), 0, slot.stream, sh.layout,
-                         static_cast<double*>(sh.data), uint64_t(0), uint64_t(cnt));
-    else
-      hipLaunchKernelGGL((nos::ndt_u_planes_kernel<float>), grid, dim3(256), 0, slot.stream, sh.layout,
-                         static_cast<float*>(sh.data), uint64_t(0), uint64_t(cnt));
-    NOS_HIP_CHECK(hipGetLastError());
-  }
-  int rc = (ds->dtype == NOS_F64) ? zero_pad_launch<double>(stored_planes(ds), sh.layout, sh.data, slot.stream)
-                                  : zero_pad_launch<float>(stored_planes(ds), sh.layout, sh.data, slot.stream);
-  if (rc != NOS_OK) return rc;
-  NOS_HIP_CHECK(hipStreamSynchronize(slot.stream));
-  return NOS_OK;
-}
-
-int create_from_records(nos_ctx* ctx, int kind, size_t n, const void* records, size_t stride,
-                        const size_t* field_offsets, int dtype, nos_dataset** out) {
-  if ((!records && n > 0) || !field_offsets) return fail(NOS_ERR_INVALID_ARGUMENT, "records / offsets is NULL");
-  nos_dataset* ds = nullptr;
-  int rc = dataset_new(ctx, kind, n, dtype, out, &ds);
-  if (rc != NOS_OK) return rc;
-  nos::FieldOffsets fo{};
-  for (int f = 0; f < ds->n_fields; ++f) {
-    if (field_offsets[f] + sizeof(double) > stride || (field_offsets[f] % sizeof(double)) != 0) {
-      nos_dataset_destroy(ds);
-      return fail(NOS_ERR_INVALID_ARGUMENT, "field offset %d out of record / misaligned", f);
-    }
-    fo.off[f] = uint32_t(field_offsets[f]);
-  }
-  if (stride % sizeof(double) != 0) {
-    nos_dataset_destroy(ds);
-    return fail(NOS_ERR_INVALID_ARGUMENT, "record stride must be a multiple of 8");
-  }
-  const size_t chunk_records = std::max<size_t>(1, (size_t(64) << 20) / stride);
-  const unsigned char* host = static_cast<const unsigned char*>(records);
-  // Which ingestion: "unpack" ships the raw records and unpacks on the device (no host work, 304 B/record over PCIe);
-  // "pack" gathers on the host with a few threads and ships planes (120 / 60 B/record).  auto = pack for large planar
-  // inputs when the host has threads to spare (NOS_INGEST=pack|unpack forces, NOS_INGEST_THREADS sets the count).
-  const std::string mode = ctx->settings.ingest == 1 ? "pack" : (ctx->settings.ingest == 2 ? "unpack" : "auto");
-  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  int pack_threads = ctx->settings.ingest_threads > 0 ? ctx->settings.ingest_threads : int(std::min(16u, hw / 2));
-  // planar planes, or tiles that divide the 256 Ki-record chunk of the pack path (the fp32 default: 1 024-item tiles)
-  const bool packable = ds->tile == 0 || (ds->tile <= (size_t(256) << 10) && ((size_t(256) << 10) % ds->tile) == 0);
-  const bool use_pack = packable && pack_threads >= 1 &&
-                        (mode == "pack" || (mode == "auto" && n >= size_t(800000) && pack_threads >= 8));
-  size_t begin = 0;
-  for (Shard& sh : ds->shards) {
-    if (use_pack) {
-      rc = ingest_host_pack(ctx, ds, sh, host + begin * stride, stride, fo, pack_threads);
-      if (rc != NOS_OK) {
-        nos_dataset_destroy(ds);
-        return rc;
-      }
-      begin += sh.layout.n;
-      continue;
-    }
-    DeviceSlot& slot = ctx->slots[sh.slot];
-    const size_t cnt = sh.layout.n;
-    hipError_t e = hipSetDevice(slot.device);
-    // persistent per-device ingestion resources (stream, events, staging buffers sized to what this call needs)
-    const size_t want_stage = std::min(chunk_records, std::max<size_t>(cnt, 1)) * stride;
-    if (e == hipSuccess && slot.copy_stream == nullptr) e = hipStreamCreateWithFlags(&slot.copy_stream, hipStreamNonBlocking);
-    for (int b = 0; b < 2 && e == hipSuccess; ++b)
-      if (slot.ing_done[b] == nullptr) e = hipEventCreateWithFlags(&slot.ing_done[b], hipEventDisableTiming);
-    if (e == hipSuccess && slot.ing_copied == nullptr) e = hipEventCreateWithFlags(&slot.ing_copied, hipEventDisableTiming);
-    if (e == hipSuccess && slot.stage_bytes < want_stage) {
-      for (int b = 0; b < 2; ++b) {
-        if (slot.stage[b]) (void)hipFree(slot.stage[b]);
-        slot.stage[b] = nullptr;
-      }
-      slot.stage_bytes = 0;
-      const size_t grow = std::max(want_stage, size_t(4) << 20);
-      for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipMalloc(&slot.stage[b], grow);
-      if (e == hipSuccess) slot.stage_bytes = grow;
-    }
-    void** stage = slot.stage;
-    hipEvent_t* done = slot.ing_done;
-    hipStream_t copy_stream = slot.copy_stream;
-    hipEvent_t copied = slot.ing_copied;
-    int buf = 0;
-    bool used[2] = {false, false};
-    for (size_t first = 0; first < cnt && e == hipSuccess && rc == NOS_OK; first += chunk_records, buf ^= 1) {
-      const size_t count = std::min(chunk_records, cnt - first);
-      if (used[buf]) e = hipStreamWaitEvent(copy_stream, done[buf], 0);  // unpack of the previous use finished
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(stage[buf], host + (begin + first) * stride, count * stride, hipMemcpyHostToDevice,
-                           copy_stream);
-      if (e == hipSuccess) e = hipEventRecord(copied, copy_stream);
-      if (e == hipSuccess) e = hipStreamWaitEvent(slot.stream, copied, 0);
-      if (e == hipSuccess) {
-        rc = (dtype == NOS_F64)
-                 ? unpack_launch<double>(static_cast<unsigned char*>(stage[buf]), stride, fo, ds->n_fields, first, count,
-                                         sh.layout, sh.data, slot.stream)
-                 : unpack_launch<float>(static_cast<unsigned char*>(stage[buf]), stride, fo, ds->n_fields, first, count,
-                                        sh.layout, sh.data, slot.stream);
-        if (rc == NOS_OK) e = hipEventRecord(done[buf], slot.stream);
-        used[buf] = true;
-      }
-    }
-    if (e == hipSuccess && rc == NOS_OK)
-      rc = (dtype == NOS_F64) ? zero_pad_launch<double>(stored_planes(ds), sh.layout, sh.data, slot.stream)
-                              : zero_pad_launch<float>(stored_planes(ds), sh.layout, sh.data, slot.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(slot.stream);
-    if (copy_stream) (void)hipStreamSynchronize(copy_stream);
-    if (e != hipSuccess || rc != NOS_OK) {
-      nos_dataset_destroy(ds);
-      if (rc != NOS_OK) return rc;
-      return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "record ingestion failed: %s",
-                  hipGetErrorString(e));
-    }
-    begin += cnt;
-  }
-  *out = ds;
-  return NOS_OK;
-}
-
-
-int zero_pad(int dtype, int n_fields, const nos::TiledLayout& L, void* dst, hipStream_t stream) {
-  return dtype == NOS_F64 ? zero_pad_launch<double>(n_fields, L, dst, stream) : zero_pad_launch<float>(n_fields, L, dst, stream);
-}
-
-int unpack_records(int dtype, const unsigned char* d_rec, size_t stride, const nos::FieldOffsets& fo, int n_fields,
-                   size_t first, size_t count, const nos::TiledLayout& L, void* dst, hipStream_t stream) {
-  return dtype == NOS_F64 ? unpack_launch<double>(d_rec, stride, fo, n_fields, first, count, L, dst, stream)
-                          : unpack_launch<float>(d_rec, stride, fo, n_fields, first, count, L, dst, stream);
+  return run(rq);
 }
 
 }  // namespace nosd
@@ -1537,530 +862,83 @@ using namespace nosd;
 
 extern "C" {
 
-namespace {
-// defined next to the option table: a knob read from the environment outside its range goes back to its default
-void drop_out_of_range_settings(nosd::Settings& st);
-}  // namespace
-
-int nos_ctx_create(const int* device_ids, int n_devices, nos_ctx** out_ctx) {
-  if (!out_ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "out_ctx is NULL");
-  *out_ctx = nullptr;
-  if (n_devices < 1 || n_devices > 64 || !device_ids) return fail(NOS_ERR_INVALID_ARGUMENT, "bad device list");
-  int count = 0;
-  hipError_t e = hipGetDeviceCount(&count);
-  if (e != hipSuccess || count < 1)
-    return fail(NOS_ERR_NO_DEVICE, "no usable HIP device (%s); this library has no CPU fallback",
-                e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
-  for (int i = 0; i < n_devices; ++i)
-    if (device_ids[i] < 0 || device_ids[i] >= count)
-      return fail(NOS_ERR_INVALID_ARGUMENT, "device id %d out of range [0,%d)", device_ids[i], count);
-  nos_ctx* ctx = new (std::nothrow) nos_ctx();
-  if (!ctx) return fail(NOS_ERR_OUT_OF_MEMORY, "host allocation failed");
-  ctx->slots.resize(n_devices);
-  ctx->blocks_per_cu = env_int("NOS_BLOCKS_PER_CU", 0);
-  ctx->variant = env_int("NOS_VARIANT", 0);
-  {  // the only place the experiment knobs are read from the environment
-    Settings& st = ctx->settings;
-    st.plane_skew = env_int("NOS_PLANE_SKEW", st.plane_skew);
-    st.sc1 = env_int("NOS_SC1", st.sc1);
-    st.nt = env_int("NOS_NT", st.nt);
-    st.fused = env_int("NOS_FUSED", st.fused);
-    st.lm_fused = env_int("NOS_LM_FUSED", st.lm_fused);
-    st.lm_window = env_int("NOS_LM_WINDOW", st.lm_window);
-    st.lm_single = env_int("NOS_LM_SINGLE", st.lm_single);
-    st.lm_cluster = env_int("NOS_LM_CLUSTER", st.lm_cluster);
-    st.lm_cluster_max_blocks = env_int("NOS_LM_CLUSTER_MAX_BLOCKS", st.lm_cluster_max_blocks);
-    st.stream_lds_chunks = env_int("NOS_STREAM_LDS_CHUNKS", st.stream_lds_chunks);
-    st.stream_reg_rounds = env_int("NOS_STREAM_REG_ROUNDS", st.stream_reg_rounds);
-    st.batch_max_elements = env_int("NOS_BATCH_MAX_ELEMENTS", st.batch_max_elements);
-    st.pool = env_int("NOS_POOL", st.pool);
-    st.tile_log2 = env_int("NOS_TILE_LOG2", int(kDefaultTileLog2));
-    const char* ingest = getenv("NOS_INGEST");
-    st.ingest = (ingest && !strcmp(ingest, "pack")) ? 1 : ((ingest && !strcmp(ingest, "unpack")) ? 2 : 0);
-    st.ingest_threads = env_int("NOS_INGEST_THREADS", 0);
-    st.indexed_bpc = env_int("NOS_INDEXED_BPC", st.indexed_bpc);
-    st.match_dense = env_int("NOS_MATCH_DENSE", st.match_dense);
-    st.map_compact_keys = env_int("NOS_MAP_COMPACT_KEYS", st.map_compact_keys);
-    st.pgo_host_scalars = env_int("NOS_PGO_HOST_SCALARS", st.pgo_host_scalars);
-    st.pgo_precond = env_int("NOS_PGO_PRECOND", st.pgo_precond);
-    st.pgo_agg = env_int("NOS_PGO_AGG", st.pgo_agg);
-    st.pgo_block = env_int("NOS_PGO_BLOCK", st.pgo_block);
-    st.pgo_coarse_probe = env_int("NOS_PGO_COARSE_PROBE", st.pgo_coarse_probe);
-    drop_out_of_range_settings(st);  // the same ranges nos_ctx_set_option enforces
-  }
-  for (int i = 0; i < n_devices; ++i) {
-    DeviceSlot& s = ctx->slots[i];
-    s.device = device_ids[i];
-    s.pool_enabled = ctx->settings.pool != 0;
-    hipDeviceProp_t prop;
-    e = hipSetDevice(s.device);
-    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, s.device);
-    if (e == hipSuccess) {
-      s.num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-      e = hipStreamCreateWithFlags(&s.own_stream, hipStreamNonBlocking);
-    }
-    if (e == hipSuccess) e = hipMalloc(&s.partials, sizeof(double) * kMaxPartialRows * kMaxOut);
-    if (e == hipSuccess) e = hipMalloc(&s.d_out, sizeof(double) * kMaxOut);
-    if (e == hipSuccess) e = hipHostMalloc(&s.h_out, sizeof(double) * 64, hipHostMallocMapped);
-    if (e == hipSuccess) memset(s.h_out, 0, sizeof(double) * 64);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&s.h_out_dev), s.h_out, 0);
-    if (e == hipSuccess) e = hipMalloc(&s.d_lm, sizeof(nos::LmDevice));
-    const size_t log_bytes = sizeof(double) * kLogSlots * nos::kLogEntryDoubles;
-    if (e == hipSuccess) e = hipHostMalloc(&s.h_log, log_bytes, hipHostMallocMapped);
-    if (e == hipSuccess) memset(s.h_log, 0, log_bytes);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&s.h_log_dev), s.h_log, 0);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s.d_cluster), sizeof(nos::ClusterCtl));
-    if (e == hipSuccess) e = hipMemset(s.d_cluster, 0, sizeof(nos::ClusterCtl));
-    if (e == hipSuccess) e = hipHostMalloc(&s.h_hist, sizeof(double) * kHistCapacity, hipHostMallocMapped);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&s.h_hist_dev), s.h_hist, 0);
-    if (e == hipSuccess) e = hipMalloc(&s.counter, 2048);  // top ticket + 8 group tickets, 128 bytes apart
-    if (e == hipSuccess) e = hipMemset(s.counter, 0, 2048);
-    if (e == hipSuccess) e = hipEventCreate(&s.ev0);
-    if (e == hipSuccess) e = hipEventCreate(&s.ev1);
-    if (e == hipSuccess) e = hipEventCreate(&s.ev2);
-    s.stream = s.own_stream;
-    if (e != hipSuccess) {
-      nos_ctx_destroy(ctx);
-      return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "context setup failed on device %d: %s",
-                  device_ids[i], hipGetErrorString(e));
-    }
-  }
-  *out_ctx = ctx;
-  return NOS_OK;
-}
-
-int nos_ctx_comm_destroy(nos_ctx* ctx) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  if (ctx)
-    for (DeviceSlot& sl : ctx->slots) sl.cluster_paused_solves = 0, sl.cluster_next_pause = 64;  // a new communicator starts with every rank unpaused
-  if (!ctx) return NOS_OK;
-  if (ctx->comm != nullptr) {
-    if (!ctx->slots.empty()) {
-      (void)hipSetDevice(ctx->slots[0].device);
-      (void)hipStreamSynchronize(ctx->slots[0].stream);
-    }
-    (void)Rccl()->CommDestroy(ctx->comm);
-    ctx->comm = nullptr;
-  }
-  if (ctx->shm_host != nullptr) {
-    if (!ctx->slots.empty()) {
-      (void)hipSetDevice(ctx->slots[0].device);
-      (void)hipStreamSynchronize(ctx->slots[0].stream);
-    }
-    for (size_t k = 0; k < ctx->ipc_peers.size(); ++k)
-      if (ctx->ipc_peers[k] != nullptr && int(k) != ctx->comm_rank) (void)hipIpcCloseMemHandle(ctx->ipc_peers[k]);
-    ctx->ipc_peers.clear();
-    if (ctx->ipc_own) (void)hipFree(ctx->ipc_own);
-    if (ctx->d_peers) (void)hipFree(ctx->d_peers);
-    ctx->ipc_own = nullptr;
-    ctx->d_peers = nullptr;
-    (void)hipHostUnregister(ctx->shm_host);
-    munmap(ctx->shm_host, ctx->shm_bytes);
-    if (ctx->d_round) (void)hipFree(ctx->d_round);
-    if (ctx->d_mail) (void)hipFree(ctx->d_mail);
-    ctx->shm_host = nullptr;
-    ctx->shm_dev = nullptr;
-    ctx->d_round = nullptr;
-    ctx->d_mail = nullptr;
-  }
-  ctx->comm_ranks = 1;
-  ctx->comm_rank = 0;
-  return NOS_OK;
-}
-
-int nos_ctx_destroy(nos_ctx* ctx) {
-  if (!ctx) return NOS_OK;
-  (void)nos_ctx_comm_destroy(ctx);
-  for (DeviceSlot& s : ctx->slots) {
-    (void)hipSetDevice(s.device);
-    if (s.own_stream) {
-      (void)hipStreamSynchronize(s.own_stream);
-      (void)hipStreamDestroy(s.own_stream);
-    }
-    if (s.partials) (void)hipFree(s.partials);
-    if (s.d_out) (void)hipFree(s.d_out);
-    if (s.h_out) (void)hipHostFree(s.h_out);
-    if (s.counter) (void)hipFree(s.counter);
-    if (s.d_lm) (void)hipFree(s.d_lm);
-    if (s.copy_stream) {
-      (void)hipStreamSynchronize(s.copy_stream);
-      (void)hipStreamDestroy(s.copy_stream);
-    }
-    for (int b = 0; b < 2; ++b) {
-      if (s.stage[b]) (void)hipFree(s.stage[b]);
-      if (s.ing_done[b]) (void)hipEventDestroy(s.ing_done[b]);
-    }
-    if (s.ing_copied) (void)hipEventDestroy(s.ing_copied);
-    for (int b = 0; b < 2; ++b) {
-      if (s.pack_pinned[b]) (void)hipHostFree(s.pack_pinned[b]);
-      if (s.pack_done[b]) (void)hipEventDestroy(s.pack_done[b]);
-    }
-    if (s.batch_pinned) (void)hipHostFree(s.batch_pinned);
-    for (auto& pe : s.pool) (void)hipFree(pe.ptr);
-    s.pool.clear();
-    if (s.h_log) (void)hipHostFree(s.h_log);
-    if (s.h_hist) (void)hipHostFree(s.h_hist);
-    if (s.d_cluster) (void)hipFree(s.d_cluster);
-    if (s.ev0) (void)hipEventDestroy(s.ev0);
-    if (s.ev1) (void)hipEventDestroy(s.ev1);
-    if (s.ev2) (void)hipEventDestroy(s.ev2);
-    for (hipEvent_t e : s.prof_events) (void)hipEventDestroy(e);
-  }
-  delete ctx;
-  return NOS_OK;
-}
-
-int nos_ctx_num_devices(const nos_ctx* ctx) { return ctx ? int(ctx->slots.size()) : 0; }
-
-int nos_ctx_set_stream(nos_ctx* ctx, int shard, void* hip_stream) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  if (!ctx || shard < 0 || shard >= int(ctx->slots.size())) return fail(NOS_ERR_INVALID_ARGUMENT, "bad ctx / shard");
-  ctx->slots[shard].stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->slots[shard].own_stream;
-  return NOS_OK;
-}
-
-int nos_ctx_synchronize(nos_ctx* ctx) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  if (!ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  for (DeviceSlot& s : ctx->slots) {
-    NOS_HIP_CHECK(hipSetDevice(s.device));
-    NOS_HIP_CHECK(hipStreamSynchronize(s.stream));
-  }
-  return NOS_OK;
-}
-
-namespace {
-struct OptionEntry {
-  const char* key;
-  int nosd::Settings::*field;
-  int lo, hi;
-};
-const OptionEntry kOptions[] = {
-    // key, field, lowest and highest accepted value
-    {"plane_skew", &nosd::Settings::plane_skew, 0, 1 << 20},
-    {"sc1", &nosd::Settings::sc1, 0, 1},
-    {"nt", &nosd::Settings::nt, -1, 1},
-    {"fused", &nosd::Settings::fused, 0, 1},
-    {"lm_fused", &nosd::Settings::lm_fused, 0, 1},
-    {"lm_window", &nosd::Settings::lm_window, 1, nosd::kLogSlots - 2},
-    {"lm_single", &nosd::Settings::lm_single, 0, 1},
-    {"lm_cluster", &nosd::Settings::lm_cluster, 0, 5},
-    {"lm_cluster_retry_ms", &nosd::Settings::lm_cluster_retry_ms, 0, 3600000},
-    {"pool", &nosd::Settings::pool, 0, 1},
-    {"tile_log2", &nosd::Settings::tile_log2, -1, 24},
-    {"ingest", &nosd::Settings::ingest, 0, 2},
-    {"ingest_threads", &nosd::Settings::ingest_threads, 0, 1024},
-    {"indexed_bpc", &nosd::Settings::indexed_bpc, 1, 16},
-    {"match_dense", &nosd::Settings::match_dense, 0, 1},
-    {"map_compact_keys", &nosd::Settings::map_compact_keys, 0, 1},
-    {"pgo_host_scalars", &nosd::Settings::pgo_host_scalars, 0, 1},
-    {"pgo_precond", &nosd::Settings::pgo_precond, 0, 1},
-    {"pgo_agg", &nosd::Settings::pgo_agg, 2, 1 << 20},
-    {"pgo_block", &nosd::Settings::pgo_block, 0, 1},
-    {"pgo_coarse_probe", &nosd::Settings::pgo_coarse_probe, 0, 1},
-    {"map_fma_mask", &nosd::Settings::map_fma_mask, 0, (1 << 26) - 1},
-    {"map_eigen_version", &nosd::Settings::map_eigen_version, 33, 34},
-    {"debug_cluster_abort", &nosd::Settings::debug_cluster_abort, 0, 2},
-    {"lm_cluster_max_blocks", &nosd::Settings::lm_cluster_max_blocks, 1, 256},
-    {"stream_lds_chunks", &nosd::Settings::stream_lds_chunks, 0, 3},
-    {"stream_reg_rounds", &nosd::Settings::stream_reg_rounds, 0, nos::kStreamRegRoundsMax},
-    {"batch_max_elements", &nosd::Settings::batch_max_elements, 0, 1 << 30},
-};
-bool option_in_range(const OptionEntry& o, int value);
-void drop_out_of_range_settings(nosd::Settings& st) {
-  const nosd::Settings defaults;
-  for (const OptionEntry& o : kOptions)
-    if (!option_in_range(o, st.*(o.field))) {
-      fprintf(stderr, "[nos-hip] NOS_%s = %d is outside [%d, %d]: ignored\n", o.key, st.*(o.field), o.lo, o.hi);
-      st.*(o.field) = defaults.*(o.field);
-    }
-}
-bool option_in_range(const OptionEntry& o, int value) {
-  if (value < o.lo || value > o.hi) return false;
-  if (!strcmp(o.key, "tile_log2")) return value <= 0 || value >= 10;  // -1 by element type, 0 planar, tiles of 2^10 … 2^24
-  return true;
-}
-}  // namespace
-
-int nos_ctx_set_option(nos_ctx* ctx, const char* key, int value) {
-  if (!ctx || !key) return fail(NOS_ERR_INVALID_ARGUMENT, "ctx / key is NULL");
-  nosd::CtxGuard guard_(ctx);
-  for (const OptionEntry& o : kOptions)
-    if (!strcmp(o.key, key)) {
-      if (!option_in_range(o, value))
-        return fail(NOS_ERR_INVALID_ARGUMENT, "option '%s' = %d is outside [%d, %d]", key, value, o.lo, o.hi);
-      ctx->settings.*(o.field) = value;
-      for (DeviceSlot& s : ctx->slots) s.pool_enabled = ctx->settings.pool != 0;
-      return NOS_OK;
-    }
-  return fail(NOS_ERR_INVALID_ARGUMENT, "unknown option '%s'", key);
-}
-
-int nos_ctx_get_option(const nos_ctx* ctx, const char* key, int* value) {
-  if (!ctx || !key || !value) return fail(NOS_ERR_INVALID_ARGUMENT, "ctx / key / value is NULL");
-  nosd::CtxGuard guard_(ctx);
-  for (const OptionEntry& o : kOptions)
-    if (!strcmp(o.key, key)) {
-      *value = ctx->settings.*(o.field);
-      return NOS_OK;
-    }
-  return fail(NOS_ERR_INVALID_ARGUMENT, "unknown option '%s'", key);
-}
-
-// Where the HIP runtime and the collectives library mapped into this process come from, and whether that is the ROCm
-// the library was built with.  One line of JSON.
-int nos_runtime_info(char* buf, size_t capacity) {
-  if (!buf || capacity == 0) return fail(NOS_ERR_INVALID_ARGUMENT, "buf is NULL");
-  int runtime = 0, driver = 0;
-  (void)hipRuntimeGetVersion(&runtime);
-  (void)hipDriverGetVersion(&driver);
-  std::string hip_file;
-  const std::string hip_dir = dir_of_symbol(reinterpret_cast<const void*>(&hipGetDeviceCount), &hip_file);
-  RcclApi* api = Rccl();
-  int rccl_version = 0;
-  if (api->ok && api->GetVersion) (void)api->GetVersion(&rccl_version);
-  const std::string rccl_file = api->ok ? api->path : std::string();
-  const size_t slash = rccl_file.rfind('/');
-  const std::string rccl_dir = slash == std::string::npos ? std::string() : rccl_file.substr(0, slash);
-  const int build = HIP_VERSION;  // major * 10^7 + minor * 10^5 + patch, same encoding as hipRuntimeGetVersion
-  const int n = snprintf(buf, capacity,
-                         "{\"build_hip_version\": %d, \"runtime_hip_version\": %d, \"driver_version\": %d, "
-                         "\"hip_runtime_path\": \"%s\", \"rccl_path\": \"%s\", \"rccl_version\": %d, "
-                         "\"same_rocm_tree\": %s, \"runtime_matches_build\": %s}",
-                         build, runtime, driver, hip_file.c_str(), rccl_file.c_str(), rccl_version,
-                         (!rccl_dir.empty() && rccl_dir == hip_dir) ? "true" : "false",
-                         (build / 100000 == runtime / 100000) ? "true" : "false");
-  if (n < 0 || size_t(n) >= capacity) return fail(NOS_ERR_INVALID_ARGUMENT, "buffer too small");
-  return NOS_OK;
-}
-
-// Symbol (demangled) of the hot-path kernel launched last on `shard` of this context — the instantiation the library
-// chose (problem, element type, loss, launch geometry / loop form), as rocprofv3 will list it.
-int nos_ctx_last_kernel(const nos_ctx* ctx, int shard, char* buf, size_t capacity) {
-  if (!ctx || !buf || capacity == 0) return fail(NOS_ERR_INVALID_ARGUMENT, "ctx / buf is NULL");
-  nosd::CtxGuard guard_(ctx);
-  if (shard < 0 || size_t(shard) >= ctx->slots.size()) return fail(NOS_ERR_INVALID_ARGUMENT, "bad shard index");
-  buf[0] = 0;
-  const DeviceSlot& slot = ctx->slots[shard];
-  if (slot.last_kernel == nullptr) return NOS_OK;
-  NOS_HIP_CHECK(hipSetDevice(slot.device));
-  const char* mangled = hipKernelNameRefByPtr(slot.last_kernel, slot.stream);
-  if (mangled == nullptr) return fail(NOS_ERR_HIP, "hipKernelNameRefByPtr returned NULL");
-  int status = 0;
-  char* dem = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
-  snprintf(buf, capacity, "%s", (status == 0 && dem) ? dem : mangled);
-  free(dem);
-  return NOS_OK;
-}
-
-// Number of ranks RCCL itself reports for the context's communicator (ncclCommCount); 0 without an RCCL communicator.
-int nos_ctx_comm_rccl_count(const nos_ctx* ctx, int* count) {
-  if (!ctx || !count) return fail(NOS_ERR_INVALID_ARGUMENT, "ctx / count is NULL");
-  nosd::CtxGuard guard_(ctx);
-  *count = 0;
-  if (ctx->comm == nullptr) return NOS_OK;
-  RcclApi* api = Rccl();
-  if (!api->ok || !api->CommCount) return fail(NOS_ERR_UNSUPPORTED, "ncclCommCount unavailable");
-  NOS_RCCL_CHECK(api->CommCount(ctx->comm, count));
-  return NOS_OK;
-}
-
-int nos_ctx_set_launch(nos_ctx* ctx, int blocks_per_cu, int variant) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  if (!ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (blocks_per_cu < 0 || blocks_per_cu > 32 || variant < 0 || variant >= kNumVariants)
-    return fail(NOS_ERR_INVALID_ARGUMENT, "launch override out of range");
-  ctx->blocks_per_cu = blocks_per_cu;
-  ctx->variant = variant;
-  return NOS_OK;
-}
-
-int nos_ndt_dataset_create(nos_ctx* ctx, size_t n, const double* const planes[NOS_NDT_PLANES], int dtype,
-                           nos_dataset** out_ds) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  return create_from_host_planes(ctx, kKindNdt, n, planes, dtype, out_ds);
-}
-
-int nos_reproj_dataset_create(nos_ctx* ctx, size_t n, const double* const planes[NOS_REPROJ_PLANES], int dtype,
-                              nos_dataset** out_ds) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  return create_from_host_planes(ctx, kKindReproj, n, planes, dtype, out_ds);
-}
-
-int nos_ndt_dataset_create_from_device(nos_ctx* ctx, size_t n, const void* const d_planes[NOS_NDT_PLANES],
-                                       int src_dtype, int dtype, nos_dataset** out_ds) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  return create_from_device_planes(ctx, kKindNdt, n, d_planes, src_dtype, dtype, out_ds);
-}
-
-int nos_reproj_dataset_create_from_device(nos_ctx* ctx, size_t n, const void* const d_planes[NOS_REPROJ_PLANES],
-                                          int src_dtype, int dtype, nos_dataset** out_ds) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  return create_from_device_planes(ctx, kKindReproj, n, d_planes, src_dtype, dtype, out_ds);
-}
-
-int nos_ndt_dataset_create_from_records(nos_ctx* ctx, size_t n, const void* records, size_t stride_bytes,
-                                        const size_t field_offsets[NOS_NDT_PLANES], int dtype,
-                                        nos_dataset** out_ds) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  return create_from_records(ctx, kKindNdt, n, records, stride_bytes, field_offsets, dtype, out_ds);
-}
-
-int nos_reproj_dataset_create_from_records(nos_ctx* ctx, size_t n, const void* records, size_t stride_bytes,
-                                           const size_t field_offsets[NOS_REPROJ_PLANES], int dtype,
-                                           nos_dataset** out_ds) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  return create_from_records(ctx, kKindReproj, n, records, stride_bytes, field_offsets, dtype, out_ds);
-}
-
-int nos_dataset_destroy(nos_dataset* ds) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  if (!ds) return NOS_OK;
-  for (Shard& sh : ds->shards) {
-    if (sh.data || sh.index || sh.table) (void)hipSetDevice(ds->ctx->slots[sh.slot].device);
-    if (sh.data) {
-      // the stream may still be reading the buffer (asynchronous entry points): wait before it is handed on
-      if (sh.pooled) {
-        (void)hipStreamSynchronize(ds->ctx->slots[sh.slot].stream);
-        pool_release(ds->ctx->slots[sh.slot], sh.data, sh.capacity);
-      } else {
-        (void)hipFree(sh.data);
-      }
-    }
-    if (sh.index && !sh.one_block) (void)hipFree(sh.index);
-    if (sh.table && !sh.one_block) (void)hipFree(sh.table);
-  }
-  delete ds;
-  return NOS_OK;
-}
-
-int nos_dataset_set_simd_class(nos_dataset* ds, int on) {
-  if (!ds) return fail(NOS_ERR_INVALID_ARGUMENT, "dataset is NULL");
-  nosd::CtxGuard guard_(ds->ctx);
-  ds->simd_class = on != 0 ? 1 : 0;
-  return NOS_OK;
-}
-size_t nos_dataset_size(const nos_dataset* ds) { return ds ? ds->n : 0; }
-int nos_dataset_dtype(const nos_dataset* ds) { return ds ? ds->dtype : -1; }
-size_t nos_dataset_stream_bytes(const nos_dataset* ds) {
-  if (!ds) return 0;
-  if (ds->kind == kKindNdtIndexed)  // point (3 values) + one 4-byte voxel id per slot; the voxel table is cache resident
-    return ds->n * (3 * elem_size(ds->dtype) + sizeof(int32_t) * size_t(ds->shards.empty() ? 0 : ds->shards[0].n_slots));
-  // flat datasets: the planes of the caller's record (nos.h).  Flat NDT kernels stream 12 of the 15 (p, mu, U with S = QU;
-  // fp32 3-DoF: p, mu, S) — the figure stays the record's, which the test suite pins.
-  return ds->n * size_t(ds->n_fields) * elem_size(ds->dtype);
-}
-
 int nos_ndt6_accumulate(nos_dataset* ds, const double R[9], const double t[3], const nos_loss* loss,
                         double out28[NOS_NDT6_OUT]) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  Request rq;
-  int rc = build_request(6, ds, R, 9, t, 3, nullptr, 0.0, loss, &rq);
-  if (rc != NOS_OK) return rc;
-  if (!out28) return fail(NOS_ERR_INVALID_ARGUMENT, "out28 is NULL");
-  return accumulate_sync(ds, rq, out28);
+  return with_request(6, ds, R, 9, t, 3, nullptr, 0.0, loss, [&](const Request& rq) {
+    if (!out28) return fail(NOS_ERR_INVALID_ARGUMENT, "out28 is NULL");
+    return accumulate_sync(ds, rq, out28);
+  });
 }
 
 int nos_ndt3_accumulate(nos_dataset* ds, const double R2[4], const double t2[2], const nos_loss* loss,
                         double out10[NOS_NDT3_OUT]) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  Request rq;
-  int rc = build_request(3, ds, R2, 4, t2, 2, nullptr, 0.0, loss, &rq);
-  if (rc != NOS_OK) return rc;
-  if (!out10) return fail(NOS_ERR_INVALID_ARGUMENT, "out10 is NULL");
-  return accumulate_sync(ds, rq, out10);
+  return with_request(3, ds, R2, 4, t2, 2, nullptr, 0.0, loss, [&](const Request& rq) {
+    if (!out10) return fail(NOS_ERR_INVALID_ARGUMENT, "out10 is NULL");
+    return accumulate_sync(ds, rq, out10);
+  });
 }
 
 int nos_reproj_accumulate(nos_dataset* ds, const double R[9], const double t[3], const double intr[4],
                           const nos_loss* loss, double min_depth, double out28[NOS_REPROJ_OUT]) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  Request rq;
-  int rc = build_request(2, ds, R, 9, t, 3, intr, min_depth, loss, &rq);
-  if (rc != NOS_OK) return rc;
-  if (!out28) return fail(NOS_ERR_INVALID_ARGUMENT, "out28 is NULL");
-  return accumulate_sync(ds, rq, out28);
+  return with_request(2, ds, R, 9, t, 3, intr, min_depth, loss, [&](const Request& rq) {
+    if (!out28) return fail(NOS_ERR_INVALID_ARGUMENT, "out28 is NULL");
+    return accumulate_sync(ds, rq, out28);
+  });
 }
 
 int nos_ndt6_accumulate_async(nos_dataset* ds, const double R[9], const double t[3], const nos_loss* loss,
                               double* d_out28) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  Request rq;
-  int rc = build_request(6, ds, R, 9, t, 3, nullptr, 0.0, loss, &rq);
-  if (rc != NOS_OK) return rc;
-  return accumulate_async(ds, rq, d_out28);
+  return with_request(6, ds, R, 9, t, 3, nullptr, 0.0, loss,
+                      [&](const Request& rq) { return accumulate_async(ds, rq, d_out28); });
 }
 
 int nos_ndt3_accumulate_async(nos_dataset* ds, const double R2[4], const double t2[2], const nos_loss* loss,
                               double* d_out10) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  Request rq;
-  int rc = build_request(3, ds, R2, 4, t2, 2, nullptr, 0.0, loss, &rq);
-  if (rc != NOS_OK) return rc;
-  return accumulate_async(ds, rq, d_out10);
+  return with_request(3, ds, R2, 4, t2, 2, nullptr, 0.0, loss,
+                      [&](const Request& rq) { return accumulate_async(ds, rq, d_out10); });
 }
 
 int nos_reproj_accumulate_async(nos_dataset* ds, const double R[9], const double t[3], const double intr[4],
                                 const nos_loss* loss, double min_depth, double* d_out28) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  Request rq;
-  int rc = build_request(2, ds, R, 9, t, 3, intr, min_depth, loss, &rq);
-  if (rc != NOS_OK) return rc;
-  return accumulate_async(ds, rq, d_out28);
+  return with_request(2, ds, R, 9, t, 3, intr, min_depth, loss,
+                      [&](const Request& rq) { return accumulate_async(ds, rq, d_out28); });
 }
 
 int nos_ndt6_solve(nos_dataset* ds, double R[9], double t[3], const nos_loss* loss, const nos_lm_options* options,
                    nos_lm_report* report) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  Request rq;
-  int rc = build_request(6, ds, R, 9, t, 3, nullptr, 0.0, loss, &rq);
-  if (rc != NOS_OK) return rc;
-  return lm_solve(ds, rq, options, R, 9, t, 3, report);
+  return with_request(6, ds, R, 9, t, 3, nullptr, 0.0, loss,
+                      [&](const Request& rq) { return lm_solve(ds, rq, options, R, 9, t, 3, report); });
 }
 
 int nos_ndt3_solve(nos_dataset* ds, double R2[4], double t2[2], const nos_loss* loss, const nos_lm_options* options,
                    nos_lm_report* report) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  Request rq;
-  int rc = build_request(3, ds, R2, 4, t2, 2, nullptr, 0.0, loss, &rq);
-  if (rc != NOS_OK) return rc;
-  return lm_solve(ds, rq, options, R2, 4, t2, 2, report);
+  return with_request(3, ds, R2, 4, t2, 2, nullptr, 0.0, loss,
+                      [&](const Request& rq) { return lm_solve(ds, rq, options, R2, 4, t2, 2, report); });
 }
 
 int nos_reproj_solve(nos_dataset* ds, double R[9], double t[3], const double intr[4], const nos_loss* loss,
                      double min_depth, const nos_lm_options* options, nos_lm_report* report) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  Request rq;
-  int rc = build_request(2, ds, R, 9, t, 3, intr, min_depth, loss, &rq);
-  if (rc != NOS_OK) return rc;
-  return lm_solve(ds, rq, options, R, 9, t, 3, report);
+  return with_request(2, ds, R, 9, t, 3, intr, min_depth, loss,
+                      [&](const Request& rq) { return lm_solve(ds, rq, options, R, 9, t, 3, report); });
 }
 
 int nos_ndt6_time_kernel(nos_dataset* ds, const double R[9], const double t[3], const nos_loss* loss, int repeats,
                          double* kernel_ms, double* total_ms) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  Request rq;
-  int rc = build_request(6, ds, R, 9, t, 3, nullptr, 0.0, loss, &rq);
-  if (rc != NOS_OK) return rc;
-  return time_kernel(ds, rq, repeats, kernel_ms, total_ms);
+  return with_request(6, ds, R, 9, t, 3, nullptr, 0.0, loss,
+                      [&](const Request& rq) { return time_kernel(ds, rq, repeats, kernel_ms, total_ms); });
 }
 
 int nos_ndt3_time_kernel(nos_dataset* ds, const double R2[4], const double t2[2], const nos_loss* loss, int repeats,
                          double* kernel_ms, double* total_ms) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  Request rq;
-  int rc = build_request(3, ds, R2, 4, t2, 2, nullptr, 0.0, loss, &rq);
-  if (rc != NOS_OK) return rc;
-  return time_kernel(ds, rq, repeats, kernel_ms, total_ms);
+  return with_request(3, ds, R2, 4, t2, 2, nullptr, 0.0, loss,
+                      [&](const Request& rq) { return time_kernel(ds, rq, repeats, kernel_ms, total_ms); });
 }
 
 int nos_reproj_time_kernel(nos_dataset* ds, const double R[9], const double t[3], const double intr[4],
                            const nos_loss* loss, double min_depth, int repeats, double* kernel_ms,
                            double* total_ms) {
-  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  Request rq;
-  int rc = build_request(2, ds, R, 9, t, 3, intr, min_depth, loss, &rq);
-  if (rc != NOS_OK) return rc;
-  return time_kernel(ds, rq, repeats, kernel_ms, total_ms);
+  return with_request(2, ds, R, 9, t, 3, intr, min_depth, loss,
+                      [&](const Request& rq) { return time_kernel(ds, rq, repeats, kernel_ms, total_ms); });
 }
 
 int nos_debug_lm_step(nos_ctx* ctx, int dof, const double* sums, const double settings[4], double state[22]) {
@@ -2099,361 +977,4 @@ int nos_debug_lm_step(nos_ctx* ctx, int dof, const double* sums, const double se
   return NOS_OK;
 }
 
-int nos_comm_get_unique_id(unsigned char id[NOS_COMM_ID_BYTES]) {
-  if (!id) return fail(NOS_ERR_INVALID_ARGUMENT, "id is NULL");
-  RcclApi* api = Rccl();
-  if (!api->ok) return fail(NOS_ERR_UNSUPPORTED, "librccl could not be loaded: %s", dlerror() ? dlerror() : "missing symbols");
-  static_assert(NOS_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "unique id size");
-  ncclUniqueId uid;
-  NOS_RCCL_CHECK(api->GetUniqueId(&uid));
-  memcpy(id, uid.internal, NOS_COMM_ID_BYTES);
-  return NOS_OK;
-}
-
-int nos_ctx_comm_init(nos_ctx* ctx, int n_ranks, int rank, const unsigned char id[NOS_COMM_ID_BYTES]) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  if (!ctx || !id || n_ranks < 1 || rank < 0 || rank >= n_ranks) return fail(NOS_ERR_INVALID_ARGUMENT, "bad comm arguments");
-  if (ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "a communicator needs a single-device context");
-  if (ctx->comm != nullptr) return fail(NOS_ERR_INVALID_ARGUMENT, "communicator already initialised");
-  RcclApi* api = Rccl();
-  if (!api->ok) return fail(NOS_ERR_UNSUPPORTED, "librccl could not be loaded");
-  NOS_HIP_CHECK(hipSetDevice(ctx->slots[0].device));
-  ncclUniqueId uid;
-  memcpy(uid.internal, id, NOS_COMM_ID_BYTES);
-  ncclComm_t comm = nullptr;
-  NOS_RCCL_CHECK(api->CommInitRank(&comm, n_ranks, uid, rank));
-  ctx->comm = comm;
-  ctx->comm_ranks = n_ranks;
-  return NOS_OK;
-}
-
-int nos_ctx_comm_size(const nos_ctx* ctx) { return (ctx && (ctx->comm || ctx->shm_dev)) ? ctx->comm_ranks : 0; }
-
 }  // extern "C"
-
-namespace {
-// Both mailbox communicators: the handshake and control words always live in the POSIX shm segment; the SLOTS the kernels
-// exchange through live there too (device_slots = false: bytes travel over PCIe to host memory) or in fine-grained device
-// memory of every rank, exported with hipIpcGetMemHandle and opened by the peers (device_slots = true: a rank writes its
-// sums straight into every peer's buffer — over xGMI between GPUs — and polls only its own memory).
-int comm_init_mailbox(nos_ctx* ctx, int n_ranks, int rank, const char* shm_name, bool device_slots) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  if (!ctx || !shm_name || shm_name[0] != '/' || n_ranks < 1 || n_ranks > 64 || rank < 0 || rank >= n_ranks)
-    return fail(NOS_ERR_INVALID_ARGUMENT, "bad comm arguments (name must start with '/', at most 64 ranks)");
-  if (ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "a communicator needs a single-device context");
-  if (ctx->comm != nullptr || ctx->shm_dev != nullptr) return fail(NOS_ERR_INVALID_ARGUMENT, "communicator already initialised");
-  DeviceSlot& slot = ctx->slots[0];
-  NOS_HIP_CHECK(hipSetDevice(slot.device));
-  size_t bytes = 0;
-  // Attach with a handshake that cannot be fooled by a segment of that name left behind by a crashed run (whose flag
-  // words would otherwise match the first round numbers and feed stale sums into the exchange):
-  //   rank 0 unlinks the name, creates the segment EXCLUSIVELY (a fresh, zero-filled inode), publishes a random nonce and
-  //   acknowledges every rank's own fresh random hello word with hello ^ nonce;
-  //   rank k opens the name (retrying), writes its hello and accepts the mapping only when its acknowledgement shows up —
-  //   a stale inode never acknowledges a fresh 64-bit random, so rank k drops it and opens the name again.
-  // Bounded: NOS_SHM_ATTACH_TIMEOUT_MS (default 30 s) in total.  Header (after the slots): [0] nonce, [1..64] hello, [65..128] ack.
-  const int kAttachTimeoutMs = std::max(100, env_int("NOS_SHM_ATTACH_TIMEOUT_MS", 30000));  // set-up path, not the solve path
-  const size_t slots_bytes = size_t(n_ranks) * 2 * nos::kMailSlotDoubles * sizeof(double);
-  // header (after the slots), in 8-byte words: [0] nonce, [1..64] hello, [65..128] ack, [129..192] ipc-ready, [193..704] 64 IPC handles of 64 bytes
-  const size_t header_words = 1 + 64 + 64 + 64 + 64 * 8;
-  static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
-  bytes = (slots_bytes + header_words * sizeof(unsigned long long) + 4095) & ~size_t(4095);
-  auto now_ms = [] {
-    return std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  };
-  auto fresh_random = [&]() -> unsigned long long {
-    unsigned long long v = 0;
-    std::random_device rd;
-    while (v == 0) v = (static_cast<unsigned long long>(rd()) << 32) ^ rd() ^ (static_cast<unsigned long long>(getpid()) << 17);
-    return v;
-  };
-  const long long deadline = now_ms() + kAttachTimeoutMs;
-  void* host = MAP_FAILED;
-  if (rank == 0) {
-    (void)shm_unlink(shm_name);
-    int fd = shm_open(shm_name, O_CREAT | O_EXCL | O_RDWR, 0600);
-    if (fd < 0 && errno == EEXIST) {  // somebody re-created it in between: once more
-      (void)shm_unlink(shm_name);
-      fd = shm_open(shm_name, O_CREAT | O_EXCL | O_RDWR, 0600);
-    }
-    if (fd < 0) return fail(NOS_ERR_HIP, "shm_open(%s) failed: %s", shm_name, strerror(errno));
-    if (ftruncate(fd, off_t(bytes)) != 0) {  // fresh pages read as zero = round 0 everywhere
-      const int e = errno;
-      close(fd);
-      (void)shm_unlink(shm_name);
-      return fail(NOS_ERR_HIP, "ftruncate(%s) failed: %s", shm_name, strerror(e));
-    }
-    host = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    close(fd);
-    if (host == MAP_FAILED) return fail(NOS_ERR_HIP, "mmap(%s) failed: %s", shm_name, strerror(errno));
-    auto* hdr = reinterpret_cast<std::atomic<unsigned long long>*>(static_cast<char*>(host) + slots_bytes);
-    const unsigned long long nonce = fresh_random();
-    hdr[0].store(nonce, std::memory_order_release);
-    for (int k = 1; k < n_ranks; ++k) {
-      unsigned long long hello = 0;
-      while ((hello = hdr[1 + k].load(std::memory_order_acquire)) == 0) {
-        if (now_ms() > deadline) {
-          munmap(host, bytes);
-          return fail(NOS_ERR_HIP, "rank %d did not attach to the mailbox %s within %d ms", k, shm_name, kAttachTimeoutMs);
-        }
-        usleep(200);
-      }
-      hdr[65 + k].store(hello ^ nonce, std::memory_order_release);
-    }
-  } else {
-    const unsigned long long hello = fresh_random();
-    for (;;) {
-      if (now_ms() > deadline)
-        return fail(NOS_ERR_HIP, "mailbox %s: no acknowledgement from rank 0 within %d ms", shm_name, kAttachTimeoutMs);
-      const int fd = shm_open(shm_name, O_RDWR, 0600);
-      if (fd < 0) {
-        usleep(500);
-        continue;
-      }
-      struct stat st {};
-      if (fstat(fd, &st) != 0 || size_t(st.st_size) < bytes) {  // not sized yet (or somebody else's segment)
-        close(fd);
-        usleep(500);
-        continue;
-      }
-      void* m = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-      close(fd);
-      if (m == MAP_FAILED) return fail(NOS_ERR_HIP, "mmap(%s) failed: %s", shm_name, strerror(errno));
-      auto* hdr = reinterpret_cast<std::atomic<unsigned long long>*>(static_cast<char*>(m) + slots_bytes);
-      hdr[1 + rank].store(hello, std::memory_order_release);
-      bool acked = false;
-      const long long until = std::min<long long>(deadline, now_ms() + 250);  // then look at the name again
-      while (now_ms() <= until) {
-        const unsigned long long nonce = hdr[0].load(std::memory_order_acquire);
-        if (nonce != 0 && hdr[65 + rank].load(std::memory_order_acquire) == (hello ^ nonce)) {
-          acked = true;
-          break;
-        }
-        usleep(200);
-      }
-      if (acked) {
-        host = m;
-        break;
-      }
-      munmap(m, bytes);  // stale inode (or rank 0 not there yet): drop it and open the name again
-    }
-  }
-  hipError_t e = hipHostRegister(host, bytes, hipHostRegisterMapped | hipHostRegisterPortable);
-  void* dev = nullptr;
-  if (e == hipSuccess) {
-    e = hipHostGetDevicePointer(&dev, host, 0);
-    if (e != hipSuccess) (void)hipHostUnregister(host);
-  }
-  unsigned long long* d_round = nullptr;
-  if (e == hipSuccess) {
-    e = hipMalloc(reinterpret_cast<void**>(&d_round), 2 * sizeof(unsigned long long));  // [0] round, [1] patient-until round
-    if (e == hipSuccess) e = hipMemset(d_round, 0, 2 * sizeof(unsigned long long));
-    if (e != hipSuccess) (void)hipHostUnregister(host);
-  }
-  if (e != hipSuccess) {
-    if (d_round) (void)hipFree(d_round);
-    munmap(host, bytes);
-    return fail(NOS_ERR_HIP, "mapping the mailbox into the GPU failed: %s", hipGetErrorString(e));
-  }
-  *reinterpret_cast<volatile unsigned int*>(slot.h_out + kCommErrorSlot) = 0u;
-  ctx->shm_host = host;
-  ctx->shm_bytes = bytes;
-  ctx->shm_dev = static_cast<double*>(dev);
-  ctx->d_round = d_round;
-  ctx->comm_ranks = n_ranks;
-  ctx->comm_rank = rank;
-  if (device_slots) {
-    // every rank: its own [n_ranks][2][kMailSlotDoubles] buffer in fine-grained device memory (peers write into it across the
-    // fabric while this GPU polls it: no cache may keep a stale copy), exported through the shm header and opened by the others
-    auto* hdr = reinterpret_cast<std::atomic<unsigned long long>*>(static_cast<char*>(host) + slots_bytes);
-    hipIpcMemHandle_t* handles = reinterpret_cast<hipIpcMemHandle_t*>(hdr + 193);
-    double* own = nullptr;
-    // second half: the granule slots of the one-launch loop's in-launch exchange (solve_cluster_kernel, stage 3)
-    e = hipExtMallocWithFlags(reinterpret_cast<void**>(&own), 2 * slots_bytes, hipDeviceMallocFinegrained);
-    if (e == hipSuccess) e = hipMemset(own, 0, 2 * slots_bytes);
-    hipIpcMemHandle_t mine{};
-    if (e == hipSuccess) e = hipIpcGetMemHandle(&mine, own);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-      if (own) (void)hipFree(own);
-      (void)nos_ctx_comm_destroy(ctx);
-      return fail(NOS_ERR_UNSUPPORTED, "device-memory mailbox: fine-grained allocation / IPC export failed: %s", hipGetErrorString(e));
-    }
-    ctx->ipc_own = own;
-    memcpy(&handles[rank], &mine, sizeof mine);
-    hdr[129 + rank].store(1ull, std::memory_order_release);
-    ctx->ipc_peers.assign(size_t(n_ranks), nullptr);
-    ctx->ipc_peers[size_t(rank)] = own;
-    for (int k = 0; k < n_ranks; ++k) {
-      if (k == rank) continue;
-      while (hdr[129 + k].load(std::memory_order_acquire) == 0ull) {
-        if (now_ms() > deadline) {
-          (void)nos_ctx_comm_destroy(ctx);
-          return fail(NOS_ERR_HIP, "device-memory mailbox %s: rank %d did not publish its IPC handle within %d ms", shm_name, k, kAttachTimeoutMs);
-        }
-        usleep(200);
-      }
-      hipIpcMemHandle_t theirs;
-      memcpy(&theirs, &handles[k], sizeof theirs);
-      void* p = nullptr;
-      e = hipIpcOpenMemHandle(&p, theirs, hipIpcMemLazyEnablePeerAccess);
-      if (e != hipSuccess) {
-        (void)nos_ctx_comm_destroy(ctx);
-        return fail(NOS_ERR_UNSUPPORTED, "device-memory mailbox: hipIpcOpenMemHandle(rank %d) failed: %s", k, hipGetErrorString(e));
-      }
-      ctx->ipc_peers[size_t(k)] = static_cast<double*>(p);
-    }
-    e = hipMalloc(reinterpret_cast<void**>(&ctx->d_peers), sizeof(double*) * size_t(n_ranks));
-    if (e == hipSuccess) e = hipMemcpy(ctx->d_peers, ctx->ipc_peers.data(), sizeof(double*) * size_t(n_ranks), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)nos_ctx_comm_destroy(ctx);
-      return fail(NOS_ERR_HIP, "device-memory mailbox: uploading the peer table failed: %s", hipGetErrorString(e));
-    }
-    // nobody may start exchanging (or leave and free its buffer) before every rank has opened every buffer
-    hdr[129 + rank].store(2ull, std::memory_order_release);
-    for (int k = 0; k < n_ranks; ++k)
-      while (hdr[129 + k].load(std::memory_order_acquire) < 2ull) {
-        if (now_ms() > deadline) {
-          (void)nos_ctx_comm_destroy(ctx);
-          return fail(NOS_ERR_HIP, "device-memory mailbox %s: rank %d did not finish attaching within %d ms", shm_name, k, kAttachTimeoutMs);
-        }
-        usleep(200);
-      }
-  }
-  const nos::Mailbox mb = mailbox_of(ctx, slot);
-  e = hipMalloc(reinterpret_cast<void**>(&ctx->d_mail), sizeof(nos::Mailbox));
-  if (e == hipSuccess) e = hipMemcpy(ctx->d_mail, &mb, sizeof mb, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)nos_ctx_comm_destroy(ctx);
-    return fail(NOS_ERR_HIP, "uploading the mailbox descriptor failed: %s", hipGetErrorString(e));
-  }
-  return NOS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int nos_ctx_comm_init_shm(nos_ctx* ctx, int n_ranks, int rank, const char* shm_name) {
-  return comm_init_mailbox(ctx, n_ranks, rank, shm_name, false);
-}
-
-int nos_ctx_comm_init_shm_device(nos_ctx* ctx, int n_ranks, int rank, const char* shm_name) {
-  return comm_init_mailbox(ctx, n_ranks, rank, shm_name, true);
-}
-
-int nos_comm_shm_unlink(const char* shm_name) {
-  if (!shm_name) return fail(NOS_ERR_INVALID_ARGUMENT, "name is NULL");
-  if (shm_unlink(shm_name) != 0 && errno != ENOENT) return fail(NOS_ERR_HIP, "shm_unlink(%s) failed: %s", shm_name, strerror(errno));
-  return NOS_OK;
-}
-
-int nos_ctx_comm_allreduce(nos_ctx* ctx, double* values, int count) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  if (!ctx || !values || count < 1 || count > kMaxOut) return fail(NOS_ERR_INVALID_ARGUMENT, "bad allreduce arguments");
-  if (ctx->comm == nullptr && ctx->shm_dev == nullptr) return fail(NOS_ERR_INVALID_ARGUMENT, "no communicator");
-  DeviceSlot& slot = ctx->slots[0];
-  NOS_HIP_CHECK(hipSetDevice(slot.device));
-  NOS_HIP_CHECK(hipMemcpyAsync(slot.d_out, values, sizeof(double) * count, hipMemcpyHostToDevice, slot.stream));
-  if (ctx->shm_dev != nullptr) {
-    hipLaunchKernelGGL(nos::mailbox_allreduce_kernel, dim3(1), dim3(64), 0, slot.stream, mailbox_of(ctx, slot), slot.d_out, count);
-    NOS_HIP_CHECK(hipGetLastError());
-  } else {
-    NOS_RCCL_CHECK(Rccl()->AllReduce(slot.d_out, slot.d_out, size_t(count), ncclDouble, ncclSum, ctx->comm, slot.stream));
-  }
-  NOS_HIP_CHECK(hipMemcpyAsync(values, slot.d_out, sizeof(double) * count, hipMemcpyDeviceToHost, slot.stream));
-  NOS_HIP_CHECK(hipStreamSynchronize(slot.stream));
-  return check_mailbox_error(ctx, slot);
-}
-
-int nos_ctx_profile_begin(nos_ctx* ctx, int max_launches, int sample_every) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  if (!ctx || max_launches < 1 || max_launches > (1 << 20) || sample_every < 0)
-    return fail(NOS_ERR_INVALID_ARGUMENT, "bad profile request");
-  for (DeviceSlot& s : ctx->slots) {
-    NOS_HIP_CHECK(hipSetDevice(s.device));
-    if (sample_every == 0) {  // bracket form
-      s.prof_used = 0;
-      s.prof_every = 0;
-      s.prof_launches = 0;
-      s.prof_on = true;
-      NOS_HIP_CHECK(hipEventRecord(s.ev0, s.stream));
-      continue;
-    }
-    while (s.prof_events.size() < size_t(max_launches) * 2) {
-      hipEvent_t e = nullptr;
-      NOS_HIP_CHECK(hipEventCreate(&e));
-      s.prof_events.push_back(e);
-    }
-    s.prof_used = 0;
-    s.prof_every = sample_every;
-    s.prof_launches = 0;
-    s.prof_on = true;
-  }
-  return NOS_OK;
-}
-
-int nos_ctx_profile_end(nos_ctx* ctx, int* n_launches, double* mean_ms, double* min_ms, double* max_ms) {
-  nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  if (!ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  int count = 0;
-  double sum = 0.0, lo = 1e300, hi = 0.0;
-  for (DeviceSlot& s : ctx->slots) {
-    const bool bracket = s.prof_on && s.prof_every == 0;
-    s.prof_on = false;
-    NOS_HIP_CHECK(hipSetDevice(s.device));
-    if (bracket) {
-      NOS_HIP_CHECK(hipEventRecord(s.ev1, s.stream));
-      NOS_HIP_CHECK(hipEventSynchronize(s.ev1));
-      float ms = 0.f;
-      NOS_HIP_CHECK(hipEventElapsedTime(&ms, s.ev0, s.ev1));
-      if (s.prof_launches > 0) {
-        const double per = double(ms) / double(s.prof_launches);
-        sum += per * double(s.prof_launches);
-        lo = std::min(lo, per);
-        hi = std::max(hi, per);
-        count += int(s.prof_launches);
-      }
-      s.prof_every = 1;
-      continue;
-    }
-    NOS_HIP_CHECK(hipStreamSynchronize(s.stream));
-    for (size_t i = 0; i + 1 < s.prof_used; i += 2) {
-      float ms = 0.f;
-      NOS_HIP_CHECK(hipEventElapsedTime(&ms, s.prof_events[i], s.prof_events[i + 1]));
-      sum += ms;
-      lo = std::min(lo, double(ms));
-      hi = std::max(hi, double(ms));
-      ++count;
-    }
-    s.prof_used = 0;
-  }
-  if (n_launches) *n_launches = count;
-  if (mean_ms) *mean_ms = count ? sum / count : 0.0;
-  if (min_ms) *min_ms = count ? lo : 0.0;
-  if (max_ms) *max_ms = count ? hi : 0.0;
-  return NOS_OK;
-}
-
-const char* nos_status_string(int status) {
-  switch (status) {
-    case NOS_OK: return "ok";
-    case NOS_ERR_INVALID_ARGUMENT: return "invalid argument";
-    case NOS_ERR_NO_DEVICE: return "no HIP device (no CPU fallback)";
-    case NOS_ERR_HIP: return "HIP runtime error";
-    case NOS_ERR_OUT_OF_MEMORY: return "out of memory";
-    case NOS_ERR_WRONG_KIND: return "dataset kind mismatch";
-    case NOS_ERR_UNSUPPORTED: return "unsupported";
-  }
-  return "unknown status";
-}
-
-const char* nos_last_error(void) { return nosd::last_error_text(); }
-#ifdef NOS_ALL_VARIANTS
-const char* nos_version(void) { return "nos-hip 0.3 (gfx950, all launch geometries)"; }
-#else
-const char* nos_version(void) { return "nos-hip 0.3 (gfx950)"; }
-#endif
-
-}  // extern "C"
-

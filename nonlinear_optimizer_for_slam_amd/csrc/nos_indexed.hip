@@ -45,10 +45,10 @@ int launch_indexed_by_loss(int loss_kind, int n_slots, const nos::IndexedLayout&
   return fail(NOS_ERR_INVALID_ARGUMENT, "unknown loss kind %d", loss_kind);
 }
 
-}  // namespace
-
-int nosd::launch_indexed(const nos_dataset* ds, const Shard& sh, const Request& rq, double* partials,
-                         const nos::FusedFinal& fin, hipStream_t stream, int* rows_out) {
+// One problem in one element type: its item parameters from the request, then the launch by loss and slot count.
+template <template <typename, int> class ProblemT, typename T>
+int launch_indexed_problem(const nos_dataset* ds, const Shard& sh, const Request& rq, double* partials,
+                           const nos::FusedFinal& fin, hipStream_t stream, int* rows_out) {
   const nos_ctx* ctx = ds->ctx;
   const DeviceSlot& slot = ctx->slots[sh.slot];
   nos::IndexedLayout L{};
@@ -56,40 +56,23 @@ int nosd::launch_indexed(const nos_dataset* ds, const Shard& sh, const Request& 
   L.index = sh.index;
   L.table = sh.table;
   L.n_padded = sh.layout.n_padded;
-  const int bpc = ctx->settings.indexed_bpc;
-  const int cap = bpc * slot.num_cus;
-  if (rq.problem == 6) {
-    if (ds->dtype == NOS_F64) {
-      nos::Ndt6Params<double> P;
-      for (int k = 0; k < 9; ++k) P.R[k] = rq.R[k];
-      for (int k = 0; k < 3; ++k) P.t[k] = rq.t[k];
-      fill_loss(&rq.loss, P.la, P.lb, P.lc);
-      return launch_indexed_by_loss<nos::Ndt6Problem, double>(rq.loss_kind, sh.n_slots, L, P, cap, slot.num_cus, partials, fin,
-                                                              stream, rows_out);
-    }
-    nos::Ndt6Params<float> P;
-    for (int k = 0; k < 9; ++k) P.R[k] = float(rq.R[k]);
-    for (int k = 0; k < 3; ++k) P.t[k] = float(rq.t[k]);
-    fill_loss(&rq.loss, P.la, P.lb, P.lc);
-    return launch_indexed_by_loss<nos::Ndt6Problem, float>(rq.loss_kind, sh.n_slots, L, P, cap, slot.num_cus, partials, fin,
-                                                           stream, rows_out);
-  }
-  if (rq.problem == 3) {
-    if (ds->dtype == NOS_F64) {
-      nos::Ndt3Params<double> P;
-      for (int k = 0; k < 4; ++k) P.R2[k] = rq.R[k];
-      for (int k = 0; k < 2; ++k) P.t2[k] = rq.t[k];
-      fill_loss(&rq.loss, P.la, P.lb, P.lc);
-      return launch_indexed_by_loss<nos::Ndt3Problem, double>(rq.loss_kind, sh.n_slots, L, P, cap, slot.num_cus, partials, fin,
-                                                              stream, rows_out);
-    }
-    nos::Ndt3Params<float> P;
-    for (int k = 0; k < 4; ++k) P.R2[k] = float(rq.R[k]);
-    for (int k = 0; k < 2; ++k) P.t2[k] = float(rq.t[k]);
-    fill_loss(&rq.loss, P.la, P.lb, P.lc);
-    return launch_indexed_by_loss<nos::Ndt3Problem, float>(rq.loss_kind, sh.n_slots, L, P, cap, slot.num_cus, partials, fin,
-                                                           stream, rows_out);
-  }
+  typename ProblemT<T, nos::kLossNone>::Params P{};
+  fill_params(P, rq, ds);
+  return launch_indexed_by_loss<ProblemT, T>(rq.loss_kind, sh.n_slots, L, P, ctx->settings.indexed_bpc * slot.num_cus,
+                                             slot.num_cus, partials, fin, stream, rows_out);
+}
+
+}  // namespace
+
+int nosd::launch_indexed(const nos_dataset* ds, const Shard& sh, const Request& rq, double* partials,
+                         const nos::FusedFinal& fin, hipStream_t stream, int* rows_out) {
+  const bool f64 = ds->dtype == NOS_F64;
+  if (rq.problem == 6)
+    return f64 ? launch_indexed_problem<nos::Ndt6Problem, double>(ds, sh, rq, partials, fin, stream, rows_out)
+               : launch_indexed_problem<nos::Ndt6Problem, float>(ds, sh, rq, partials, fin, stream, rows_out);
+  if (rq.problem == 3)
+    return f64 ? launch_indexed_problem<nos::Ndt3Problem, double>(ds, sh, rq, partials, fin, stream, rows_out)
+               : launch_indexed_problem<nos::Ndt3Problem, float>(ds, sh, rq, partials, fin, stream, rows_out);
   return fail(NOS_ERR_WRONG_KIND, "voxel-indexed datasets serve the NDT entry points only");
 }
 

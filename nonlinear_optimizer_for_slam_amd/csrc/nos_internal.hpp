@@ -33,9 +33,19 @@
 
 namespace nosd {
 
-// thread-local text of the last failure + status pass-through (defined in nos_core.hip)
+struct DeviceSlot;
+
+// nos_ctx.hip
+// thread-local text of the last failure + status pass-through
 int fail(int status, const char* fmt, ...);
 void clear_last_error();  // a failure that was handled (a fallback that went on to succeed) leaves no text behind
+// Directory of the shared object that provides `symbol` in this process ("" if unknown); file_out: its path.
+std::string dir_of_symbol(const void* symbol, std::string* file_out = nullptr);
+int env_int(const char* name, int dflt);
+// the slot's device-buffer pool; pool_drain frees what is parked there
+int pool_alloc(DeviceSlot& slot, size_t bytes, void** ptr, size_t* capacity);
+void pool_release(DeviceSlot& slot, void* ptr, size_t capacity);
+void pool_drain(DeviceSlot& slot);
 
 #define NOS_HIP_CHECK(expr)                                                               \
   do {                                                                                    \
@@ -60,7 +70,9 @@ struct RcclApi {
   bool ok = false;
 };
 
+// nos_comm.hip
 RcclApi* Rccl();
+void comm_release(nos_ctx* ctx);  // frees whatever communicator the context has (nos_ctx_destroy calls it)
 
 #define NOS_RCCL_CHECK(expr)                                                                     \
   do {                                                                                           \
@@ -74,6 +86,7 @@ constexpr int kMaxPartialRows = 8192;  // upper bound on grid size of the assemb
 constexpr int kMaxOut = 28;
 constexpr int kHistCapacity = 4096;     // iterations whose cost the single-workgroup solve can report
 constexpr int kLogSlots = 64;          // ring of loop log entries; bounds the number of launches in flight
+constexpr int kNumVariants = 14;       // compiled geometry variants per dtype (the NOS_CASE tables of nos_core.hip; 0 = default)
 
 struct DeviceSlot {
   int device = 0;
@@ -93,8 +106,6 @@ struct DeviceSlot {
   double* h_hist = nullptr;        // pinned, device-mapped cost history of the single-workgroup solve [kHistCapacity]
   double* h_hist_dev = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-  // per-launch kernel timing (nos_ctx_profile_begin/_end): event pairs recorded on the
-  // launch stream around every assemble kernel while profiling is on
   // Ingestion resources, created on first use and kept (a cold Solve() used to spend ≈ 3 ms creating and freeing
   // them): copy stream, events, two staging buffers that only grow.
   hipStream_t copy_stream = nullptr;
@@ -124,6 +135,8 @@ struct DeviceSlot {
   // SOLVES — every rank gives up in the same solve and counts the same calls — not in wall time.
   int cluster_paused_solves = 0;
   int cluster_next_pause = 64;  // doubles with every give-up in a row (up to 65 536 solves), back to 64 after a one-launch solve that finished
+  // per-launch kernel timing (nos_ctx_profile_begin/_end): event pairs recorded on the
+  // launch stream around every assemble kernel while profiling is on
   std::vector<hipEvent_t> prof_events;
   size_t prof_used = 0;
   bool prof_on = false;
@@ -131,10 +144,6 @@ struct DeviceSlot {
   long prof_launches = 0;
 };
 
-
-}  // namespace nosd
-
-namespace nosd {
 constexpr int kMapReferenceFmaMask = (4 | 8 | 16 | 32) | ((1 | 4 | 8 | 32 | 256) << 8) | (0x1ff << 17);
 // Experiment / test knobs.  Read from the environment ONCE, when the context is created (nos_ctx_create), and
 // changed afterwards only through nos_ctx_set_option: nothing on the solve / accumulate path calls getenv().
@@ -288,9 +297,6 @@ hipError_t upload(T** dptr, const std::vector<T>& host) {
   return e;
 }
 
-int pool_alloc(DeviceSlot& slot, size_t bytes, void** ptr, size_t* capacity);
-void pool_release(DeviceSlot& slot, void* ptr, size_t capacity);
-
 // Scratch buffers of one call, freed when it returns.  Without a slot: one hipMalloc / hipFree per buffer (round 1).  With a
 // slot (round 4): an ARENA — buffers are carved out of a few large slabs that come from the slot's buffer pool and go back
 // to it, so a map build no longer pays ≈ 20 hipMalloc + hipFree pairs (each hipFree also waits for the device) per call,
@@ -346,7 +352,6 @@ struct DeviceBuffers {
   }
 };
 
-
 // What one accumulate call computes; POD so the same code path serves all three problems.
 struct Request {
   int problem;  // 6, 3, 2 (reprojection)
@@ -374,22 +379,71 @@ inline void fill_loss(const nos_loss* loss, T& la, T& lb, T& lc) {
   }
 }
 
-// nos_core.hip
-int pool_alloc(DeviceSlot& slot, size_t bytes, void** ptr, size_t* capacity);
-void pool_release(DeviceSlot& slot, void* ptr, size_t capacity);
-int env_int(const char* name, int dflt);
+// Item parameters of one problem from its request; ds: reprojection follows the dataset's simd_class.
+template <typename T>
+void fill_params(nos::Ndt6Params<T>& P, const Request& rq, const nos_dataset*) {
+  for (int k = 0; k < 9; ++k) P.R[k] = T(rq.R[k]);
+  for (int k = 0; k < 3; ++k) P.t[k] = T(rq.t[k]);
+  fill_loss(&rq.loss, P.la, P.lb, P.lc);
+}
+template <typename T>
+void fill_params(nos::Ndt3Params<T>& P, const Request& rq, const nos_dataset*) {
+  for (int k = 0; k < 4; ++k) P.R2[k] = T(rq.R[k]);
+  for (int k = 0; k < 2; ++k) P.t2[k] = T(rq.t[k]);
+  fill_loss(&rq.loss, P.la, P.lb, P.lc);
+}
+template <typename T>
+void fill_params(nos::ReprojParams<T>& P, const Request& rq, const nos_dataset* ds) {
+  for (int k = 0; k < 9; ++k) P.R[k] = T(rq.R[k]);
+  for (int k = 0; k < 3; ++k) P.t[k] = T(rq.t[k]);
+  P.inv_fx = T(rq.intr[0]);
+  P.inv_fy = T(rq.intr[1]);
+  P.cx = T(rq.intr[2]);
+  P.cy = T(rq.intr[3]);
+  P.min_depth = T(rq.min_depth);
+  nos::set_reproj_rules(P, ds->simd_class != 0);  // per dataset: each problem follows its own simd_class
+  fill_loss(&rq.loss, P.la, P.lb, P.lc);
+}
+
+// Loop settings of one solve.  The one place for the float_schedule rule: the fp32 (SIMD) NDT classes of the reference keep
+// lambda and previous_cost in float, its reprojection class does not.
+inline nos_host::LmSettings make_lm_settings(const nos_lm_options* opt, int simd_class, int kind) {
+  nos_host::LmSettings s;
+  s.max_iterations = opt->max_iterations;
+  s.gradient_tolerance = opt->gradient_tolerance;
+  s.parameter_tolerance = opt->parameter_tolerance;
+  s.float_schedule = (simd_class != 0 && kind != kKindReproj) ? 1 : 0;
+  return s;
+}
+
+// What lm_init_kernel (and the host mirror of the loop state) starts a solve of `ds` from.
+inline nos::LmInitArgs make_lm_init(const nos_dataset* ds, const Request& rq, const nos_lm_options* opt, const double* R, int nR,
+                                    const double* t, int nt) {
+  nos::LmInitArgs init{};
+  for (int k = 0; k < nR; ++k) init.R[k] = R[k];
+  for (int k = 0; k < nt; ++k) init.t[k] = t[k];
+  init.settings = make_lm_settings(opt, ds->simd_class, ds->kind);
+  init.dof = rq.n_out == 28 ? 6 : 3;
+  return init;
+}
+
+// nos_dataset.hip
 size_t elem_size(int dtype);
 int dataset_new(nos_ctx* ctx, int kind, size_t n, int dtype, nos_dataset** out, nos_dataset** made);
 // layout of a dataset's shard: tile size by element type and context settings, then the planes (flat NDT: nos::kNdtStored)
 int dataset_tile_log2(const nos_ctx* ctx, int dtype);
 nos::TiledLayout make_layout(size_t n, int n_fields, int tile_log2, int plane_skew);
 size_t layout_elems(const nos::TiledLayout& L, int n_fields);
-int check_loss(const nos_loss* loss, int* kind_out);
 int zero_pad(int dtype, int n_fields, const nos::TiledLayout& L, void* dst, hipStream_t stream);
 int unpack_records(int dtype, const unsigned char* d_rec, size_t stride, const nos::FieldOffsets& fo, int n_fields,
                    size_t first, size_t count, const nos::TiledLayout& L, void* dst, hipStream_t stream);
+// nos_core.hip
+int check_loss(const nos_loss* loss, int* kind_out);
 int build_request(int problem, const nos_dataset* ds, const double* R, int nR, const double* t, int nt,
                   const double* intr, double min_depth, const nos_loss* loss, Request* rq);
+// mailbox descriptor for the in-launch cross-rank exchange, and the time-out flag the kernels raise in the pinned block
+nos::Mailbox mailbox_of(const nos_ctx* ctx, const DeviceSlot& slot);
+int check_mailbox_error(const nos_ctx* ctx, DeviceSlot& slot);
 // the device-resident loop of one dataset (nos_*_solve)
 int lm_solve(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, double* R, int nR, double* t, int nt,
              nos_lm_report* report);

@@ -24,6 +24,7 @@ struct RegisterCall {
   nos_register_report* reports;
 };
 
+// Not the shared fill_params: a registration has a 3x3 start pose and a loss, no Request and no dataset to take them from.
 template <typename T>
 void fill_loss_params(nos::Ndt6Params<T>& P, const double R[9], const double t[3], const nos_loss* loss) {
   for (int k = 0; k < 9; ++k) P.R[k] = T(R[k]);
@@ -106,11 +107,7 @@ int run_register(const RegisterCall& c, int loss_kind) {
     d.dof = c.dof;
     for (int k = 0; k < 9; ++k) d.R[k] = c.R[9 * i + k];
     for (int k = 0; k < 3; ++k) d.t[k] = c.t[3 * i + k];
-    // what lm_solve hands lm_init_kernel (a matcher-written dataset has simd_class 0)
-    d.settings.max_iterations = c.opt->max_iterations;
-    d.settings.gradient_tolerance = c.opt->gradient_tolerance;
-    d.settings.parameter_tolerance = c.opt->parameter_tolerance;
-    d.settings.float_schedule = 0;
+    d.settings = make_lm_settings(c.opt, 0, kKindNdt);  // as lm_solve; a matcher-written dataset has simd_class 0
   }
   nos::RegisterResult* const d_results = reinterpret_cast<nos::RegisterResult*>(dev_bytes + desc_bytes);
   nos::RegisterRound* const d_log = reinterpret_cast<nos::RegisterRound*>(dev_bytes + desc_bytes + result_bytes);

@@ -47,7 +47,8 @@ def test_default_build_is_not_bloated(core):
     assert all(k["spill"] == 0 and k["scratch"] == 0 for k in core), [k["name"][:120] for k in core if k["spill"] or k["scratch"]]
 
 
-@pytest.mark.parametrize("obj", ["nos_match.o", "nos_mapbuild.o", "nos_mapexact.o", "nos_indexed.o", "nos_pgo.o"])
+@pytest.mark.parametrize("obj", ["nos_match.o", "nos_mapbuild.o", "nos_mapexact.o", "nos_indexed.o", "nos_pgo.o", "nos_dataset.o",
+                                 "nos_comm.o"])
 def test_other_translation_units_report(obj):
     import kernel_resources
     ks = kernel_resources.kernel_resources(os.path.join(CSRC, obj))
