@@ -602,6 +602,33 @@ int nos_ndt3_register_batch(nos_ndt_map* map, nos_scan* const* scans, int32_t n_
                             const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
                             nos_register_report* reports);
 
+/* ---- the same, against the LIVE voxel store ---------------------------
+ * nos_ndt6_register_batch / nos_ndt3_register_batch with a nos_voxel_map in place of the nos_ndt_map: every round of every
+ * problem is matched against the store as it is now, through the key -> slot table the inserts maintain (the matcher of
+ * nos_voxel_map_match), inside the one launch.  Arguments, reports, round log, the failure of a single problem and the
+ * "a rejected call writes nothing" rule are those of nos_ndt*_register_batch.
+ * Contract: problem i ends, bit for bit and at any scan size, with what nos_voxel_map_snapshot followed by
+ * nos_ndt*_register_batch gives it — pose, outer_iter, and per round matches / used / iterations / ok / printed and last
+ * cost — subject to the guard-band caveat of nos_voxel_map_match (a voxel is looked for in its own cell, widened by
+ * resolution / 1024).  It therefore also ends with what pipeline.scan_to_map on the store gives: bit for bit for scans of
+ * ≤ 512 points, to rounding above.
+ * The call is one upload, one launch, one copy back and one synchronisation; nothing is sorted and nothing is allocated in
+ * proportion to the map.  The store is only read: voxels, epoch, generation and stamps stay as they were (the one word of
+ * it the call writes is its internal probe-error flag, cleared before the launch and brought back with the results).
+ * An empty store is not an error: every problem fails alone in round 0 (ok = 0, its pose kept).
+ * Rejected before anything runs: everything nos_ndt*_register_batch rejects, with the same status (a scan of another
+ * context than the store's: NOS_ERR_INVALID_ARGUMENT, as there and as in nos_voxel_map_match); a search ball that spans
+ * more than 9 cells per axis, 2 r / resolution + 2 > 9 (NOS_ERR_UNSUPPORTED, as nos_voxel_map_match); a store an earlier
+ * failure left undefined (NOS_ERR_HIP).  A table probe that runs through the whole table (it cannot at the store's load
+ * factor) makes the call return NOS_ERR_HIP with R, t, reports and round_log unwritten.
+ * Not covered: what nos_ndt*_register_batch does not cover. */
+int nos_voxel_map_register6_batch(nos_voxel_map* map, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
+                                  const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
+                                  nos_register_report* reports);
+int nos_voxel_map_register3_batch(nos_voxel_map* map, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
+                                  const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
+                                  nos_register_report* reports);
+
 /* Test hook: ONE step of the device-resident loop on given sums and a given loop state — the stand-alone step kernel
  * (the same single-lane function every device loop form calls).  dof 6: sums[28], dof 3: sums[10].
  * state[22] = R (9, row-major; planar: R[0..3] = the 2x2 rotation) | t (3) | q w x y z (4) | lambda | previous_cost | cost |

@@ -41,7 +41,7 @@ C_ABI_SYMBOLS = (
     "nos_ndt6_accumulate_async", "nos_ndt3_accumulate_async", "nos_reproj_accumulate_async",
     "nos_ndt6_solve", "nos_ndt3_solve", "nos_reproj_solve",
     "nos_ndt6_solve_batch", "nos_ndt3_solve_batch", "nos_reproj_solve_batch",
-    "nos_ndt6_register_batch", "nos_ndt3_register_batch",
+    "nos_ndt6_register_batch", "nos_ndt3_register_batch", "nos_voxel_map_register6_batch", "nos_voxel_map_register3_batch",
     "nos_ctx_set_launch", "nos_ctx_set_option", "nos_ctx_get_option", "nos_runtime_info", "nos_ctx_comm_rccl_count",
     "nos_ctx_last_kernel", "nos_ctx_profile_begin", "nos_ctx_profile_end", "nos_ndt6_time_kernel", "nos_reproj_time_kernel",
     "nos_ndt3_time_kernel", "nos_status_string", "nos_last_error", "nos_version",
@@ -231,6 +231,9 @@ def _declare(lib):
         ro, rr = ctypes.POINTER(NosRegisterOptions), ctypes.POINTER(NosRegisterReport)
         lib.nos_ndt6_register_batch.argtypes = [vp, c_void_pp, ctypes.c_int32, dp, dp, lp, ro, lmo, rr]
         lib.nos_ndt3_register_batch.argtypes = [vp, c_void_pp, ctypes.c_int32, dp, dp, lp, ro, lmo, rr]
+        if hasattr(lib, "nos_voxel_map_register6_batch"):  # against the live voxel store: absent from builds older still
+            lib.nos_voxel_map_register6_batch.argtypes = [vp, c_void_pp, ctypes.c_int32, dp, dp, lp, ro, lmo, rr]
+            lib.nos_voxel_map_register3_batch.argtypes = [vp, c_void_pp, ctypes.c_int32, dp, dp, lp, ro, lmo, rr]
     lib.nos_ndt6_time_kernel.argtypes = [vp, dp, dp, lp, i, dp, dp]
     lib.nos_ndt3_time_kernel.argtypes = [vp, dp, dp, lp, i, dp, dp]
     lib.nos_reproj_time_kernel.argtypes = [vp, dp, dp, dp, lp, ctypes.c_double, i, dp, dp]

@@ -317,24 +317,33 @@ def _register_call(fn, where, ndt_map, scans, R, t, loss, max_outer_iterations, 
     return R, t, out
 
 
+def _register_entry(ndt_map, dof):
+    """The C entry point of a batched registration by the kind of map: an NdtMap, or a VoxelMap (the live store)."""
+    name = ("nos_voxel_map_register%d_batch" if isinstance(ndt_map, VoxelMap) else "nos_ndt%d_register_batch") % dof
+    return getattr(hip_lib(), name), name  # a library without the symbol: AttributeError, no other route is tried
+
+
 def register6_batch(ndt_map, scans, R, t, loss, max_outer_iterations=10, keep_multiple=None, max_neighbors=2, dtype="f64",
                     max_iterations=40, gradient_tolerance=1e-6, parameter_tolerance=1e-6):
     """B scan-to-map registrations against one map in one launch (nos_ndt6_register_batch): every round's matching, tail
     drop (keep_multiple), LM solve and stopping test run on the device.  scans: B Scans of the map's context (the same one
     may repeat: multi-start); R [B, 9] or [B, 3, 3], t [B, 3] start poses.  Row i equals pipeline.scan_to_map from
-    (R[i], t[i]).  Returns (R [B, 9], t [B, 3], [B reports {outer_iter, rounds: [per-round dicts], ok}])."""
-    return _register_call(hip_lib().nos_ndt6_register_batch, "nos_ndt6_register_batch", ndt_map, scans, R, t, loss,
-                          max_outer_iterations, keep_multiple, max_neighbors, dtype, max_iterations, gradient_tolerance,
-                          parameter_tolerance)
+    (R[i], t[i]).  Returns (R [B, 9], t [B, 3], [B reports {outer_iter, rounds: [per-round dicts], ok}]).
+    ndt_map: an NdtMap, or a VoxelMap — every round is then matched against the live store inside the same launch
+    (nos_voxel_map_register6_batch): no snapshot, and row i is bit for bit the row of the call on its snapshot()."""
+    fn, name = _register_entry(ndt_map, 6)
+    return _register_call(fn, name, ndt_map, scans, R, t, loss, max_outer_iterations, keep_multiple, max_neighbors, dtype,
+                          max_iterations, gradient_tolerance, parameter_tolerance)
 
 
 def register3_batch(ndt_map, scans, R, t, loss, max_outer_iterations=10, keep_multiple=None, max_neighbors=2, dtype="f64",
                     max_iterations=40, gradient_tolerance=1e-6, parameter_tolerance=1e-6):
-    """Planar form (nos_ndt3_register_batch): R [B, 9], t [B, 3] are full 3-D poses; every round solves for the top-left
-    2x2 and (x, y) and writes only those back, as the 3-DoF drop-in class does."""
-    return _register_call(hip_lib().nos_ndt3_register_batch, "nos_ndt3_register_batch", ndt_map, scans, R, t, loss,
-                          max_outer_iterations, keep_multiple, max_neighbors, dtype, max_iterations, gradient_tolerance,
-                          parameter_tolerance)
+    """Planar form (nos_ndt3_register_batch; for a VoxelMap nos_voxel_map_register3_batch): R [B, 9], t [B, 3] are full
+    3-D poses; every round solves for the top-left 2x2 and (x, y) and writes only those back, as the 3-DoF drop-in class
+    does."""
+    fn, name = _register_entry(ndt_map, 3)
+    return _register_call(fn, name, ndt_map, scans, R, t, loss, max_outer_iterations, keep_multiple, max_neighbors, dtype,
+                          max_iterations, gradient_tolerance, parameter_tolerance)
 
 
 class _Dataset:

@@ -14,8 +14,9 @@ namespace nos {
 // pipeline.scan_to_map runs OptimizePoseAnalytic's outer loop (MDM/tests/simple_optimization_test.cc:474-503) from the
 // host: per round a match launch, an optional tail-drop launch, a solve launch and a host synchronisation.  Here workgroup b
 // runs all rounds of problem b inside one launch.  Per round:
-//   1. match: the lanes stride over scan b's points, each through match_point (match_kernel's body) into the problem's
-//      scratch dataset — the layout nos_ndt_match gives a dataset of 2n slots of that element type;
+//   1. match: the lanes stride over scan b's points, each through match_point (match_kernel's body; against a live voxel
+//      store: voxel_match_point, voxel_match_kernel's body, assemble_register_live.hpp) into the problem's scratch
+//      dataset — the layout nos_ndt_match gives a dataset of 2n slots of that element type;
 //   2. count the matches (integer workgroup sum) and, with keep_multiple = k > 0, clear the last matches % k non-empty
 //      records (drop_last_records, drop_last_matches_kernel's body);
 //   3. make the loop state with the LmInit6 / LmInit3 call of the lone solve and run single_block_loop, the loop of
@@ -41,7 +42,7 @@ struct RegisterResult {
   int outer_iter;     // scan_to_map's `outer`: the round that met the stopping test, max_outer if none did, the failed round
   int rounds;         // rounds run (log entries written), a failed one included
   int ok;             // 0: a round's solve failed (scan_to_map raises there)
-  int pad;
+  int probe_error;    // live store only: non-zero when a table probe ran through the whole table (the call then fails)
 };
 
 // One round of one problem: the layout of nos_register_round (include/nos.h).
@@ -95,12 +96,24 @@ __device__ __forceinline__ bool pose_converged(const double R[9], const double t
   return sqrt(nn) < 1e-5 && sqrt(h > 0.0 ? h : 0.0) < 1e-5;
 }
 
-template <typename Problem, typename T, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void register_batch_kernel(MapView map,
-                                                              const RegisterDesc<typename Problem::Params>* __restrict__ descs,
-                                                              RegisterResult* __restrict__ results,
-                                                              RegisterRound* __restrict__ round_log, int max_outer,
-                                                              int max_neighbors, int keep_multiple) {
+// The matcher of one scan point by the kind of map: the only line of a registration that depends on it.  This one is the
+// snapshot's (match_point); the live store's overload is in assemble_register_live.hpp.  error: unused here.
+template <typename T>
+__device__ __forceinline__ int register_match_point(const MapView& map, const double* __restrict__ px,
+                                                    const double* __restrict__ py, const double* __restrict__ pz, uint64_t i,
+                                                    const PosePod& pose, int max_neighbors, const TiledLayout& L,
+                                                    T* __restrict__ dst, unsigned int*) {
+  return match_point<T>(map, px, py, pz, i, pose, max_neighbors, L, dst);
+}
+
+// Problem blockIdx.x of a batched registration, all rounds: the body of register_batch_kernel (below) and of
+// register_live_kernel (assemble_register_live.hpp).  View: MapView or VoxelMatchView; error: what the view's matcher
+// reports a failed table probe through (the live store's kInfoProbeError word; null for a snapshot).
+template <typename Problem, typename T, int BLOCK, typename View>
+__device__ __forceinline__ void register_problem(const View& map, unsigned int* __restrict__ error,
+                                                 const RegisterDesc<typename Problem::Params>* __restrict__ descs,
+                                                 RegisterResult* __restrict__ results, RegisterRound* __restrict__ round_log,
+                                                 int max_outer, int max_neighbors, int keep_multiple) {
   constexpr int kOut = Problem::kOut;
   constexpr int kWaves = BLOCK / kWave;
   const RegisterDesc<typename Problem::Params>& d = descs[blockIdx.x];
@@ -134,7 +147,7 @@ __global__ __launch_bounds__(BLOCK) void register_batch_kernel(MapView map,
     // 1. match
     int found = 0;
     for (uint64_t i = threadIdx.x; i < d.n_points; i += BLOCK)
-      found += match_point<T>(map, px, py, pz, i, pose, max_neighbors, L, data);
+      found += register_match_point<T>(map, px, py, pz, i, pose, max_neighbors, L, data, error);
     // 2. count: wave sums, then every lane adds the kWaves partials in one order
     unsigned long long s = (unsigned long long)found;
 #pragma unroll
@@ -234,8 +247,19 @@ __global__ __launch_bounds__(BLOCK) void register_batch_kernel(MapView map,
     r.outer_iter = outer;
     r.rounds = rounds;
     r.ok = ok;
-    r.pad = 0;
+    // the probe-error word as this workgroup sees it after its last round: a probe of one of ITS lanes that failed is in
+    // it (every round ends behind a barrier), so the host learns of every failure from the copy that brings the results
+    r.probe_error = error != nullptr ? int(__hip_atomic_load(error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 0;
   }
+}
+
+template <typename Problem, typename T, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void register_batch_kernel(MapView map,
+                                                              const RegisterDesc<typename Problem::Params>* __restrict__ descs,
+                                                              RegisterResult* __restrict__ results,
+                                                              RegisterRound* __restrict__ round_log, int max_outer,
+                                                              int max_neighbors, int keep_multiple) {
+  register_problem<Problem, T, BLOCK>(map, nullptr, descs, results, round_log, max_outer, max_neighbors, keep_multiple);
 }
 
 }  // namespace nos

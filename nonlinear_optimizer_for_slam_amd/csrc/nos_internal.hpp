@@ -30,6 +30,7 @@
 #include "../../include/nos.h"
 #include "assemble_kernels.hpp"
 #include "match_kernels.hpp"
+#include "voxelmatch_kernels.hpp"
 
 namespace nosd {
 
@@ -454,6 +455,26 @@ int map_create_device(nos_ctx* ctx, size_t n_voxels, const double* d_means, cons
 // build's own kernel, so a segment's nine sums are the same bits from either)
 hipError_t launch_voxel_sums(const double* d_records, const uint32_t* sorted_idx, const uint32_t* seg_offset,
                              const uint32_t* seg_count, uint32_t n_voxels, double* acc_out, hipStream_t stream);
+// nos_voxelregister.hip: a batched registration against the live voxel store, for the entry points of nos_voxelmap.hip
+// (which own struct nos_voxel_map).  store == NULL: the map argument was NULL.
+struct LiveStore {
+  nos_ctx* ctx;
+  nos::VoxelMatchView view;
+  unsigned int* d_probe_error;  // the store's kInfoProbeError word
+  double span;                  // cells the search ball spans per axis (check_match_span)
+  bool broken;                  // an earlier failure left the store undefined
+};
+// The live matcher visits at most kVoxelMatchMaxSpan cells per axis: span = 2 r / resolution + 2 must not exceed it.
+inline int check_match_span(double span) {
+  if (span > double(nos::kVoxelMatchMaxSpan))
+    return fail(NOS_ERR_UNSUPPORTED,
+                "the search ball spans more than %d voxel cells per axis (2 r / resolution + 2 = %g): match against a snapshot",
+                nos::kVoxelMatchMaxSpan, span);
+  return NOS_OK;
+}
+int register_live(int dof, const LiveStore* store, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
+                  const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
+                  nos_register_report* reports);
 // nos_indexed.hip
 int launch_indexed(const nos_dataset* ds, const Shard& sh, const Request& rq, double* partials,
                    const nos::FusedFinal& fin, hipStream_t stream, int* rows_out);

@@ -3,207 +3,31 @@
 // B scan-to-map registrations against one map in ONE launch, one workgroup each (nos::register_batch_kernel,
 // assemble_register.hpp): every round's matching, tail drop, LM loop and stopping test run on the device.  Problem i ends
 // with what pipeline.scan_to_map gives scans[i].
-#include "nos_internal.hpp"
-#include "assemble_register.hpp"
+#include "register_host.hpp"
 
 namespace nosd {
 namespace {
 
-constexpr int kRegisterBlock = 512;  // the single-workgroup solve's block: same chunks, same reduction order
-
-struct RegisterCall {
-  int dof;
-  nos_ndt_map* map;
-  nos_scan* const* scans;
-  int n;
-  double* R;  // [n][9], in-out
-  double* t;  // [n][3], in-out
-  const nos_loss* loss;
-  const nos_register_options* ropt;
-  const nos_lm_options* opt;
-  nos_register_report* reports;
+struct SnapshotLauncher {
+  const nos::MapView& map;
+  static constexpr bool kTallyLaunch = false;
+  hipError_t prepare(hipStream_t) const { return hipSuccess; }
+  template <typename Problem, typename T>
+  const void* launch(uint32_t n_blocks, const nos::RegisterDesc<typename Problem::Params>* d_descs,
+                     nos::RegisterResult* d_results, nos::RegisterRound* d_log, const nos_register_options* ropt,
+                     hipStream_t stream) const {
+    const auto kernel = nos::register_batch_kernel<Problem, T, kRegisterBlock>;
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kRegisterBlock), 0, stream, map, d_descs, d_results, d_log,
+                       ropt->max_outer_iterations, ropt->max_neighbors, ropt->keep_multiple);
+    return reinterpret_cast<const void*>(kernel);
+  }
 };
 
-// Not the shared fill_params: a registration has a 3x3 start pose and a loss, no Request and no dataset to take them from.
-template <typename T>
-void fill_loss_params(nos::Ndt6Params<T>& P, const double R[9], const double t[3], const nos_loss* loss) {
-  for (int k = 0; k < 9; ++k) P.R[k] = T(R[k]);
-  for (int k = 0; k < 3; ++k) P.t[k] = T(t[k]);
-  fill_loss(loss, P.la, P.lb, P.lc);
-}
-template <typename T>
-void fill_loss_params(nos::Ndt3Params<T>& P, const double R[9], const double t[3], const nos_loss* loss) {
-  const double R2[4] = {R[0], R[1], R[3], R[4]};
-  for (int k = 0; k < 4; ++k) P.R2[k] = T(R2[k]);
-  for (int k = 0; k < 2; ++k) P.t2[k] = T(t[k]);
-  fill_loss(loss, P.la, P.lb, P.lc);
-}
-
-template <typename Problem, typename T>
-int launch_register_kernel(uint32_t n_blocks, const nos::MapView& map, const void* d_descs, nos::RegisterResult* d_results,
-                           nos::RegisterRound* d_log, const nos_register_options* ropt, hipStream_t stream,
-                           const void** kernel_out) {
-  const auto kernel = nos::register_batch_kernel<Problem, T, kRegisterBlock>;
-  *kernel_out = reinterpret_cast<const void*>(kernel);
-  hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kRegisterBlock), 0, stream, map,
-                     static_cast<const nos::RegisterDesc<typename Problem::Params>*>(d_descs), d_results, d_log,
-                     ropt->max_outer_iterations, ropt->max_neighbors, ropt->keep_multiple);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(NOS_ERR_HIP, "batched registration launch failed: %s", hipGetErrorString(e));
-  return NOS_OK;
-}
-
-// Descriptors up through pinned memory, one pooled device block for descriptors, results, round log and every problem's
-// scratch dataset, one launch, results and log down in one copy, one synchronisation, then the caller's arrays.
-template <template <typename, int> class ProblemT, typename T>
-int run_register(const RegisterCall& c, int loss_kind) {
-  using Desc = nos::RegisterDesc<typename ProblemT<T, nos::kLossNone>::Params>;
-  nos_ctx* ctx = c.map->ctx;
-  DeviceSlot& slot = ctx->slots[0];
-  hipStream_t stream = slot.stream;
-  const size_t B = size_t(c.n);
-  const int max_outer = c.ropt->max_outer_iterations;
-  auto round_up = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t desc_bytes = round_up(B * sizeof(Desc));
-  const size_t result_bytes = round_up(B * sizeof(nos::RegisterResult));
-  const size_t log_bytes = round_up(B * size_t(max_outer) * sizeof(nos::RegisterRound));
-  const size_t pinned_total = desc_bytes + result_bytes + log_bytes;
-  // scratch datasets: the layout nos_ndt_match gives a dataset of 2n slots of this element type
-  const int tile_log2 = dataset_tile_log2(ctx, c.ropt->dtype);
-  if (tile_log2 != 0 && (tile_log2 < 10 || tile_log2 > 24)) return fail(NOS_ERR_INVALID_ARGUMENT, "tile_log2 out of range");
-  std::vector<nos::TiledLayout> layouts(B);
-  std::vector<size_t> offsets(B);
-  size_t scratch_bytes = 0;
-  for (size_t i = 0; i < B; ++i) {
-    layouts[i] = make_layout(2 * c.scans[i]->n, nos::kNdtStored, tile_log2, ctx->settings.plane_skew);
-    offsets[i] = scratch_bytes;
-    scratch_bytes += round_up(layout_elems(layouts[i], nos::kNdtStored) * sizeof(T));
-  }
-
-  NOS_HIP_CHECK(hipSetDevice(slot.device));
-  if (slot.batch_pinned_bytes < pinned_total) {  // grows only; freed with the context
-    if (slot.batch_pinned != nullptr) (void)hipHostFree(slot.batch_pinned);
-    slot.batch_pinned = nullptr;
-    slot.batch_pinned_bytes = 0;
-    NOS_HIP_CHECK(hipHostMalloc(&slot.batch_pinned, pinned_total, hipHostMallocDefault));
-    slot.batch_pinned_bytes = pinned_total;
-  }
-  void* dev = nullptr;
-  size_t dev_capacity = 0;
-  int rc = pool_alloc(slot, pinned_total + scratch_bytes, &dev, &dev_capacity);
-  if (rc != NOS_OK) return rc;
-  unsigned char* const dev_bytes = static_cast<unsigned char*>(dev);
-  unsigned char* const scratch = dev_bytes + pinned_total;
-  unsigned char* const pinned = static_cast<unsigned char*>(slot.batch_pinned);
-  for (size_t i = 0; i < B; ++i) {
-    const nos_scan* scan = c.scans[i];
-    Desc& d = *new (pinned + i * sizeof(Desc)) Desc{};
-    d.L = layouts[i];
-    d.L.base = scratch + offsets[i];
-    fill_loss_params(d.P, c.R + 9 * i, c.t + 3 * i, c.loss);
-    d.points = scan->d_planes;
-    d.n_points = scan->n;
-    d.n_chunks = uint32_t((std::max<uint64_t>(d.L.n, 1) + kRegisterBlock - 1) / kRegisterBlock);
-    d.dof = c.dof;
-    for (int k = 0; k < 9; ++k) d.R[k] = c.R[9 * i + k];
-    for (int k = 0; k < 3; ++k) d.t[k] = c.t[3 * i + k];
-    d.settings = make_lm_settings(c.opt, 0, kKindNdt);  // as lm_solve; a matcher-written dataset has simd_class 0
-  }
-  nos::RegisterResult* const d_results = reinterpret_cast<nos::RegisterResult*>(dev_bytes + desc_bytes);
-  nos::RegisterRound* const d_log = reinterpret_cast<nos::RegisterRound*>(dev_bytes + desc_bytes + result_bytes);
-  const void* kernel = nullptr;
-  hipError_t e = hipMemcpyAsync(dev, pinned, desc_bytes, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) {
-    const nos::MapView& map = c.map->view;
-    const uint32_t n_blocks = uint32_t(B);
-    switch (loss_kind) {  // one loss for the whole call
-      case NOS_LOSS_NONE:
-        rc = launch_register_kernel<ProblemT<T, nos::kLossNone>, T>(n_blocks, map, dev, d_results, d_log, c.ropt, stream, &kernel);
-        break;
-      case NOS_LOSS_EXPONENTIAL:
-        rc = launch_register_kernel<ProblemT<T, nos::kLossExponential>, T>(n_blocks, map, dev, d_results, d_log, c.ropt, stream,
-                                                                           &kernel);
-        break;
-      default:
-        rc = launch_register_kernel<ProblemT<T, nos::kLossHuber>, T>(n_blocks, map, dev, d_results, d_log, c.ropt, stream,
-                                                                     &kernel);
-        break;
-    }
-    if (rc == NOS_OK) {
-      slot.last_kernel = kernel;
-      e = hipMemcpyAsync(pinned + desc_bytes, dev_bytes + desc_bytes, result_bytes + log_bytes, hipMemcpyDeviceToHost, stream);
-    }
-  }
-  const hipError_t es = hipStreamSynchronize(stream);  // before the buffer goes back to the pool, after a failure too
-  pool_release(slot, dev, dev_capacity);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess)
-    return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "batched registration: %s",
-                hipGetErrorString(e));
-  if (rc != NOS_OK) return rc;
-
-  const nos::RegisterResult* const results = reinterpret_cast<const nos::RegisterResult*>(pinned + desc_bytes);
-  const nos::RegisterRound* const log = reinterpret_cast<const nos::RegisterRound*>(pinned + desc_bytes + result_bytes);
-  static_assert(sizeof(nos::RegisterRound) == sizeof(nos_register_round), "round log entry layout");
-  for (size_t i = 0; i < B; ++i) {
-    const nos::RegisterResult& r = results[i];
-    for (int k = 0; k < 9; ++k) c.R[9 * i + k] = r.R[k];
-    for (int k = 0; k < 3; ++k) c.t[3 * i + k] = r.t[k];
-    nos_register_report& rep = c.reports[i];
-    rep.outer_iter = r.outer_iter;
-    rep.rounds = r.rounds;
-    rep.ok = r.ok;
-    rep.pad = 0;
-    if (c.ropt->round_log != nullptr) {
-      nos_register_round* row = c.ropt->round_log + i * size_t(max_outer);
-      for (int k = 0; k < max_outer; ++k) {
-        nos_register_round& o = row[k];
-        if (k < r.rounds) {
-          const nos::RegisterRound& g = log[i * size_t(max_outer) + size_t(k)];
-          o.matches = g.matches;
-          o.used = g.used;
-          o.iterations = g.iterations;
-          o.ok = g.ok;
-          o.printed_cost = g.printed_cost;
-          o.last_cost = g.last_cost;
-        } else {
-          memset(&o, 0, sizeof o);
-        }
-      }
-    }
-  }
-  return NOS_OK;
-}
-
-// Validation first (nothing is launched and nothing written before every check has passed), then the launch.
-int register_batch(const RegisterCall& c) {
-  if (c.n < 0) return fail(NOS_ERR_INVALID_ARGUMENT, "n_problems < 0");
-  if (c.n == 0) return NOS_OK;
-  if (!c.map || !c.scans || !c.R || !c.t || !c.ropt || !c.opt || !c.reports) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL array");
-  nos_ctx* ctx = c.map->ctx;
-  CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  for (int i = 0; i < c.n; ++i) {
-    if (c.scans[i] == nullptr) return fail(NOS_ERR_INVALID_ARGUMENT, "scan %d is NULL", i);
-    if (c.scans[i]->ctx != ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "scan %d belongs to another context than the map", i);
-  }
-  const nos_register_options& ro = *c.ropt;
-  if (ro.max_outer_iterations < 1) return fail(NOS_ERR_INVALID_ARGUMENT, "max_outer_iterations < 1");
-  if (ro.keep_multiple < 0) return fail(NOS_ERR_INVALID_ARGUMENT, "keep_multiple < 0");
-  if (ro.dtype != NOS_F64 && ro.dtype != NOS_F32) return fail(NOS_ERR_INVALID_ARGUMENT, "unknown dtype %d", ro.dtype);
-  if (c.opt->max_iterations < 0) return fail(NOS_ERR_INVALID_ARGUMENT, "max_iterations < 0");
-  if (c.opt->cost_history != nullptr)
-    return fail(NOS_ERR_INVALID_ARGUMENT, "cost_history is not supported by batched registration (rounds: round_log)");
-  int loss_kind = 0;
-  const int rc = check_loss(c.loss, &loss_kind);
-  if (rc != NOS_OK) return rc;
-  if (ro.max_neighbors < 1 || ro.max_neighbors > 2) return fail(NOS_ERR_UNSUPPORTED, "max_neighbors must be 1 or 2");
-  if (ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "batched registration needs a single-device context");
-  if (ctx->comm != nullptr || ctx->shm_dev != nullptr)
-    return fail(NOS_ERR_UNSUPPORTED, "batched registration is process-local: the context has a communicator");
-  const bool f64 = ro.dtype == NOS_F64;
-  if (c.dof == 6)
-    return f64 ? run_register<nos::Ndt6Problem, double>(c, loss_kind) : run_register<nos::Ndt6Problem, float>(c, loss_kind);
-  return f64 ? run_register<nos::Ndt3Problem, double>(c, loss_kind) : run_register<nos::Ndt3Problem, float>(c, loss_kind);
+int register_snapshot(int dof, nos_ndt_map* map, nos_scan* const* scans, int32_t n, double* R, double* t, const nos_loss* loss,
+                      const nos_register_options* ropt, const nos_lm_options* opt, nos_register_report* reports) {
+  static const nos::MapView no_map{};  // never launched with: a NULL map is rejected first
+  return register_batch({dof, map ? map->ctx : nullptr, scans, n, R, t, loss, ropt, opt, reports}, [] { return NOS_OK; },
+                        SnapshotLauncher{map ? map->view : no_map});
 }
 
 }  // namespace
@@ -214,13 +38,13 @@ extern "C" {
 int nos_ndt6_register_batch(nos_ndt_map* map, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
                             const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
                             nos_register_report* reports) {
-  return nosd::register_batch({6, map, scans, n_problems, R, t, loss, ropt, options, reports});
+  return nosd::register_snapshot(6, map, scans, n_problems, R, t, loss, ropt, options, reports);
 }
 
 int nos_ndt3_register_batch(nos_ndt_map* map, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
                             const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
                             nos_register_report* reports) {
-  return nosd::register_batch({3, map, scans, n_problems, R, t, loss, ropt, options, reports});
+  return nosd::register_snapshot(3, map, scans, n_problems, R, t, loss, ropt, options, reports);
 }
 
 }  // extern "C"

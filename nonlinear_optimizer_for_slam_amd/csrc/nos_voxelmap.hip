@@ -305,6 +305,33 @@ int store_prune(nos_voxel_map* vm, const nos::VoxelKeepRule& rule, size_t* n_rem
   return NOS_OK;
 }
 
+// The store as the live matcher reads it, and the cells its search ball spans per axis.
+nos::VoxelMatchView match_view(const nos_voxel_map* vm) {
+  const nos::VoxelStoreView& v = vm->view;
+  nos::VoxelMatchView view{};
+  view.table_key = v.table_key;
+  view.table_slot = v.table_slot;
+  view.mean = v.mean;
+  view.sqrt_info = v.sqrt_info;
+  view.valid = v.valid;
+  view.table_mask = v.table_mask;
+  view.inv_res = 1.0 / vm->voxel_resolution;  // what voxel_points_kernel is handed
+  view.reach = std::sqrt(vm->search_radius_sq) + nos::kVoxelMatchGuard * vm->voxel_resolution;
+  view.radius_sq = vm->search_radius_sq;
+  return view;
+}
+
+double match_span(const nos_voxel_map* vm) { return 2.0 * std::sqrt(vm->search_radius_sq) / vm->voxel_resolution + 2.0; }
+
+int voxel_map_register(int dof, nos_voxel_map* vm, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
+                       const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
+                       nos_register_report* reports) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!vm) return register_live(dof, nullptr, scans, n_problems, R, t, loss, ropt, options, reports);
+  const LiveStore store{vm->ctx, match_view(vm), vm->d_info + nos::kInfoProbeError, match_span(vm), vm->broken};
+  return register_live(dof, &store, scans, n_problems, R, t, loss, ropt, options, reports);
+}
+
 }  // namespace
 
 extern "C" {
@@ -429,11 +456,8 @@ int nos_voxel_map_match(nos_voxel_map* vm, nos_scan* scan, const double R[9], co
   if (max_neighbors < 1 || max_neighbors > 2) return fail(NOS_ERR_UNSUPPORTED, "max_neighbors must be 1 or 2");
   nos_ctx* ctx = vm->ctx;
   if (ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "matching against a voxel store needs a single-device context");
-  const double radius = std::sqrt(vm->search_radius_sq);
-  if (2.0 * radius / vm->voxel_resolution + 2.0 > double(nos::kVoxelMatchMaxSpan))
-    return fail(NOS_ERR_UNSUPPORTED,
-                "the search ball spans more than %d voxel cells per axis (2 r / resolution + 2 = %g): match against a snapshot",
-                nos::kVoxelMatchMaxSpan, 2.0 * radius / vm->voxel_resolution + 2.0);
+  const int rc_span = check_match_span(match_span(vm));
+  if (rc_span != NOS_OK) return rc_span;
   if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
   nos_dataset* made = nullptr;
   nos_dataset* ds = nullptr;
@@ -445,17 +469,7 @@ int nos_voxel_map_match(nos_voxel_map* vm, nos_scan* scan, const double R[9], co
   nos::PosePod pose;
   for (int k = 0; k < 9; ++k) pose.R[k] = R[k];
   for (int k = 0; k < 3; ++k) pose.t[k] = t[k];
-  const nos::VoxelStoreView& v = vm->view;
-  nos::VoxelMatchView view{};
-  view.table_key = v.table_key;
-  view.table_slot = v.table_slot;
-  view.mean = v.mean;
-  view.sqrt_info = v.sqrt_info;
-  view.valid = v.valid;
-  view.table_mask = v.table_mask;
-  view.inv_res = 1.0 / vm->voxel_resolution;  // what voxel_points_kernel is handed
-  view.reach = radius + nos::kVoxelMatchGuard * vm->voxel_resolution;
-  view.radius_sq = vm->search_radius_sq;
+  const nos::VoxelMatchView view = match_view(vm);
   unsigned long long* d_count = reinterpret_cast<unsigned long long*>(vm->d_info + nos::kInfoMatches);
   static_assert(nos::kInfoMatches % 2 == 0 && nos::kInfoMatches + 2 <= nos::kInfoWords, "info layout");
   long launches = 0;
@@ -501,6 +515,18 @@ int nos_voxel_map_match(nos_voxel_map* vm, nos_scan* scan, const double R[9], co
   if (n_matches) *n_matches = size_t(count);
   *out_ds = ds;
   return NOS_OK;
+}
+
+int nos_voxel_map_register6_batch(nos_voxel_map* vm, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
+                                  const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
+                                  nos_register_report* reports) {
+  return voxel_map_register(6, vm, scans, n_problems, R, t, loss, ropt, options, reports);
+}
+
+int nos_voxel_map_register3_batch(nos_voxel_map* vm, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
+                                  const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
+                                  nos_register_report* reports) {
+  return voxel_map_register(3, vm, scans, n_problems, R, t, loss, ropt, options, reports);
 }
 
 int nos_voxel_map_stats(nos_voxel_map* vm, nos_map_stats** out_stats) {

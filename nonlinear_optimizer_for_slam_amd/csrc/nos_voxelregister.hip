@@ -1,0 +1,44 @@
+// nos_voxelregister.hip — nos_voxel_map_register6_batch / nos_voxel_map_register3_batch (C ABI of include/nos.h; the entry
+// points themselves are in nos_voxelmap.hip, which owns the store).
+//
+// nos_ndt*_register_batch (nos_register.hip) against the LIVE voxel store: B registrations in ONE launch, one workgroup
+// each (nos::register_live_kernel, assemble_register_live.hpp), every round matched through the table the inserts
+// maintain — no snapshot, nothing sorted, nothing allocated in proportion to the map.
+#include "register_host.hpp"
+#include "assemble_register_live.hpp"
+
+namespace nosd {
+namespace {
+
+struct LiveLauncher {
+  const LiveStore& store;
+  static constexpr bool kTallyLaunch = true;
+  hipError_t prepare(hipStream_t stream) const { return hipMemsetAsync(store.d_probe_error, 0, sizeof(unsigned int), stream); }
+  template <typename Problem, typename T>
+  const void* launch(uint32_t n_blocks, const nos::RegisterDesc<typename Problem::Params>* d_descs,
+                     nos::RegisterResult* d_results, nos::RegisterRound* d_log, const nos_register_options* ropt,
+                     hipStream_t stream) const {
+    const auto kernel = nos::register_live_kernel<Problem, T, kRegisterBlock>;
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kRegisterBlock), 0, stream, store.view, store.d_probe_error, d_descs,
+                       d_results, d_log, ropt->max_outer_iterations, ropt->max_neighbors, ropt->keep_multiple);
+    return reinterpret_cast<const void*>(kernel);
+  }
+};
+
+}  // namespace
+
+int register_live(int dof, const LiveStore* store, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
+                  const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
+                  nos_register_report* reports) {
+  static const LiveStore no_store{};  // never launched with: a NULL map is rejected first
+  const LiveStore& s = store ? *store : no_store;
+  auto more_checks = [&s] {  // what nos_voxel_map_match rejects, in its order
+    const int rc = check_match_span(s.span);
+    if (rc != NOS_OK) return rc;
+    if (s.broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+    return int(NOS_OK);
+  };
+  return register_batch({dof, s.ctx, scans, n_problems, R, t, loss, ropt, options, reports}, more_checks, LiveLauncher{s});
+}
+
+}  // namespace nosd

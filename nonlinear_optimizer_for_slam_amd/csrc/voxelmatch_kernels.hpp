@@ -15,7 +15,7 @@
 // mean can pass the radius test.  That is the guard band `g` (kVoxelMatchGuard of a cell edge; the argument is in
 // DESIGN.md §15): a mean lies in its own cell only up to the rounding of the sums and of the cell assignment.
 //
-// Memory side: per (x, 3 x 3 block of y, z) step a lane issues NINE independent probes — key and slot of the first
+// Memory side: per (x, 3 x 3 block of y, z) step a lane of voxel_match_kernel issues NINE independent probes — key and slot of the first
 // table entry of every cell are loaded together, then valid flag and mean of every hit — so a 27-cell search is three
 // rounds of dependent loads, not 27; a collision (the table is at most half full) is resolved by a bounded loop
 // afterwards.  Consecutive z cells differ in the lowest key bits only, but the hash scatters them: what makes the lanes of
@@ -25,7 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "voxelmap_kernels.hpp"
+#include "match_kernels.hpp"
 
 namespace nos {
 
@@ -45,6 +45,104 @@ struct VoxelMatchView {
   double radius_sq;
 };
 
+// Scan point i (i < n_points) warped by `pose` and matched against the live store: writes slots 2i and 2i + 1 of the
+// dataset and returns the number of real matches among them (0-2) — match_point (match_kernels.hpp) on the store's table.
+// error: the store's kInfoProbeError word.  voxel_match_kernel (one thread per point) and register_live_kernel
+// (assemble_register_live.hpp, the lanes of one workgroup striding over a scan) both call this, so their records are the
+// same bits.
+template <typename DST>
+__device__ __forceinline__ int voxel_match_point(const VoxelMatchView& map, const double* __restrict__ px,
+                                                 const double* __restrict__ py, const double* __restrict__ pz, uint64_t i,
+                                                 const PosePod& pose, int max_neighbors, const TiledLayout& L,
+                                                 DST* __restrict__ dst, unsigned int* __restrict__ error) {
+  constexpr int kProbes = 9;  // the 3 x 3 block of (y, z) cells probed together per step
+  const double x = px[i], y = py[i], z = pz[i];
+  double q[3];
+  warp_point(pose, x, y, z, q[0], q[1], q[2]);
+  // cells floor((q - r - g) inv_res) … floor((q + r + g) inv_res) per axis, clamped to the addressable grid
+  // [-2^20, 2^20) that voxel_points_kernel admits — no voxel lives outside it, and pack_cell would fold a cell beyond
+  // it onto a real key.  A point that is not finite, or whose range misses the grid altogether, visits no cell.
+  int64_t c0[3];
+  int span[3];
+  bool reachable = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double lim = double(1 << 20);
+    const double lo = fmax(floor((q[k] - map.reach) * map.inv_res), -lim);
+    const double hi = fmin(floor((q[k] + map.reach) * map.inv_res), lim - 1.0);
+    reachable = reachable && (lo <= hi);  // a NaN fails (fmax / fmin would drop it: test the point itself too)
+    reachable = reachable && (q[k] == q[k]);
+    c0[k] = reachable ? int64_t(lo) : 0;
+    const int n = reachable ? int(hi - lo) + 1 : 0;
+    span[k] = n < kVoxelMatchMaxSpan ? n : kVoxelMatchMaxSpan;
+  }
+  if (!reachable) span[0] = 0;
+  TwoNearest best;
+  best.init();
+  for (int ix = 0; ix < span[0]; ++ix)
+    for (int by = 0; by < span[1]; by += 3)
+      for (int bz = 0; bz < span[2]; bz += 3) {
+        uint64_t key[kProbes];
+        uint32_t h[kProbes], slot[kProbes];
+        unsigned long long seen[kProbes];
+        bool on[kProbes];
+        // round 1: the first table entry of every cell of the block — key and slot loaded together, nothing depends on
+        // a compare
+#pragma unroll
+        for (int u = 0; u < kProbes; ++u) {
+          const int dy = by + u / 3, dz = bz + u % 3;
+          on[u] = dy < span[1] && dz < span[2];
+          key[u] = pack_cell(c0[0] + ix, c0[1] + dy, c0[2] + dz);
+          h[u] = hash_cell(key[u]) & map.table_mask;
+        }
+#pragma unroll
+        for (int u = 0; u < kProbes; ++u) {
+          seen[u] = map.table_key[h[u]];
+          slot[u] = map.table_slot[h[u]];
+        }
+        // collisions: voxel_table_find's probe sequence from the second entry on, bounded by the table size
+#pragma unroll
+        for (int u = 0; u < kProbes; ++u) {
+          bool hit = on[u] && seen[u] == key[u];
+          if (on[u] && !hit && seen[u] != kEmptyCell) {
+            uint32_t hh = h[u];
+            bool ended = false;
+            for (uint32_t probe = 1; probe <= map.table_mask; ++probe) {
+              hh = (hh + 1) & map.table_mask;
+              const unsigned long long k = map.table_key[hh];
+              if (k == key[u]) {
+                slot[u] = map.table_slot[hh];
+                hit = ended = true;
+                break;
+              }
+              if (k == kEmptyCell) {
+                ended = true;
+                break;
+              }
+            }
+            if (!ended) atomicOr(error, 1u);
+          }
+          on[u] = hit;
+          slot[u] = hit ? slot[u] : 0u;  // slot 0 exists in every store (capacity >= 16): a miss reads it and drops it
+        }
+        // round 2: valid flag and mean of every hit, again independent loads
+        unsigned char ok[kProbes];
+        double m[kProbes][3];
+#pragma unroll
+        for (int u = 0; u < kProbes; ++u) {
+          ok[u] = map.valid[slot[u]];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) m[u][k] = map.mean[3 * size_t(slot[u]) + k];
+        }
+#pragma unroll
+        for (int u = 0; u < kProbes; ++u) {
+          const double dist = match_dist(q[0] - m[u][0], q[1] - m[u][1], q[2] - m[u][2]);
+          if (on[u] && ok[u] != 0 && dist < map.radius_sq) best.offer(dist, slot[u], slot[u]);
+        }
+      }
+  return write_match_records<DST>(map.mean, map.sqrt_info, best.j, x, y, z, i, max_neighbors, L, dst);
+}
+
 // One thread per scan point.  points: 3 planes of n doubles (local frame).  error: the store's kInfoProbeError word.
 template <typename DST>
 __global__ __launch_bounds__(256) void voxel_match_kernel(VoxelMatchView map, const double* __restrict__ px,
@@ -53,93 +151,7 @@ __global__ __launch_bounds__(256) void voxel_match_kernel(VoxelMatchView map, co
                                                           DST* __restrict__ dst, unsigned long long* __restrict__ n_matches,
                                                           unsigned int* __restrict__ error) {
   const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
-  int found = 0;
-  if (i < n_points) {
-    const double x = px[i], y = py[i], z = pz[i];
-    double q[3];
-    warp_point(pose, x, y, z, q[0], q[1], q[2]);
-    // cells floor((q - r - g) inv_res) … floor((q + r + g) inv_res) per axis, clamped to the addressable grid
-    // [-2^20, 2^20) that voxel_points_kernel admits — no voxel lives outside it, and pack_cell would fold a cell beyond
-    // it onto a real key.  A point that is not finite, or whose range misses the grid altogether, visits no cell.
-    int64_t c0[3];
-    int span[3];
-    bool reachable = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double lim = double(1 << 20);
-      const double lo = fmax(floor((q[k] - map.reach) * map.inv_res), -lim);
-      const double hi = fmin(floor((q[k] + map.reach) * map.inv_res), lim - 1.0);
-      reachable = reachable && (lo <= hi);  // a NaN fails (fmax / fmin would drop it: test the point itself too)
-      reachable = reachable && (q[k] == q[k]);
-      c0[k] = reachable ? int64_t(lo) : 0;
-      const int n = reachable ? int(hi - lo) + 1 : 0;
-      span[k] = n < kVoxelMatchMaxSpan ? n : kVoxelMatchMaxSpan;
-    }
-    if (!reachable) span[0] = 0;
-    TwoNearest best;
-    best.init();
-    for (int ix = 0; ix < span[0]; ++ix)
-      for (int by = 0; by < span[1]; by += 3)
-        for (int bz = 0; bz < span[2]; bz += 3) {
-          uint64_t key[9];
-          uint32_t h[9], slot[9];
-          unsigned long long seen[9];
-          bool on[9];
-          // round 1: the first table entry of nine cells — key and slot loaded together, nothing depends on a compare
-#pragma unroll
-          for (int u = 0; u < 9; ++u) {
-            const int dy = by + u / 3, dz = bz + u % 3;
-            on[u] = dy < span[1] && dz < span[2];
-            key[u] = pack_cell(c0[0] + ix, c0[1] + dy, c0[2] + dz);
-            h[u] = hash_cell(key[u]) & map.table_mask;
-          }
-#pragma unroll
-          for (int u = 0; u < 9; ++u) {
-            seen[u] = map.table_key[h[u]];
-            slot[u] = map.table_slot[h[u]];
-          }
-          // collisions: voxel_table_find's probe sequence from the second entry on, bounded by the table size
-#pragma unroll
-          for (int u = 0; u < 9; ++u) {
-            bool hit = on[u] && seen[u] == key[u];
-            if (on[u] && !hit && seen[u] != kEmptyCell) {
-              uint32_t hh = h[u];
-              bool ended = false;
-              for (uint32_t probe = 1; probe <= map.table_mask; ++probe) {
-                hh = (hh + 1) & map.table_mask;
-                const unsigned long long k = map.table_key[hh];
-                if (k == key[u]) {
-                  slot[u] = map.table_slot[hh];
-                  hit = ended = true;
-                  break;
-                }
-                if (k == kEmptyCell) {
-                  ended = true;
-                  break;
-                }
-              }
-              if (!ended) atomicOr(error, 1u);
-            }
-            on[u] = hit;
-            slot[u] = hit ? slot[u] : 0u;  // slot 0 exists in every store (capacity >= 16): a miss reads it and drops it
-          }
-          // round 2: valid flag and mean of every hit, again nine independent loads each
-          unsigned char ok[9];
-          double m[9][3];
-#pragma unroll
-          for (int u = 0; u < 9; ++u) {
-            ok[u] = map.valid[slot[u]];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) m[u][k] = map.mean[3 * size_t(slot[u]) + k];
-          }
-#pragma unroll
-          for (int u = 0; u < 9; ++u) {
-            const double dist = match_dist(q[0] - m[u][0], q[1] - m[u][1], q[2] - m[u][2]);
-            if (on[u] && ok[u] != 0 && dist < map.radius_sq) best.offer(dist, slot[u], slot[u]);
-          }
-        }
-    found = write_match_records<DST>(map.mean, map.sqrt_info, best.j, x, y, z, i, max_neighbors, L, dst);
-  }
+  const int found = i < n_points ? voxel_match_point<DST>(map, px, py, pz, i, pose, max_neighbors, L, dst, error) : 0;
   add_match_count(found, n_matches);
 }
 

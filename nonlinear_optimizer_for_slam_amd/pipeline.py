@@ -85,7 +85,9 @@ def scan_to_map_batch(ctx, ndt_map, scans, initial_poses=None, loss=("exponentia
     runs on the device, one workgroup per scan.  scans: list of api.Scan (the same one may repeat); initial_poses: None
     (identity for all) or a list of Poses.  → list of (Pose, rounds, outer_iter) shaped exactly as scan_to_map returns
     them, or None where scan_to_map would raise RuntimeError (a round's solve failed; the other rows are unaffected).
-    Bit for bit scan_to_map's result for scans of ≤ 512 points, to rounding above."""
+    Bit for bit scan_to_map's result for scans of ≤ 512 points, to rounding above.
+    ndt_map: api.NdtMap, or an api.VoxelMap — the rounds then match against the live store inside the launch (no
+    snapshot); every row is bit for bit the row of the call on its snapshot(), at any scan size."""
     scans = list(scans)
     B = len(scans)
     if initial_poses is None:
@@ -110,8 +112,11 @@ def scan_to_map_batch(ctx, ndt_map, scans, initial_poses=None, loss=("exponentia
     return out
 
 
+_ONE_LAUNCH_KWARGS = ("loss", "options", "max_outer_iterations", "dof", "dtype", "keep_multiple")
+
+
 def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, max_voxel_age=None, filter_voxel_size=None,
-             insert_filtered=False, live_match=False, **scan_to_map_kwargs):
+             insert_filtered=False, live_match=None, one_launch=False, **scan_to_map_kwargs):
     """Scan-to-map odometry over a growing map (api.VoxelMap): for each scan, snapshot the store → scan_to_map from the
     previous scan's pose → insert the scan at the pose found (VoxelMap.insert_scan, warped on the device).  The harness's
     sequence UpdateNdtMap → OptimizePose → UpdateNdtMap (MDM/tests/simple_optimization_test.cc:236-281, 474-503) with the
@@ -125,7 +130,28 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
     is closed after the frame.  None: the scans are registered and inserted as they are.
     live_match=True: no snapshot is taken; every round matches against the store itself (VoxelMap.match), so no step
     of a frame passes over the whole map.  Same poses and rounds, bit for bit.
+    one_launch=True: each frame's registration is ONE batched call of one problem against the live store
+    (scan_to_map_batch on the VoxelMap): all rounds in one launch with one host wait, instead of a match and a solve
+    launch and their waits per round — what a frame of a small (filtered) scan is made of.  Implies live_match.  Takes
+    loss, options, max_outer_iterations, dof, dtype and keep_multiple; indexed, on_solve, device_loop=False and an explicit
+    live_match=False raise ValueError.  A frame whose registration fails raises RuntimeError as scan_to_map does, before
+    anything is inserted.  Same poses and rounds as live_match=True, bit for bit, for scans of ≤ 512 points; to rounding
+    above, where the lone path is also the faster one.
     → (list of Poses, list of per-scan round lists)."""
+    if one_launch:
+        if live_match is not None and not live_match:
+            raise ValueError("one_launch=True registers against the live store: live_match=False contradicts it")
+        if scan_to_map_kwargs.get("indexed"):
+            raise ValueError("one_launch=True: there is no voxel-indexed match against a VoxelMap")
+        if scan_to_map_kwargs.get("on_solve") is not None:
+            raise ValueError("one_launch=True: the rounds run inside one launch, on_solve cannot be called between them")
+        if not scan_to_map_kwargs.get("device_loop", True):
+            raise ValueError("one_launch=True: the LM loop runs on the device, device_loop=False contradicts it")
+        unknown = sorted(set(scan_to_map_kwargs) - set(_ONE_LAUNCH_KWARGS) - {"indexed", "on_solve", "device_loop"})
+        if unknown:
+            raise TypeError("one_launch=True does not take %s" % ", ".join(unknown))
+        batch_kwargs = {k: v for k, v in scan_to_map_kwargs.items() if k in _ONE_LAUNCH_KWARGS}
+    live_match = bool(live_match) or one_launch
     pose = Pose() if initial_pose is None else Pose(initial_pose.R, initial_pose.t)
     windowed = window_half_extent is not None or max_voxel_age is not None
     poses, all_rounds = [], []
@@ -134,7 +160,13 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
         try:
             ndt_map = voxel_map if live_match else voxel_map.snapshot()
             try:
-                pose, rounds, _ = scan_to_map(ctx, ndt_map, registered, initial_pose=pose, **scan_to_map_kwargs)
+                if one_launch:
+                    row = scan_to_map_batch(ctx, voxel_map, [registered], [pose], **batch_kwargs)[0]
+                    if row is None:
+                        raise RuntimeError("SolveDataset failed (a round of the one-launch registration returned ok = 0)")
+                    pose, rounds, _ = row
+                else:
+                    pose, rounds, _ = scan_to_map(ctx, ndt_map, registered, initial_pose=pose, **scan_to_map_kwargs)
             finally:
                 if not live_match:
                     ndt_map.close()
