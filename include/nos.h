@@ -300,6 +300,13 @@ int nos_ndt_match_indexed(nos_ndt_map* map, nos_scan* scan, const double R[9], c
                           int max_neighbors, int dtype, int sort_by_voxel, nos_dataset** out_ds,
                           size_t* n_matches);
 
+/* Inspection of a voxel-indexed dataset, however it was made (any output pointer may be NULL; a flat dataset:
+ * NOS_ERR_WRONG_KIND).  n_slots: id planes; n_voxels: table rows.  The download gives the ids in stored order —
+ * index_planes[k] receives nos_dataset_size entries, k < n_slots — and the table [n_voxels][16] = {mean(3), U(6), 7 pads}
+ * widened to double. */
+int nos_indexed_dataset_info(const nos_dataset* ds, int* n_slots, size_t* n_voxels);
+int nos_indexed_dataset_download(nos_dataset* ds, int32_t* const index_planes[], double* table /* [n_voxels][16] */);
+
 /* ---- NDT map construction on the device --------------------
  * Replaces UpdateNdtMap of the reference's test harness
  * (MDM/tests/simple_optimization_test.cc:236-281): voxelise points_xyz ([n][3], map frame) at
@@ -398,6 +405,31 @@ int nos_voxel_map_stats(nos_voxel_map* map, nos_map_stats** out_stats);
  * r / 3.5 the snapshot's coarser grid is the better structure); NOS_ERR_HIP for a store an earlier failure left undefined. */
 int nos_voxel_map_match(nos_voxel_map* map, nos_scan* scan, const double R[9], const double t[3],
                         int max_neighbors, int dtype, nos_dataset** out_ds, size_t* n_matches);
+/* nos_voxel_map_match producing the voxel-indexed form of nos_ndt_match_indexed, with a COMPACT voxel table
+ * (DESIGN.md §17): no snapshot, and a table sized by the scan, not by the map.
+ * Correspondences: those of nos_voxel_map_match — the same warp, distance, strict radius test and tie-break by slot, the
+ * same guard band g = resolution / 1024 with its caveat, the same limit of 9 cells per axis; *n_matches equals
+ * nos_voxel_map_match's.
+ * Table: one row per DISTINCT store slot that any slot plane of this scan references, in ascending store-slot order; a
+ * point's id is the rank of its voxel in that list, or -1 for none.  A row is {mean(3), U(6) of S = QU, pad} in the
+ * dataset's element type, computed from the store's mean and sqrt-information by the expression every voxel-indexed
+ * dataset's table is built with.  The dataset's n_voxels (nos_indexed_dataset_info) is the number of distinct referenced
+ * voxels, 0 when nothing matched (the table allocation still holds one readable row).
+ * sort_by_voxel as in nos_ndt_match_indexed: a stable order by slot-0 id, absent ids last; 0 keeps the scan's stored order.
+ * Consequence: for every point and slot the referenced row holds the values of the row the snapshot route references, and
+ * the assemble kernel's geometry depends on the padded point count alone — so with sort_by_voxel = 0 every accumulate and
+ * every solve on the returned dataset is bit for bit that of nos_voxel_map_snapshot + nos_ndt_match_indexed(sort_by_voxel
+ * = 0), in both element types; with sort_by_voxel = 1 the ids are numbered differently (rank of the store slot here,
+ * position in the snapshot's cell order there), so the point order differs and the results are equal to rounding.
+ * Work follows the scan: the search, a radix sort of the ids over the bits a slot can have, a unique, a rank pass and the
+ * dataset build; no kernel has a grid or trip count proportional to the store's capacity or voxel count and nothing
+ * allocated is proportional to them; two host waits (the table's size, the finished dataset).  The store is not
+ * modified (nos_voxel_map_memory, voxels, epoch, generation, stamps) and the dataset is independent of it afterwards.
+ * Rejections: those of nos_voxel_map_match, same statuses, *out_ds unwritten (and NOS_ERR_UNSUPPORTED for a scan of 2^31
+ * points or more: ids and ranks are 32-bit); a table probe that ran through the whole table returns NOS_ERR_HIP and nothing. */
+int nos_voxel_map_match_indexed(nos_voxel_map* map, nos_scan* scan, const double R[9], const double t[3],
+                                int max_neighbors, int dtype, int sort_by_voxel,
+                                nos_dataset** out_ds, size_t* n_matches);
 /* Sliding window: removes voxels by a box around a point and / or by age, compacts the survivors on the device and
  * rebuilds the key -> slot table.  The store can shrink.
  * Keep rule (exact):

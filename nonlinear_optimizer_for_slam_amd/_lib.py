@@ -30,10 +30,10 @@ C_ABI_SYMBOLS = (
     "nos_ndt_dataset_create_from_device", "nos_reproj_dataset_create_from_device",
     "nos_ndt_dataset_create_from_records", "nos_reproj_dataset_create_from_records",
     "nos_dataset_download", "nos_ndt_map_create", "nos_ndt_map_destroy", "nos_ndt_map_size", "nos_scan_create",
-    "nos_scan_destroy", "nos_scan_size", "nos_scan_sort_by_cell", "nos_scan_order", "nos_scan_filter", "nos_scan_points", "nos_ndt_match", "nos_ndt_indexed_dataset_create", "nos_ndt_match_indexed", "nos_ndt_map_build", "nos_map_stats_size",
+    "nos_scan_destroy", "nos_scan_size", "nos_scan_sort_by_cell", "nos_scan_order", "nos_scan_filter", "nos_scan_points", "nos_ndt_match", "nos_ndt_indexed_dataset_create", "nos_ndt_match_indexed", "nos_indexed_dataset_info", "nos_indexed_dataset_download", "nos_ndt_map_build", "nos_map_stats_size",
     "nos_map_stats_get", "nos_map_stats_get_eigen", "nos_map_stats_destroy",
     "nos_voxel_map_create", "nos_voxel_map_insert", "nos_voxel_map_insert_scan", "nos_voxel_map_info", "nos_voxel_map_snapshot",
-    "nos_voxel_map_stats", "nos_voxel_map_match", "nos_voxel_map_prune", "nos_voxel_map_memory", "nos_voxel_map_destroy", "nos_dataset_drop_last_matches", "nos_pgo_create", "nos_pgo_destroy", "nos_pgo_num_unknowns",
+    "nos_voxel_map_stats", "nos_voxel_map_match", "nos_voxel_map_match_indexed", "nos_voxel_map_prune", "nos_voxel_map_memory", "nos_voxel_map_destroy", "nos_dataset_drop_last_matches", "nos_pgo_create", "nos_pgo_destroy", "nos_pgo_num_unknowns",
     "nos_pgo_linearize", "nos_pgo_solve", "nos_pgo_retract", "nos_pgo_get_state", "nos_pgo_get_vector",
     "nos_pgo_matvec", "nos_pgo_time_sweep", "nos_pgo_layout_info", "nos_debug_lm_step", "nos_dataset_destroy", "nos_dataset_size", "nos_dataset_dtype", "nos_dataset_stream_bytes",
     "nos_dataset_set_simd_class",
@@ -186,6 +186,10 @@ def _declare(lib):
             lib.nos_voxel_map_memory.argtypes = [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ull_p, ull_p]
         if hasattr(lib, "nos_voxel_map_match"):  # matching against the live store: absent from builds older still
             lib.nos_voxel_map_match.argtypes = [vp, vp, dp, dp, i, i, c_void_pp, ctypes.POINTER(sz)]
+        if hasattr(lib, "nos_voxel_map_match_indexed"):  # the voxel-indexed form of it: absent from builds older still
+            lib.nos_voxel_map_match_indexed.argtypes = [vp, vp, dp, dp, i, i, i, c_void_pp, ctypes.POINTER(sz)]
+            lib.nos_indexed_dataset_info.argtypes = [vp, ctypes.POINTER(i), ctypes.POINTER(sz)]
+            lib.nos_indexed_dataset_download.argtypes = [vp, ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)), dp]
     if hasattr(lib, "nos_dataset_drop_last_matches"):
         lib.nos_dataset_drop_last_matches.argtypes = [vp, sz]
     ip = ctypes.POINTER(ctypes.c_int32)

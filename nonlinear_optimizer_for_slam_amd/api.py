@@ -541,6 +541,37 @@ class NdtIndexedDataset(NdtDataset):
               "nos_ndt_indexed_dataset_create")
         return cls(ctx, h)
 
+    def _indexed_info(self):
+        k, v = ctypes.c_int(), ctypes.c_size_t()
+        check(self._lib.nos_indexed_dataset_info(self._h, ctypes.byref(k), ctypes.byref(v)), "nos_indexed_dataset_info")
+        return int(k.value), int(v.value)
+
+    @property
+    def n_slots(self):
+        """id planes per point (1 or 2)"""
+        return self._indexed_info()[0]
+
+    @property
+    def n_voxels(self):
+        """rows of the voxel table"""
+        return self._indexed_info()[1]
+
+    def ids(self):
+        """→ [n_slots, n] int32: the voxel ids (table rows, -1 = none) in stored order (nos_indexed_dataset_download)."""
+        K, _ = self._indexed_info()
+        out = np.zeros((K, len(self)), dtype=np.int32)
+        ip_t = ctypes.POINTER(ctypes.c_int32)
+        planes = (ip_t * K)(*[out[k].ctypes.data_as(ip_t) for k in range(K)])
+        check(self._lib.nos_indexed_dataset_download(self._h, planes, None), "nos_indexed_dataset_download")
+        return out
+
+    def table(self):
+        """→ [n_voxels, 16] float64: the voxel table {mean(3), U(6) of S = QU, pads}, widened from the element type."""
+        _, V = self._indexed_info()
+        out = np.zeros((V, 16))
+        check(self._lib.nos_indexed_dataset_download(self._h, None, _dp(out)), "nos_indexed_dataset_download")
+        return out
+
 
 class ReprojDataset(_Dataset):
     """Device-resident 3D↔2D correspondences (X, Y, Z, u, v)."""
@@ -784,6 +815,22 @@ class VoxelMap:
         check(self._lib.nos_voxel_map_match(self._h, scan._h, _dp(R), _dp(t), max_neighbors, _DTYPES[dtype],
                                             ctypes.byref(h), ctypes.byref(n)), "nos_voxel_map_match")
         return NdtDataset(self._ctx, h), int(n.value)
+
+    def match_indexed(self, scan, R, t, max_neighbors=2, dtype="f64", sort_by_voxel=True):
+        """NdtMap.match_indexed against the store as it is now, without a snapshot (nos_voxel_map_match_indexed) →
+        (NdtIndexedDataset, number of real matches).  The voxel table is COMPACT: one row per distinct voxel this scan
+        matched, in ascending slot order (n_voxels ≤ max_neighbors · len(scan)), so it is sized by the scan, not by the
+        map.  With sort_by_voxel=False every sum and solve is bit for bit that of snapshot().match_indexed(...,
+        sort_by_voxel=False); with True, equal to rounding.  The dataset is independent of the store; the store is not
+        modified."""
+        R = _dvec(R, 9)
+        t = _dvec(t, 3)
+        h = ctypes.c_void_p()
+        n = ctypes.c_size_t()
+        check(self._lib.nos_voxel_map_match_indexed(self._h, scan._h, _dp(R), _dp(t), max_neighbors, _DTYPES[dtype],
+                                                    int(bool(sort_by_voxel)), ctypes.byref(h), ctypes.byref(n)),
+              "nos_voxel_map_match_indexed")
+        return NdtIndexedDataset(self._ctx, h), int(n.value)
 
     def stats(self):
         """→ dict with means, sqrt_infos, valid, counts, cells in voxel-id order (the keys NdtMap.build returns)."""

@@ -144,15 +144,19 @@ __global__ __launch_bounds__(256) void gather_plane_kernel(const SRC* __restrict
   dst[j] = j < n ? DST(src[perm ? perm[j] : j]) : pad_value;
 }
 
-// voxel table: [V][3] means + [V][9] sqrt-informations (double) → [V][16] records of T = {mean, U of S = QU}
+// voxel table: [·][3] means + [·][9] sqrt-informations (double) → [V][16] records of T = {mean, U of S = QU}.  rows (the
+// way gather_plane_kernel takes perm): table row r is built from source row rows[r] — the compact table of a match
+// against the live store, whose sources are the referenced store slots; null: source row r.
 template <typename T>
 __global__ __launch_bounds__(256) void build_voxel_table_kernel(const double* __restrict__ means,
-                                                                const double* __restrict__ sqrt_infos, uint64_t n_voxels,
+                                                                const double* __restrict__ sqrt_infos,
+                                                                const uint32_t* __restrict__ rows, uint64_t n_voxels,
                                                                 T* __restrict__ table) {
   const uint64_t t = uint64_t(blockIdx.x) * 256 + threadIdx.x;
-  const uint64_t v = t >> 4;
+  const uint64_t r = t >> 4;
   const int k = int(t & 15);
-  if (v >= n_voxels) return;
+  if (r >= n_voxels) return;
+  const uint64_t v = rows ? rows[r] : r;
   T val = T(0);
   if (k < 3) {
     val = T(means[3 * v + k]);

@@ -76,13 +76,12 @@ int nosd::launch_indexed(const nos_dataset* ds, const Shard& sh, const Request& 
   return fail(NOS_ERR_WRONG_KIND, "voxel-indexed datasets serve the NDT entry points only");
 }
 
-namespace {
-
 // Builds the dataset from device-resident inputs: point planes [3][n] (double), index planes [K][n] (int32),
-// voxel arrays (double).  Sorts by slot-0 voxel id when asked.  All on the context's stream.
-int indexed_from_device(nos_ctx* ctx, size_t n, const double* d_points, int n_slots, const int32_t* d_index,
-                        size_t n_voxels, const double* d_means, const double* d_sqrt_infos, int dtype, int sort_by_voxel,
-                        nos_dataset** out_ds) {
+// voxel arrays (double).  Sorts by slot-0 voxel id when asked.  All on the context's stream.  d_rows (may be null): table
+// row r comes from row d_rows[r] of the voxel arrays instead of row r (n_voxels entries).
+int nosd::indexed_from_device(nos_ctx* ctx, size_t n, const double* d_points, int n_slots, const int32_t* d_index,
+                              size_t n_voxels, const double* d_means, const double* d_sqrt_infos, const uint32_t* d_rows,
+                              int dtype, int sort_by_voxel, nos_dataset** out_ds) {
   if (dtype != NOS_F64 && dtype != NOS_F32) return fail(NOS_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
   if (n >= 0xFFFFFFFFull) return fail(NOS_ERR_UNSUPPORTED, "too many points for one indexed dataset");
   nos_dataset* ds = new (std::nothrow) nos_dataset();
@@ -168,10 +167,10 @@ int indexed_from_device(nos_ctx* ctx, size_t n, const double* d_points, int n_sl
     const dim3 grid(unsigned((n_voxels * 16 + 255) / 256));
     if (dtype == NOS_F64)
       hipLaunchKernelGGL((nos::build_voxel_table_kernel<double>), grid, dim3(256), 0, st, d_means, d_sqrt_infos,
-                         uint64_t(n_voxels), static_cast<double*>(sh.table));
+                         d_rows, uint64_t(n_voxels), static_cast<double*>(sh.table));
     else
       hipLaunchKernelGGL((nos::build_voxel_table_kernel<float>), grid, dim3(256), 0, st, d_means, d_sqrt_infos,
-                         uint64_t(n_voxels), static_cast<float*>(sh.table));
+                         d_rows, uint64_t(n_voxels), static_cast<float*>(sh.table));
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -183,6 +182,8 @@ int indexed_from_device(nos_ctx* ctx, size_t n, const double* d_points, int n_sl
   *out_ds = ds;
   return NOS_OK;
 }
+
+namespace {
 
 // like match_kernel, but emits voxel ids (positions in the map's cell-ordered arrays) instead of records
 __global__ __launch_bounds__(256) void match_index_kernel(nos::MapView map, const double* __restrict__ px,
@@ -248,7 +249,7 @@ int nos_ndt_indexed_dataset_create(nos_ctx* ctx, size_t n_points, const double* 
   if (e == hipSuccess && n_voxels > 0) e = hipMemcpyAsync(d_means, means_xyz, n_voxels * 3 * sizeof(double), hipMemcpyHostToDevice, slot.stream);
   if (e == hipSuccess && n_voxels > 0) e = hipMemcpyAsync(d_S, sqrt_infos, n_voxels * 9 * sizeof(double), hipMemcpyHostToDevice, slot.stream);
   if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "indexed upload failed: %s", hipGetErrorString(e));
-  return indexed_from_device(ctx, n_points, d_pts, n_slots, d_idx, n_voxels, d_means, d_S, dtype, sort_by_voxel, out_ds);
+  return indexed_from_device(ctx, n_points, d_pts, n_slots, d_idx, n_voxels, d_means, d_S, nullptr, dtype, sort_by_voxel, out_ds);
 }
 
 int nos_ndt_match_indexed(nos_ndt_map* map, nos_scan* scan, const double R[9], const double t[3], int max_neighbors,
@@ -280,9 +281,44 @@ int nos_ndt_match_indexed(nos_ndt_map* map, nos_scan* scan, const double R[9], c
   if (e == hipSuccess) e = hipStreamSynchronize(slot.stream);
   if (e != hipSuccess) return fail(NOS_ERR_HIP, "indexed matching failed: %s", hipGetErrorString(e));
   const int rc = indexed_from_device(ctx, n, scan->d_planes, max_neighbors, d_idx, map->n_voxels, map->d_mean, map->d_sqrt_info,
-                                     dtype, sort_by_voxel, out_ds);
+                                     nullptr, dtype, sort_by_voxel, out_ds);
   if (rc != NOS_OK) return rc;
   if (n_matches) *n_matches = size_t(count);
+  return NOS_OK;
+}
+
+int nos_indexed_dataset_info(const nos_dataset* ds, int* n_slots, size_t* n_voxels) {
+  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!ds) return fail(NOS_ERR_INVALID_ARGUMENT, "dataset is NULL");
+  if (ds->kind != kKindNdtIndexed) return fail(NOS_ERR_WRONG_KIND, "not a voxel-indexed dataset");
+  const Shard& sh = ds->shards[0];
+  if (n_slots) *n_slots = sh.n_slots;
+  if (n_voxels) *n_voxels = sh.n_voxels;
+  return NOS_OK;
+}
+
+int nos_indexed_dataset_download(nos_dataset* ds, int32_t* const index_planes[], double* table) {
+  nosd::CtxGuard guard_(ds ? ds->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!ds) return fail(NOS_ERR_INVALID_ARGUMENT, "dataset is NULL");
+  if (ds->kind != kKindNdtIndexed) return fail(NOS_ERR_WRONG_KIND, "not a voxel-indexed dataset");
+  const Shard& sh = ds->shards[0];
+  DeviceSlot& slot = ds->ctx->slots[sh.slot];
+  NOS_HIP_CHECK(hipSetDevice(slot.device));
+  NOS_HIP_CHECK(hipStreamSynchronize(slot.stream));
+  for (int k = 0; index_planes && k < sh.n_slots; ++k)
+    if (index_planes[k] && ds->n > 0)
+      NOS_HIP_CHECK(hipMemcpy(index_planes[k], sh.index + size_t(k) * sh.layout.n_padded, ds->n * sizeof(int32_t),
+                              hipMemcpyDeviceToHost));
+  const size_t cells = sh.n_voxels * 16;
+  if (table && cells > 0) {
+    if (ds->dtype == NOS_F64) {
+      NOS_HIP_CHECK(hipMemcpy(table, sh.table, cells * sizeof(double), hipMemcpyDeviceToHost));
+    } else {  // widened on the host: exact
+      std::vector<float> narrow(cells);
+      NOS_HIP_CHECK(hipMemcpy(narrow.data(), sh.table, cells * sizeof(float), hipMemcpyDeviceToHost));
+      for (size_t c = 0; c < cells; ++c) table[c] = double(narrow[c]);
+    }
+  }
   return NOS_OK;
 }
 

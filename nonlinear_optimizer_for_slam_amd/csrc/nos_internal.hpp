@@ -476,6 +476,13 @@ int register_live(int dof, const LiveStore* store, nos_scan* const* scans, int32
                   const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
                   nos_register_report* reports);
 // nos_indexed.hip
+// A voxel-indexed dataset from device-resident inputs (point planes [3][n], id planes [n_slots][n], voxel arrays), all on
+// the context's stream; one host wait.  d_rows == NULL: table row r is row r of d_means / d_sqrt_infos and ids index them
+// (nos_ndt_match_indexed).  Otherwise table row r is built from row d_rows[r] (n_voxels entries) and ids are ranks in
+// d_rows: the compact table of nos_voxel_map_match_indexed (nos_voxelmap.hip), whose sources are the store's own arrays.
+int indexed_from_device(nos_ctx* ctx, size_t n, const double* d_points, int n_slots, const int32_t* d_index, size_t n_voxels,
+                        const double* d_means, const double* d_sqrt_infos, const uint32_t* d_rows, int dtype,
+                        int sort_by_voxel, nos_dataset** out_ds);
 int launch_indexed(const nos_dataset* ds, const Shard& sh, const Request& rq, double* partials,
                    const nos::FusedFinal& fin, hipStream_t stream, int* rows_out);
 

@@ -45,7 +45,7 @@ enum VoxelInfoWord {
   kInfoRemoved = 5,     // voxels the last keep pass marked for removal
   kInfoRemovedPoints = 6,  // their points: one 64-bit counter in words 6 and 7
   kInfoKeptValid = 8,   // valid voxels among those the last keep pass kept
-  kInfoMatches = 10,    // real matches of the last nos_voxel_map_match: one 64-bit counter in words 10 and 11.  That call
+  kInfoMatches = 10,    // real matches of the last nos_voxel_map_match(_indexed): one 64-bit counter in words 10 and 11.  That call
                         // writes these two words and clears kInfoProbeError before its launch; "the store is not modified"
                         // holds for the info block by convention only: no call reads words 10-11, and every call that
                         // reads kInfoProbeError (insert, growth, prune) clears it itself before the kernels that raise it

@@ -45,18 +45,13 @@ struct VoxelMatchView {
   double radius_sq;
 };
 
-// Scan point i (i < n_points) warped by `pose` and matched against the live store: writes slots 2i and 2i + 1 of the
-// dataset and returns the number of real matches among them (0-2) — match_point (match_kernels.hpp) on the store's table.
-// error: the store's kInfoProbeError word.  voxel_match_kernel (one thread per point) and register_live_kernel
-// (assemble_register_live.hpp, the lanes of one workgroup striding over a scan) both call this, so their records are the
-// same bits.
-template <typename DST>
-__device__ __forceinline__ int voxel_match_point(const VoxelMatchView& map, const double* __restrict__ px,
-                                                 const double* __restrict__ py, const double* __restrict__ pz, uint64_t i,
-                                                 const PosePod& pose, int max_neighbors, const TiledLayout& L,
-                                                 DST* __restrict__ dst, unsigned int* __restrict__ error) {
+// The search of the live matcher: scan point (x, y, z) warped by `pose`, the cells its ball touches, and the nine-probe
+// rounds into `best` — best.j[k] is the store slot of the k-th nearest valid voxel mean within the radius (ties by slot),
+// or 0xFFFFFFFF.  error: the store's kInfoProbeError word.  What voxel_match_point turns into records and
+// voxel_match_index_kernel (nos_voxelmap.hip) into slot ids: one search, so both forms name the same voxels.
+__device__ __forceinline__ void voxel_find_two_nearest(const VoxelMatchView& map, const PosePod& pose, double x, double y,
+                                                       double z, TwoNearest& best, unsigned int* __restrict__ error) {
   constexpr int kProbes = 9;  // the 3 x 3 block of (y, z) cells probed together per step
-  const double x = px[i], y = py[i], z = pz[i];
   double q[3];
   warp_point(pose, x, y, z, q[0], q[1], q[2]);
   // cells floor((q - r - g) inv_res) … floor((q + r + g) inv_res) per axis, clamped to the addressable grid
@@ -77,7 +72,6 @@ __device__ __forceinline__ int voxel_match_point(const VoxelMatchView& map, cons
     span[k] = n < kVoxelMatchMaxSpan ? n : kVoxelMatchMaxSpan;
   }
   if (!reachable) span[0] = 0;
-  TwoNearest best;
   best.init();
   for (int ix = 0; ix < span[0]; ++ix)
     for (int by = 0; by < span[1]; by += 3)
@@ -140,6 +134,21 @@ __device__ __forceinline__ int voxel_match_point(const VoxelMatchView& map, cons
           if (on[u] && ok[u] != 0 && dist < map.radius_sq) best.offer(dist, slot[u], slot[u]);
         }
       }
+}
+
+// Scan point i (i < n_points) warped by `pose` and matched against the live store: writes slots 2i and 2i + 1 of the
+// dataset and returns the number of real matches among them (0-2) — match_point (match_kernels.hpp) on the store's table.
+// error: the store's kInfoProbeError word.  voxel_match_kernel (one thread per point) and register_live_kernel
+// (assemble_register_live.hpp, the lanes of one workgroup striding over a scan) both call this, so their records are the
+// same bits.
+template <typename DST>
+__device__ __forceinline__ int voxel_match_point(const VoxelMatchView& map, const double* __restrict__ px,
+                                                 const double* __restrict__ py, const double* __restrict__ pz, uint64_t i,
+                                                 const PosePod& pose, int max_neighbors, const TiledLayout& L,
+                                                 DST* __restrict__ dst, unsigned int* __restrict__ error) {
+  const double x = px[i], y = py[i], z = pz[i];
+  TwoNearest best;
+  voxel_find_two_nearest(map, pose, x, y, z, best, error);
   return write_match_records<DST>(map.mean, map.sqrt_info, best.j, x, y, z, i, max_neighbors, L, dst);
 }
 

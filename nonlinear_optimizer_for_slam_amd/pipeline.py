@@ -21,7 +21,7 @@ def _quat_vec_norm(R):
 
 def scan_to_map(ctx, ndt_map, scan, initial_pose=None, loss=("exponential", 1.0, 1.0), options=None,
                 max_outer_iterations=10, dof=6, dtype="f64", on_solve=None, indexed=False, keep_multiple=None,
-                device_loop=True):
+                device_loop=True, live_indexed=False):
     """ndt_map: api.NdtMap, or an api.VoxelMap — every round then matches against the live store (VoxelMap.match, no
     snapshot) and gives the pose, rounds and outer_iter of scan_to_map on its snapshot(), bit for bit; scan: api.Scan.
     → (Pose, list of per-round dicts, outer_iter) — outer_iter as the reference prints it (index of the round that met
@@ -30,6 +30,12 @@ def scan_to_map(ctx, ndt_map, scan, initial_pose=None, loss=("exponential", 1.0,
     indexed=True: the matcher emits voxel ids instead of 120-byte records (nos_ndt_match_indexed) and the solver runs on
     the voxel-indexed layout — 2-3x less memory traffic per LM iteration for large scans (sort the scan by cell first:
     api.Scan(..., sort_cell=...)); same sums, same pose.
+
+    live_indexed=True (an api.VoxelMap only): every round matches through VoxelMap.match_indexed(..., sort_by_voxel=False)
+    — the voxel-indexed layout against the live store, with a voxel table of just the voxels the round matched
+    (nos_voxel_map_match_indexed).  Pose, rounds and outer_iter are bit for bit those of
+    scan_to_map(ctx, voxel_map.snapshot(), scan, indexed=True).  Its own keyword because indexed=True with a VoxelMap
+    raises ValueError and keeps doing so; an NdtMap, keep_multiple or indexed=True next to it raise ValueError.
 
     keep_multiple=k: every round uses only the first floor(N/k)*k of its N matches, as the reference's classes do on their
     correspondence vector (k = 4: scalar 3-DoF class, MDM/..._analytic_3dof.cc:33-36, and the revision of the 6-DoF class
@@ -40,6 +46,14 @@ def scan_to_map(ctx, ndt_map, scan, initial_pose=None, loss=("exponential", 1.0,
     if indexed and keep_multiple:
         raise ValueError("keep_multiple (the tail drop of the reference's classes) is implemented for the flat layout only: "
                          "a voxel-indexed dataset has no per-match records to clear (nos_dataset_drop_last_matches)")
+    if live_indexed:
+        if indexed:
+            raise ValueError("live_indexed=True and indexed=True are two routes: pick one (indexed=True needs an NdtMap)")
+        if keep_multiple:
+            raise ValueError("keep_multiple is implemented for the flat layout only: live_indexed=True builds a "
+                             "voxel-indexed dataset")
+        if not isinstance(ndt_map, VoxelMap):
+            raise ValueError("live_indexed=True matches against a live VoxelMap: with an NdtMap use indexed=True")
     if indexed and isinstance(ndt_map, VoxelMap):
         raise ValueError("indexed=True needs an NdtMap: there is no live voxel-indexed match against a VoxelMap "
                          "(take a snapshot() first)")
@@ -53,7 +67,7 @@ def scan_to_map(ctx, ndt_map, scan, initial_pose=None, loss=("exponential", 1.0,
     outer = 0
     for outer in range(max_outer_iterations):
         n_used = None
-        if indexed:
+        if indexed or live_indexed:
             dataset, n_matches = ndt_map.match_indexed(scan, pose.R, pose.t, 2, dtype, sort_by_voxel=False)
         else:
             dataset, n_matches = ndt_map.match(scan, pose.R, pose.t, 2, dtype)
@@ -116,7 +130,7 @@ _ONE_LAUNCH_KWARGS = ("loss", "options", "max_outer_iterations", "dof", "dtype",
 
 
 def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, max_voxel_age=None, filter_voxel_size=None,
-             insert_filtered=False, live_match=None, one_launch=False, **scan_to_map_kwargs):
+             insert_filtered=False, live_match=None, one_launch=False, live_indexed=False, **scan_to_map_kwargs):
     """Scan-to-map odometry over a growing map (api.VoxelMap): for each scan, snapshot the store → scan_to_map from the
     previous scan's pose → insert the scan at the pose found (VoxelMap.insert_scan, warped on the device).  The harness's
     sequence UpdateNdtMap → OptimizePose → UpdateNdtMap (MDM/tests/simple_optimization_test.cc:236-281, 474-503) with the
@@ -137,7 +151,15 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
     live_match=False raise ValueError.  A frame whose registration fails raises RuntimeError as scan_to_map does, before
     anything is inserted.  Same poses and rounds as live_match=True, bit for bit, for scans of ≤ 512 points; to rounding
     above, where the lone path is also the faster one.
+    live_indexed=True: every round matches through VoxelMap.match_indexed (scan_to_map's live_indexed: the voxel-indexed
+    layout with a compact table, no snapshot).  Implies live_match; an explicit live_match=False raises ValueError.  Same
+    poses and rounds, bit for bit, as odometry(indexed=True) on the snapshot route.  Not a keyword of one_launch=True.
     → (list of Poses, list of per-scan round lists)."""
+    if live_indexed:
+        if live_match is not None and not live_match:
+            raise ValueError("live_indexed=True matches against the live store: live_match=False contradicts it")
+        scan_to_map_kwargs["live_indexed"] = True  # with one_launch=True: its unknown-keyword TypeError below
+        live_match = True
     if one_launch:
         if live_match is not None and not live_match:
             raise ValueError("one_launch=True registers against the live store: live_match=False contradicts it")
