@@ -14,9 +14,9 @@ namespace nos {
 // pipeline.scan_to_map runs OptimizePoseAnalytic's outer loop (MDM/tests/simple_optimization_test.cc:474-503) from the
 // host: per round a match launch, an optional tail-drop launch, a solve launch and a host synchronisation.  Here workgroup b
 // runs all rounds of problem b inside one launch.  Per round:
-//   1. match: the lanes stride over scan b's points, each through match_point (match_kernel's body; against a live voxel
-//      store: voxel_match_point, voxel_match_kernel's body, assemble_register_live.hpp) into the problem's scratch
-//      dataset — the layout nos_ndt_match gives a dataset of 2n slots of that element type;
+//   1. match: the lanes stride over scan b's points, each through match_point (match_kernels.hpp: the body of
+//      match_kernel and, instantiated for the live voxel store's view, of voxel_match_kernel) into the problem's
+//      scratch dataset — the layout nos_ndt_match gives a dataset of 2n slots of that element type;
 //   2. count the matches (integer workgroup sum) and, with keep_multiple = k > 0, clear the last matches % k non-empty
 //      records (drop_last_records, drop_last_matches_kernel's body);
 //   3. make the loop state with the LmInit6 / LmInit3 call of the lone solve and run single_block_loop, the loop of
@@ -96,19 +96,10 @@ __device__ __forceinline__ bool pose_converged(const double R[9], const double t
   return sqrt(nn) < 1e-5 && sqrt(h > 0.0 ? h : 0.0) < 1e-5;
 }
 
-// The matcher of one scan point by the kind of map: the only line of a registration that depends on it.  This one is the
-// snapshot's (match_point); the live store's overload is in assemble_register_live.hpp.  error: unused here.
-template <typename T>
-__device__ __forceinline__ int register_match_point(const MapView& map, const double* __restrict__ px,
-                                                    const double* __restrict__ py, const double* __restrict__ pz, uint64_t i,
-                                                    const PosePod& pose, int max_neighbors, const TiledLayout& L,
-                                                    T* __restrict__ dst, unsigned int*) {
-  return match_point<T>(map, px, py, pz, i, pose, max_neighbors, L, dst);
-}
-
 // Problem blockIdx.x of a batched registration, all rounds: the body of register_batch_kernel (below) and of
-// register_live_kernel (assemble_register_live.hpp).  View: MapView or VoxelMatchView; error: what the view's matcher
-// reports a failed table probe through (the live store's kInfoProbeError word; null for a snapshot).
+// register_live_kernel (assemble_register_live.hpp).  View: MapView or VoxelMatchView — match_point, a template over it,
+// is the only line of a registration that depends on the kind of map; error: what it reports a failed table probe
+// through (the live store's kInfoProbeError word; null for a snapshot).
 template <typename Problem, typename T, int BLOCK, typename View>
 __device__ __forceinline__ void register_problem(const View& map, unsigned int* __restrict__ error,
                                                  const RegisterDesc<typename Problem::Params>* __restrict__ descs,
@@ -147,7 +138,7 @@ __device__ __forceinline__ void register_problem(const View& map, unsigned int* 
     // 1. match
     int found = 0;
     for (uint64_t i = threadIdx.x; i < d.n_points; i += BLOCK)
-      found += register_match_point<T>(map, px, py, pz, i, pose, max_neighbors, L, data, error);
+      found += match_point<T>(map, px, py, pz, i, pose, max_neighbors, L, data, error);
     // 2. count: wave sums, then every lane adds the kWaves partials in one order
     unsigned long long s = (unsigned long long)found;
 #pragma unroll

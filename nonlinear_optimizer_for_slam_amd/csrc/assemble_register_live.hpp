@@ -1,6 +1,6 @@
 // assemble_register_live.hpp — batched registration against the LIVE voxel store (nos_voxel_map_register6_batch /
-// nos_voxel_map_register3_batch): register_batch_kernel's rounds (assemble_register.hpp) with the matcher of
-// voxelmatch_kernels.hpp in place of the snapshot's.
+// nos_voxel_map_register3_batch): register_problem (assemble_register.hpp) instantiated for the store's
+// view, so every round's match is match_point on find_two_nearest of voxelmatch_kernels.hpp.
 // Part of the hand-written gfx950 kernels of the Gauss-Newton normal-equation assembly path; see assemble_kernels.hpp.
 #pragma once
 
@@ -14,13 +14,6 @@ namespace nos {
 // kernel is not acceptable.  The match phase is not where the registers peak: the loop's state lives in LDS across it,
 // and the peak is single_block_loop's.  Every instantiation compiles to 170 … 206 VGPRs, no spill, no scratch
 // (tests/test_voxel_register_kernel_resources.py), so the probe depth is left as it is.
-template <typename T>
-__device__ __forceinline__ int register_match_point(const VoxelMatchView& map, const double* __restrict__ px,
-                                                    const double* __restrict__ py, const double* __restrict__ pz, uint64_t i,
-                                                    const PosePod& pose, int max_neighbors, const TiledLayout& L,
-                                                    T* __restrict__ dst, unsigned int* __restrict__ error) {
-  return voxel_match_point<T>(map, px, py, pz, i, pose, max_neighbors, L, dst, error);
-}
 
 // register_batch_kernel on the live store.  The store is only read; `error` (its kInfoProbeError word) is the one word of
 // it this kernel may write.  (The name must not contain "register_batch_kernel<": the resource test of that kernel counts

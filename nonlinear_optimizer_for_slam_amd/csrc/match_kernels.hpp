@@ -14,6 +14,12 @@
 // exactly nothing to H, g and cost — so no compaction pass and no host round trip are needed
 // between matching and solving.  HBM-bound integer/pointer work: coalesced point reads, 16-byte
 // coalesced record writes, candidate reads served from L2 (the map is small).
+//
+// One matcher for both kinds of map.  find_two_nearest has an overload per view — MapView here,
+// VoxelMatchView (the live voxel store) in voxelmatch_kernels.hpp — and everything around the search exists once:
+//   match_point<DST>     = warp_point, find_two_nearest, write_match_records   → records: match_kernel, voxel_match_kernel
+//                          (that call for the thread's point, then add_match_count) and the registrations (register_problem)
+//   match_point_ids      = warp_point, find_two_nearest, -1 for an absent slot → ids: match_index_kernel, voxel_match_index_kernel
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -99,7 +105,10 @@ __device__ __forceinline__ double match_dist(double ex, double ey, double ez) {
 
 // The (up to) two nearest valid voxel means within the radius of the world point q — FLANN radiusSearch with
 // max_neighbors = 2 on squared distances, ties broken by original voxel id.  Same result from both grid forms.
-__device__ __forceinline__ void find_two_nearest(const MapView& map, double qx, double qy, double qz, TwoNearest& best) {
+// One overload per map view (the live store's: voxelmatch_kernels.hpp), one signature: the warped point, the result in
+// best.j (a position in view.mean / view.sqrt_info, or 0xFFFFFFFF), the probe-error word (unused: no probe here can fail).
+__device__ __forceinline__ void find_two_nearest(const MapView& map, const double (&q)[3], TwoNearest& best, unsigned int*) {
+  const double qx = q[0], qy = q[1], qz = q[2];
   best.init();
   const int64_t cx = int64_t(floor(qx * map.inv_cell));
   const int64_t cy = int64_t(floor(qy * map.inv_cell));
@@ -160,7 +169,8 @@ __device__ __forceinline__ void find_two_nearest(const MapView& map, double qx, 
 
 // The local point (x, y, z) warped by `pose`.  The multiply-adds are spelled out, in the form the compiler chose for
 // match_kernel when it was written as `R0 x + R1 y + R2 z + t0`: left to the compiler, a different surrounding kernel
-// could fuse another product.  match_point and voxel_match_kernel call this; the voxel store's insert (voxel_points_kernel) spells the same form.
+// could fuse another product.  match_point and match_point_ids, the only callers, warp every point of every matcher; the
+// voxel store's insert (voxel_points_kernel) spells the same form.
 __device__ __forceinline__ void warp_point(const PosePod& pose, double x, double y, double z, double& qx, double& qy,
                                            double& qz) {
   qx = __builtin_fma(pose.R[2], z, __builtin_fma(pose.R[0], x, pose.R[1] * y)) + pose.t[0];
@@ -171,8 +181,8 @@ __device__ __forceinline__ void warp_point(const PosePod& pose, double x, double
 // Slots 2i and 2i + 1 of the dataset for scan point i = (x, y, z): record k holds the local point, mean[best_j[k]] and
 // sqrt_info[best_j[k]] (and its triangular factor U), or all zeros when best_j[k] is 0xFFFFFFFF (or k = 1 and
 // max_neighbors = 1).  → the number of real records (0-2).  `mean` [V][3] and `sqrt_info` [V][9] are whatever arrays the
-// search indexed: the snapshot's cell-ordered copies (match_point) or the voxel store's own (voxel_match_kernel,
-// voxelmatch_kernels.hpp) — one record writer, so the two routes store the same bits for the same voxel.
+// search indexed: the snapshot's cell-ordered copies or the voxel store's own — one record writer, so the two routes
+// store the same bits for the same voxel.
 template <typename DST>
 __device__ __forceinline__ int write_match_records(const double* __restrict__ mean, const double* __restrict__ sqrt_info,
                                                    const uint32_t (&best_j)[2], double x, double y, double z, uint64_t i,
@@ -217,19 +227,43 @@ __device__ __forceinline__ void add_match_count(int found, unsigned long long* _
   if ((threadIdx.x & (kWave - 1)) == 0 && s > 0) atomicAdd(n_matches, (unsigned long long)s);
 }
 
-// Scan point i (i < n_points) warped by `pose` and matched: writes slots 2i and 2i + 1 of the dataset and returns the
-// number of real matches among them (0-2).  match_kernel (one thread per point) and register_batch_kernel (the lanes of
-// one workgroup striding over a scan, assemble_register.hpp) both call this, so their records are the same bits.
-template <typename DST>
-__device__ __forceinline__ int match_point(const MapView& map, const double* __restrict__ px, const double* __restrict__ py,
+// Scan point i (i < n_points) warped by `pose` and matched against `map` (a MapView or a VoxelMatchView): writes slots
+// 2i and 2i + 1 of the dataset and returns the number of real matches among them (0-2).  error: the probe-error word
+// find_two_nearest is handed.  The one-thread-per-point kernels and the batched registrations (register_problem: the
+// lanes of one workgroup striding over a scan) all call this, so a registration round's records are a lone match's bits.
+template <typename DST, typename View>
+__device__ __forceinline__ int match_point(const View& map, const double* __restrict__ px, const double* __restrict__ py,
                                            const double* __restrict__ pz, uint64_t i, const PosePod& pose,
-                                           int max_neighbors, const TiledLayout& L, DST* __restrict__ dst) {
+                                           int max_neighbors, const TiledLayout& L, DST* __restrict__ dst,
+                                           unsigned int* __restrict__ error) {
   const double x = px[i], y = py[i], z = pz[i];
-  double qx, qy, qz;
-  warp_point(pose, x, y, z, qx, qy, qz);
+  double q[3];
+  warp_point(pose, x, y, z, q[0], q[1], q[2]);
   TwoNearest best;
-  find_two_nearest(map, qx, qy, qz, best);
+  find_two_nearest(map, q, best, error);
   return write_match_records<DST>(map.mean, map.sqrt_info, best.j, x, y, z, i, max_neighbors, L, dst);
+}
+
+// match_point naming the voxels instead of writing their records: idx0[i] / idx1[i] = best.j of the nearest / second
+// nearest voxel, or -1 (idx1 also when max_neighbors = 1).  → the number of ids that are not -1.  The same warp and the
+// same search, so the indexed form names exactly the voxels whose records the flat form writes.
+// kSecondFirst: the order of the two terms of that number, which moves the last ten instructions of an index kernel: each
+// kernel names the order that keeps the body it had before it called this function (tools/compare_kernel_asm.py).  It
+// pins the source to one compiler's choice: delete it as soon as identical code objects are no longer asked for.
+template <bool kSecondFirst, typename View>
+__device__ __forceinline__ int match_point_ids(const View& map, const double* __restrict__ px, const double* __restrict__ py,
+                                               const double* __restrict__ pz, uint64_t i, const PosePod& pose,
+                                               int max_neighbors, int32_t* __restrict__ idx0, int32_t* __restrict__ idx1,
+                                               unsigned int* __restrict__ error) {
+  double q[3];
+  warp_point(pose, px[i], py[i], pz[i], q[0], q[1], q[2]);
+  TwoNearest best;
+  find_two_nearest(map, q, best, error);
+  const bool ok0 = best.j[0] != 0xFFFFFFFFu, ok1 = best.j[1] != 0xFFFFFFFFu && max_neighbors > 1;
+  idx0[i] = ok0 ? int32_t(best.j[0]) : -1;  // a position is < 2^31 (nos_ndt_map_create, store_reserve)
+  idx1[i] = ok1 ? int32_t(best.j[1]) : -1;
+  if constexpr (kSecondFirst) return int(ok1) + int(ok0);
+  return int(ok0) + int(ok1);
 }
 
 // One thread per scan point.  points: 3 planes of n doubles (local frame).
@@ -241,7 +275,7 @@ __global__ __launch_bounds__(256) void match_kernel(MapView map, const double* _
                                                     DST* __restrict__ dst,
                                                     unsigned long long* __restrict__ n_matches) {
   const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
-  const int found = i < n_points ? match_point<DST>(map, px, py, pz, i, pose, max_neighbors, L, dst) : 0;
+  const int found = i < n_points ? match_point<DST>(map, px, py, pz, i, pose, max_neighbors, L, dst, nullptr) : 0;
   add_match_count(found, n_matches);
 }
 
@@ -285,3 +319,19 @@ __global__ __launch_bounds__(256) void untile_kernel(const SRC* __restrict__ src
 }
 
 }  // namespace nos
+
+// match_kernel emitting voxel ids (positions in the map's cell-ordered arrays) instead of records.  Not a template, so
+// every unit that sees the definition compiles a copy: nos_indexed.hip, the one unit that launches it, asks for it.
+#ifdef NOS_WITH_MATCH_INDEX_KERNEL
+namespace {
+__global__ __launch_bounds__(256) void match_index_kernel(nos::MapView map, const double* __restrict__ px,
+                                                          const double* __restrict__ py, const double* __restrict__ pz,
+                                                          uint64_t n_points, nos::PosePod pose, int max_neighbors,
+                                                          int32_t* __restrict__ idx0, int32_t* __restrict__ idx1,
+                                                          unsigned long long* __restrict__ n_matches) {
+  const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+  const int found = i < n_points ? nos::match_point_ids<true>(map, px, py, pz, i, pose, max_neighbors, idx0, idx1, nullptr) : 0;
+  nos::add_match_count(found, n_matches);
+}
+}  // namespace
+#endif

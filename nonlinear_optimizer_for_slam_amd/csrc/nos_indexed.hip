@@ -1,5 +1,6 @@
 // nos_indexed.hip — voxel-indexed NDT datasets.  Kernel: assemble_indexed_kernel in assemble_kernels.hpp.
-#include "nos_internal.hpp"
+#define NOS_WITH_MATCH_INDEX_KERNEL  // match_kernels.hpp: this unit compiles (and launches) match_index_kernel
+#include "match_host.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -176,43 +177,11 @@ int nosd::indexed_from_device(nos_ctx* ctx, size_t n, const double* d_points, in
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) {
     nos_dataset_destroy(ds);
-    return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "indexed dataset build failed: %s",
-                hipGetErrorString(e));
+    return hip_fail(e, "indexed dataset build");
   }
   *out_ds = ds;
   return NOS_OK;
 }
-
-namespace {
-
-// like match_kernel, but emits voxel ids (positions in the map's cell-ordered arrays) instead of records
-__global__ __launch_bounds__(256) void match_index_kernel(nos::MapView map, const double* __restrict__ px,
-                                                          const double* __restrict__ py, const double* __restrict__ pz,
-                                                          uint64_t n_points, nos::PosePod pose, int max_neighbors,
-                                                          int32_t* __restrict__ idx0, int32_t* __restrict__ idx1,
-                                                          unsigned long long* __restrict__ n_matches) {
-  const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
-  int found = 0;
-  if (i < n_points) {
-    const double x = px[i], y = py[i], z = pz[i];
-    const double qx = pose.R[0] * x + pose.R[1] * y + pose.R[2] * z + pose.t[0];
-    const double qy = pose.R[3] * x + pose.R[4] * y + pose.R[5] * z + pose.t[1];
-    const double qz = pose.R[6] * x + pose.R[7] * y + pose.R[8] * z + pose.t[2];
-    nos::TwoNearest best;
-    nos::find_two_nearest(map, qx, qy, qz, best);
-    const uint32_t (&best_j)[2] = best.j;
-    const bool ok0 = best_j[0] != 0xFFFFFFFFu, ok1 = best_j[1] != 0xFFFFFFFFu && max_neighbors > 1;
-    idx0[i] = ok0 ? int32_t(best_j[0]) : -1;
-    idx1[i] = ok1 ? int32_t(best_j[1]) : -1;
-    found = int(ok0) + int(ok1);
-  }
-  int s = found;
-#pragma unroll
-  for (int o = nos::kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, nos::kWave);
-  if ((threadIdx.x & (nos::kWave - 1)) == 0 && s > 0) atomicAdd(n_matches, (unsigned long long)s);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -248,42 +217,28 @@ int nos_ndt_indexed_dataset_create(nos_ctx* ctx, size_t n_points, const double* 
     e = hipMemcpyAsync(d_idx + size_t(k) * n_points, index_planes[k], n_points * sizeof(int32_t), hipMemcpyHostToDevice, slot.stream);
   if (e == hipSuccess && n_voxels > 0) e = hipMemcpyAsync(d_means, means_xyz, n_voxels * 3 * sizeof(double), hipMemcpyHostToDevice, slot.stream);
   if (e == hipSuccess && n_voxels > 0) e = hipMemcpyAsync(d_S, sqrt_infos, n_voxels * 9 * sizeof(double), hipMemcpyHostToDevice, slot.stream);
-  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "indexed upload failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "indexed upload");
   return indexed_from_device(ctx, n_points, d_pts, n_slots, d_idx, n_voxels, d_means, d_S, nullptr, dtype, sort_by_voxel, out_ds);
 }
 
 int nos_ndt_match_indexed(nos_ndt_map* map, nos_scan* scan, const double R[9], const double t[3], int max_neighbors,
                           int dtype, int sort_by_voxel, nos_dataset** out_ds, size_t* n_matches) {
   nosd::CtxGuard guard_(map ? map->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  if (!map || !scan || !R || !t || !out_ds) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
-  *out_ds = nullptr;
-  if (map->ctx != scan->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "map and scan belong to different contexts");
-  if (max_neighbors < 1 || max_neighbors > 2) return fail(NOS_ERR_UNSUPPORTED, "max_neighbors must be 1 or 2");
-  nos_ctx* ctx = map->ctx;
-  DeviceSlot& slot = ctx->slots[0];
-  DeviceBuffers buf(&slot);
-  int32_t* d_idx = nullptr;
-  const size_t n = scan->n;
-  hipError_t e = hipSetDevice(slot.device);
-  if (e == hipSuccess) e = buf.alloc(&d_idx, 2 * n);
-  if (e == hipSuccess) e = hipMemsetAsync(map->d_n_matches, 0, sizeof(unsigned long long), slot.stream);
-  nos::PosePod pose;
-  for (int k = 0; k < 9; ++k) pose.R[k] = R[k];
-  for (int k = 0; k < 3; ++k) pose.t[k] = t[k];
-  if (e == hipSuccess && n > 0) {
-    hipLaunchKernelGGL(match_index_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, slot.stream, map->view, scan->d_planes,
-                       scan->d_planes + n, scan->d_planes + 2 * n, uint64_t(n), pose, max_neighbors, d_idx, d_idx + n,
-                       map->d_n_matches);
-    e = hipGetLastError();
-  }
-  unsigned long long count = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&count, map->d_n_matches, sizeof count, hipMemcpyDeviceToHost, slot.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(slot.stream);
-  if (e != hipSuccess) return fail(NOS_ERR_HIP, "indexed matching failed: %s", hipGetErrorString(e));
-  const int rc = indexed_from_device(ctx, n, scan->d_planes, max_neighbors, d_idx, map->n_voxels, map->d_mean, map->d_sqrt_info,
-                                     nullptr, dtype, sort_by_voxel, out_ds);
+  if (map && scan && R && t && out_ds) *out_ds = nullptr;  // cleared as soon as the pointers are known not to be NULL
+  int rc = check_match_call(map ? map->ctx : nullptr, scan, R, t, out_ds, max_neighbors);
   if (rc != NOS_OK) return rc;
-  if (n_matches) *n_matches = size_t(count);
+  nos_ctx* ctx = map->ctx;
+  DeviceBuffers buf(&ctx->slots[0]);
+  int32_t* d_idx = nullptr;
+  size_t count = 0;
+  rc = run_match_ids(SnapshotSource(map), match_index_kernel, ctx, buf, scan, make_pose(R, t), max_neighbors, &d_idx, &count,
+                     [](int32_t*) { return hipSuccess; });
+  if (rc != NOS_OK) return rc;
+  // ids are positions in the snapshot's cell-ordered arrays: those are the table
+  rc = indexed_from_device(ctx, scan->n, scan->d_planes, max_neighbors, d_idx, map->n_voxels, map->d_mean, map->d_sqrt_info,
+                           nullptr, dtype, sort_by_voxel, out_ds);
+  if (rc != NOS_OK) return rc;
+  if (n_matches) *n_matches = count;
   return NOS_OK;
 }
 

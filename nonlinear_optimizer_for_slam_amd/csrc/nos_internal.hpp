@@ -56,6 +56,11 @@ void pool_drain(DeviceSlot& slot);
                   "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
+// A failed HIP call outside a macro's reach → its status and "<what> failed: <HIP's text>".
+inline int hip_fail(hipError_t e, const char* what) {
+  return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+}
+
 // RCCL is bound at run time (dlopen) so that single-GPU use never needs it and so that a process
 // that already carries torch's copy of librccl shares that copy instead of loading a second one.
 struct RcclApi {
@@ -353,6 +358,14 @@ struct DeviceBuffers {
   }
 };
 
+// The pose the matcher and the store's insert warp a scan by, as their kernels take it.
+inline nos::PosePod make_pose(const double R[9], const double t[3]) {
+  nos::PosePod pose;
+  for (int k = 0; k < 9; ++k) pose.R[k] = R[k];
+  for (int k = 0; k < 3; ++k) pose.t[k] = t[k];
+  return pose;
+}
+
 // What one accumulate call computes; POD so the same code path serves all three problems.
 struct Request {
   int problem;  // 6, 3, 2 (reprojection)
@@ -455,23 +468,28 @@ int map_create_device(nos_ctx* ctx, size_t n_voxels, const double* d_means, cons
 // build's own kernel, so a segment's nine sums are the same bits from either)
 hipError_t launch_voxel_sums(const double* d_records, const uint32_t* sorted_idx, const uint32_t* seg_offset,
                              const uint32_t* seg_count, uint32_t n_voxels, double* acc_out, hipStream_t stream);
-// nos_voxelregister.hip: a batched registration against the live voxel store, for the entry points of nos_voxelmap.hip
-// (which own struct nos_voxel_map).  store == NULL: the map argument was NULL.
+// The live voxel store as whatever matches against it is handed it — the matcher of nos_voxelmap.hip (which owns struct
+// nos_voxel_map; its match source, match_host.hpp, derives from this) and the batched registration of
+// nos_voxelregister.hip.
 struct LiveStore {
   nos_ctx* ctx;
   nos::VoxelMatchView view;
-  unsigned int* d_probe_error;  // the store's kInfoProbeError word
-  double span;                  // cells the search ball spans per axis (check_match_span)
+  unsigned long long* d_count;  // the store's kInfoMatches words: the match counter of a lone match
+  unsigned int* d_error;        // the store's kInfoProbeError word
+  double span;                  // cells the search ball spans per axis: 2 r / resolution + 2
   bool broken;                  // an earlier failure left the store undefined
 };
-// The live matcher visits at most kVoxelMatchMaxSpan cells per axis: span = 2 r / resolution + 2 must not exceed it.
-inline int check_match_span(double span) {
-  if (span > double(nos::kVoxelMatchMaxSpan))
+// What a lone match and a registration reject of the store itself, in this order.  The live matcher visits at most
+// kVoxelMatchMaxSpan cells per axis.
+inline int check_live_store(const LiveStore& s) {
+  if (s.span > double(nos::kVoxelMatchMaxSpan))
     return fail(NOS_ERR_UNSUPPORTED,
                 "the search ball spans more than %d voxel cells per axis (2 r / resolution + 2 = %g): match against a snapshot",
-                nos::kVoxelMatchMaxSpan, span);
+                nos::kVoxelMatchMaxSpan, s.span);
+  if (s.broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
   return NOS_OK;
 }
+// nos_voxelregister.hip: a batched registration against the store.  store == NULL: the map argument was NULL.
 int register_live(int dof, const LiveStore* store, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
                   const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
                   nos_register_report* reports);

@@ -1,5 +1,5 @@
 // nos_match.hip — device correspondence matcher, scans, dataset download.
-#include "nos_internal.hpp"
+#include "match_host.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -259,7 +259,7 @@ int map_create_from_device(nos_ctx* ctx, size_t n_voxels, const double* d_means,
   if (e == hipSuccess) e = hipStreamSynchronize(st);  // the temporaries go out of scope
   if (e != hipSuccess) {
     nos_ndt_map_destroy(map);
-    return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "map tables failed: %s", hipGetErrorString(e));
+    return hip_fail(e, "map tables");
   }
   map->view.mean = map->d_mean;
   map->view.sqrt_info = map->d_sqrt_info;
@@ -316,8 +316,7 @@ int nos_ndt_map_create(nos_ctx* ctx, size_t n_voxels, const double* means_xyz, c
     if (e == hipSuccess) e = hipMemcpyAsync(d_S, sqrt_infos, n_voxels * 9 * sizeof(double), hipMemcpyHostToDevice, slot.stream);
     if (e == hipSuccess && valid) e = hipMemcpyAsync(d_valid, valid, n_voxels, hipMemcpyHostToDevice, slot.stream);
   }
-  if (e != hipSuccess)
-    return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "map upload failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e, "map upload");
   return map_create_from_device(ctx, n_voxels, d_means, d_S, d_valid, search_radius_sq, out_map);
 }
 
@@ -373,7 +372,7 @@ int nos_scan_create(nos_ctx* ctx, size_t n_points, const double* points_xyz, nos
   if (e != hipSuccess || rc != NOS_OK) {
     nos_scan_destroy(scan);
     if (rc != NOS_OK) return rc;
-    return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "scan upload failed: %s", hipGetErrorString(e));
+    return hip_fail(e, "scan upload");
   }
   *out_scan = scan;
   return NOS_OK;
@@ -394,49 +393,10 @@ size_t nos_scan_size(const nos_scan* scan) { return scan ? scan->n : 0; }
 int nos_ndt_match(nos_ndt_map* map, nos_scan* scan, const double R[9], const double t[3], int max_neighbors,
                   int dtype, nos_dataset** out_ds, size_t* n_matches) {
   nosd::CtxGuard guard_(map ? map->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  if (!map || !scan || !R || !t || !out_ds) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (map->ctx != scan->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "map and scan belong to different contexts");
-  if (max_neighbors < 1 || max_neighbors > 2) return fail(NOS_ERR_UNSUPPORTED, "max_neighbors must be 1 or 2");
-  nos_ctx* ctx = map->ctx;
-  nos_dataset* ds = nullptr;
-  int rc = dataset_new(ctx, kKindNdt, 2 * scan->n, dtype, out_ds, &ds);
+  const int rc = check_match_call(map ? map->ctx : nullptr, scan, R, t, out_ds, max_neighbors);
   if (rc != NOS_OK) return rc;
-  Shard& sh = ds->shards[0];
-  DeviceSlot& slot = ctx->slots[0];
-  nos::PosePod pose;
-  for (int k = 0; k < 9; ++k) pose.R[k] = R[k];
-  for (int k = 0; k < 3; ++k) pose.t[k] = t[k];
-  hipError_t e = hipSetDevice(slot.device);
-  if (e == hipSuccess) e = hipMemsetAsync(map->d_n_matches, 0, sizeof(unsigned long long), slot.stream);
-  if (e == hipSuccess && scan->n > 0) {
-    const dim3 grid(unsigned((scan->n + 255) / 256));
-    const double* px = scan->d_planes;
-    const double* py = scan->d_planes + scan->n;
-    const double* pz = scan->d_planes + 2 * scan->n;
-    if (dtype == NOS_F64)
-      hipLaunchKernelGGL((nos::match_kernel<double>), grid, dim3(256), 0, slot.stream, map->view, px, py, pz,
-                         uint64_t(scan->n), pose, max_neighbors, sh.layout, static_cast<double*>(sh.data),
-                         map->d_n_matches);
-    else
-      hipLaunchKernelGGL((nos::match_kernel<float>), grid, dim3(256), 0, slot.stream, map->view, px, py, pz,
-                         uint64_t(scan->n), pose, max_neighbors, sh.layout, static_cast<float*>(sh.data),
-                         map->d_n_matches);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess)
-    rc = zero_pad(dtype, nos::kNdtStored, sh.layout, sh.data, slot.stream);
-  unsigned long long count = 0;
-  if (e == hipSuccess && rc == NOS_OK)
-    e = hipMemcpyAsync(&count, map->d_n_matches, sizeof count, hipMemcpyDeviceToHost, slot.stream);
-  if (e == hipSuccess && rc == NOS_OK) e = hipStreamSynchronize(slot.stream);
-  if (e != hipSuccess || rc != NOS_OK) {
-    nos_dataset_destroy(ds);
-    if (rc != NOS_OK) return rc;
-    return fail(NOS_ERR_HIP, "matching failed: %s", hipGetErrorString(e));
-  }
-  if (n_matches) *n_matches = size_t(count);
-  *out_ds = ds;
-  return NOS_OK;
+  return run_match(SnapshotSource(map), nos::match_kernel<double>, nos::match_kernel<float>, map->ctx, scan, make_pose(R, t),
+                   max_neighbors, dtype, out_ds, n_matches);
 }
 
 int nos_dataset_drop_last_matches(nos_dataset* ds, size_t n_drop) {

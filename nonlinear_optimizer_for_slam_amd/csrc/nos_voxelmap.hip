@@ -1,5 +1,6 @@
 // nos_voxelmap.hip — incremental NDT voxel store: a device-resident map that grows scan by scan.
-#include "nos_internal.hpp"
+#define NOS_WITH_VOXEL_INDEX_KERNELS  // voxelmatch_kernels.hpp: this unit compiles (and launches) the two index kernels
+#include "match_host.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -28,10 +29,6 @@ struct nos_voxel_map {
 };
 
 namespace {
-
-inline int hip_fail(hipError_t e, const char* what) {
-  return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-}
 
 // Arrays and table for `capacity` slots in one allocation; the table's keys start empty.
 hipError_t store_alloc(size_t capacity, hipStream_t st, void** block, size_t* block_bytes, nos::VoxelStoreView* v) {
@@ -305,8 +302,9 @@ int store_prune(nos_voxel_map* vm, const nos::VoxelKeepRule& rule, size_t* n_rem
   return NOS_OK;
 }
 
-// The store as the live matcher reads it, and the cells its search ball spans per axis.
-nos::VoxelMatchView match_view(const nos_voxel_map* vm) {
+// The store as whatever matches against it is handed it: the view the live matcher reads (nothing of it is written), the
+// two words of d_info a match may write, the cells the search ball spans per axis.
+LiveStore live_store(const nos_voxel_map* vm) {
   const nos::VoxelStoreView& v = vm->view;
   nos::VoxelMatchView view{};
   view.table_key = v.table_key;
@@ -318,50 +316,58 @@ nos::VoxelMatchView match_view(const nos_voxel_map* vm) {
   view.inv_res = 1.0 / vm->voxel_resolution;  // what voxel_points_kernel is handed
   view.reach = std::sqrt(vm->search_radius_sq) + nos::kVoxelMatchGuard * vm->voxel_resolution;
   view.radius_sq = vm->search_radius_sq;
-  return view;
+  static_assert(nos::kInfoMatches % 2 == 0 && nos::kInfoMatches + 2 <= nos::kInfoWords, "info layout");
+  return LiveStore{vm->ctx, view, reinterpret_cast<unsigned long long*>(vm->d_info + nos::kInfoMatches),
+                   vm->d_info + nos::kInfoProbeError, 2.0 * std::sqrt(vm->search_radius_sq) / vm->voxel_resolution + 2.0,
+                   vm->broken};
 }
 
-double match_span(const nos_voxel_map* vm) { return 2.0 * std::sqrt(vm->search_radius_sq) / vm->voxel_resolution + 2.0; }
-
-// voxel_match_kernel emitting store slots instead of records: one lane per scan point, the search of
-// voxel_match_point, then idx0[i] / idx1[i] = slot of the nearest / second nearest voxel, or -1 (idx1 also when
-// max_neighbors = 1) — what match_index_kernel (nos_indexed.hip) is to match_kernel.
-__global__ __launch_bounds__(256) void voxel_match_index_kernel(nos::VoxelMatchView map, const double* __restrict__ px,
-                                                                const double* __restrict__ py, const double* __restrict__ pz,
-                                                                uint64_t n_points, nos::PosePod pose, int max_neighbors,
-                                                                int32_t* __restrict__ idx0, int32_t* __restrict__ idx1,
-                                                                unsigned long long* __restrict__ n_matches,
-                                                                unsigned int* __restrict__ error) {
-  const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
-  int found = 0;
-  if (i < n_points) {
-    nos::TwoNearest best;
-    nos::voxel_find_two_nearest(map, pose, px[i], py[i], pz[i], best, error);
-    const bool ok0 = best.j[0] != 0xFFFFFFFFu, ok1 = best.j[1] != 0xFFFFFFFFu && max_neighbors > 1;
-    idx0[i] = ok0 ? int32_t(best.j[0]) : -1;  // a slot is < 2^30 (store_reserve)
-    idx1[i] = ok1 ? int32_t(best.j[1]) : -1;
-    found = int(ok0) + int(ok1);
-  }
-  nos::add_match_count(found, n_matches);
+// What both matches against the store reject: check_match_call's list (the dtype in it, ahead of max_neighbors), then
+// what only a store adds.
+int check_store_match(const nos_voxel_map* vm, const nos_scan* scan, const double* R, const double* t, nos_dataset** out_ds,
+                      int max_neighbors, int dtype) {
+  const int rc = check_match_call(vm ? vm->ctx : nullptr, scan, R, t, out_ds, max_neighbors, dtype);
+  if (rc != NOS_OK) return rc;
+  if (vm->ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "matching against a voxel store needs a single-device context");
+  return check_live_store(live_store(vm));
 }
 
-// ids[i] (a store slot, or -1 which stays) → its rank in `rows`, the ascending list of the *n_rows distinct values of
-// ids (0xFFFFFFFF, the key of -1, last when present): a binary search in a list the size of the scan's footprint, which
-// stays in L2.  Every id is in the list.
-__global__ __launch_bounds__(256) void voxel_rank_ids_kernel(int32_t* __restrict__ ids, uint64_t n_ids,
-                                                             const uint32_t* __restrict__ rows,
-                                                             const uint32_t* __restrict__ n_rows) {
-  const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (i >= n_ids) return;
-  const int32_t id = ids[i];
-  if (id < 0) return;
-  uint32_t lo = 0, hi = *n_rows;  // first position with rows[pos] >= id
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (rows[mid] < uint32_t(id)) lo = mid + 1;
-    else hi = mid;
+// The compact table of an indexed match, queued behind the search that wrote `ids` — n_keys store slots
+// or -1 (plane 1, all -1 when max_neighbors = 1, is left out): *rows = the distinct ids, ascending (radix sort over the
+// bits a slot can have, then unique; 0xFFFFFFFF, the key of -1, last when some id is absent), every id replaced by its
+// rank among them, their number in *n_rows after the caller's wait.  All memory is the arena's, which the caller's
+// buf.reserve sized by the scan: nothing here allocates or waits while the search is in flight.
+hipError_t compact_ids(size_t capacity, DeviceSlot& slot, DeviceBuffers& buf, int32_t* ids, size_t n_keys, uint32_t** rows,
+                       uint32_t* n_rows) {
+  hipStream_t st = slot.stream;
+  int key_bits = 1;  // a slot is < capacity = 2^c, and -1 has bit c set: c + 1 bits order both
+  while ((size_t(1) << (key_bits - 1)) < capacity) ++key_bits;
+  uint32_t *sorted = nullptr, *d_n_rows = nullptr;
+  void* tmp = nullptr;
+  size_t t_sort = 0, t_unique = 0;
+  uint32_t* keys = reinterpret_cast<uint32_t*>(ids);  // -1 reads as 0xFFFFFFFF: after every slot
+  hipError_t e = buf.alloc(&sorted, n_keys);
+  if (e == hipSuccess) e = buf.alloc(rows, n_keys);
+  if (e == hipSuccess) e = buf.alloc(&d_n_rows, 1);
+  if (e == hipSuccess && n_keys > 0) e = rocprim::radix_sort_keys(nullptr, t_sort, keys, sorted, n_keys, 0, key_bits, st);
+  if (e == hipSuccess && n_keys > 0)
+    e = rocprim::unique(nullptr, t_unique, sorted, *rows, d_n_rows, n_keys, rocprim::equal_to<uint32_t>(), st);
+  if (e == hipSuccess) e = buf.alloc_bytes(&tmp, std::max(std::max(t_sort, t_unique), size_t(16)));
+  if (e == hipSuccess) e = hipMemsetAsync(d_n_rows, 0, sizeof(uint32_t), st);
+  if (e == hipSuccess && n_keys > 0) {
+    e = rocprim::radix_sort_keys(tmp, t_sort, keys, sorted, n_keys, 0, key_bits, st);
+    if (e == hipSuccess) e = rocprim::unique(tmp, t_unique, sorted, *rows, d_n_rows, n_keys, rocprim::equal_to<uint32_t>(), st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(voxel_rank_ids_kernel, dim3(unsigned((n_keys + 255) / 256)), dim3(256), 0, st, ids, uint64_t(n_keys),
+                         *rows, d_n_rows);
+      e = hipGetLastError();
+    }
+    // bracket profiling, SELF-REPORTED like start_match's launch: the kernel above and one per rocPRIM call (whose own
+    // launches depend on the number of keys and key bits)
+    if (slot.prof_on && slot.prof_every == 0) slot.prof_launches += 3;
   }
-  ids[i] = int32_t(lo);
+  if (e == hipSuccess) e = hipMemcpyAsync(n_rows, d_n_rows, sizeof *n_rows, hipMemcpyDeviceToHost, st);
+  return e;
 }
 
 int voxel_map_register(int dof, nos_voxel_map* vm, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
@@ -369,7 +375,7 @@ int voxel_map_register(int dof, nos_voxel_map* vm, nos_scan* const* scans, int32
                        nos_register_report* reports) {
   nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
   if (!vm) return register_live(dof, nullptr, scans, n_problems, R, t, loss, ropt, options, reports);
-  const LiveStore store{vm->ctx, match_view(vm), vm->d_info + nos::kInfoProbeError, match_span(vm), vm->broken};
+  const LiveStore store = live_store(vm);
   return register_live(dof, &store, scans, n_problems, R, t, loss, ropt, options, reports);
 }
 
@@ -424,10 +430,7 @@ int nos_voxel_map_insert_scan(nos_voxel_map* vm, nos_scan* scan, const double R[
   nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
   if (!vm || !scan || !R || !t) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
   if (vm->ctx != scan->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map and scan belong to different contexts");
-  nos::PosePod pose;
-  for (int k = 0; k < 9; ++k) pose.R[k] = R[k];
-  for (int k = 0; k < 3; ++k) pose.t[k] = t[k];
-  return store_insert(vm, scan->n, nullptr, scan->d_planes, pose, n_touched);
+  return store_insert(vm, scan->n, nullptr, scan->d_planes, make_pose(R, t), n_touched);
 }
 
 int nos_voxel_map_info(const nos_voxel_map* vm, size_t* n_voxels, size_t* n_valid, unsigned long long* n_points) {
@@ -491,159 +494,42 @@ int nos_voxel_map_snapshot(nos_voxel_map* vm, nos_ndt_map** out_map) {
 int nos_voxel_map_match(nos_voxel_map* vm, nos_scan* scan, const double R[9], const double t[3], int max_neighbors, int dtype,
                         nos_dataset** out_ds, size_t* n_matches) {
   nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  if (!vm || !scan || !R || !t || !out_ds) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (vm->ctx != scan->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map and scan belong to different contexts");
-  if (dtype != NOS_F64 && dtype != NOS_F32) return fail(NOS_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
-  if (max_neighbors < 1 || max_neighbors > 2) return fail(NOS_ERR_UNSUPPORTED, "max_neighbors must be 1 or 2");
-  nos_ctx* ctx = vm->ctx;
-  if (ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "matching against a voxel store needs a single-device context");
-  const int rc_span = check_match_span(match_span(vm));
-  if (rc_span != NOS_OK) return rc_span;
-  if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
-  nos_dataset* made = nullptr;
-  nos_dataset* ds = nullptr;
-  int rc = dataset_new(ctx, kKindNdt, 2 * scan->n, dtype, &made, &ds);  // *out_ds is written on success only
+  int rc = check_store_match(vm, scan, R, t, out_ds, max_neighbors, dtype);
   if (rc != NOS_OK) return rc;
-  Shard& sh = ds->shards[0];
-  DeviceSlot& slot = ctx->slots[0];
-  hipStream_t st = slot.stream;
-  nos::PosePod pose;
-  for (int k = 0; k < 9; ++k) pose.R[k] = R[k];
-  for (int k = 0; k < 3; ++k) pose.t[k] = t[k];
-  const nos::VoxelMatchView view = match_view(vm);
-  unsigned long long* d_count = reinterpret_cast<unsigned long long*>(vm->d_info + nos::kInfoMatches);
-  static_assert(nos::kInfoMatches % 2 == 0 && nos::kInfoMatches + 2 <= nos::kInfoWords, "info layout");
-  long launches = 0;
-  hipError_t e = hipSetDevice(slot.device);
-  if (e == hipSuccess) e = hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st);
-  if (e == hipSuccess) e = hipMemsetAsync(vm->d_info + nos::kInfoProbeError, 0, sizeof(unsigned int), st);
-  if (e == hipSuccess && scan->n > 0) {
-    const dim3 grid(unsigned((scan->n + 255) / 256));
-    const double* px = scan->d_planes;
-    const double* py = scan->d_planes + scan->n;
-    const double* pz = scan->d_planes + 2 * scan->n;
-    if (dtype == NOS_F64) {
-      hipLaunchKernelGGL((nos::voxel_match_kernel<double>), grid, dim3(256), 0, st, view, px, py, pz, uint64_t(scan->n), pose,
-                         max_neighbors, sh.layout, static_cast<double*>(sh.data), d_count, vm->d_info + nos::kInfoProbeError);
-      slot.last_kernel = reinterpret_cast<const void*>(&nos::voxel_match_kernel<double>);
-    } else {
-      hipLaunchKernelGGL((nos::voxel_match_kernel<float>), grid, dim3(256), 0, st, view, px, py, pz, uint64_t(scan->n), pose,
-                         max_neighbors, sh.layout, static_cast<float*>(sh.data), d_count, vm->d_info + nos::kInfoProbeError);
-      slot.last_kernel = reinterpret_cast<const void*>(&nos::voxel_match_kernel<float>);
-    }
-    e = hipGetLastError();
-    ++launches;
-  }
-  if (e == hipSuccess) {
-    rc = zero_pad(dtype, nos::kNdtStored, sh.layout, sh.data, st);  // the dataset's padding (no launch when there is none)
-    if (sh.layout.n_padded > sh.layout.n) ++launches;
-  }
-  // bracket profiling (nos_ctx_profile_begin with sample_every = 0): the count is SELF-REPORTED — this function tallies the
-  // launches it issues above, so a launch added to this call must be added to `launches` as well
-  if (slot.prof_on && slot.prof_every == 0) slot.prof_launches += launches;
-  unsigned long long count = 0;
-  unsigned int probe_error = 0;
-  if (e == hipSuccess && rc == NOS_OK) e = hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && rc == NOS_OK)
-    e = hipMemcpyAsync(&probe_error, vm->d_info + nos::kInfoProbeError, sizeof probe_error, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && rc == NOS_OK) e = hipStreamSynchronize(st);  // the one wait
-  if (e != hipSuccess || rc != NOS_OK || probe_error != 0) {
-    nos_dataset_destroy(ds);
-    if (rc != NOS_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "matching against the voxel store");
-    return fail(NOS_ERR_HIP, "matching against the voxel store failed: a table probe ran through the whole table");
-  }
-  if (n_matches) *n_matches = size_t(count);
-  *out_ds = ds;
-  return NOS_OK;
+  nos_dataset* ds = nullptr;  // *out_ds is written on success only
+  rc = run_match(StoreSource{live_store(vm)}, nos::voxel_match_kernel<double>, nos::voxel_match_kernel<float>, vm->ctx, scan,
+                 make_pose(R, t), max_neighbors, dtype, &ds, n_matches);
+  if (rc == NOS_OK) *out_ds = ds;
+  return rc;
 }
 
 int nos_voxel_map_match_indexed(nos_voxel_map* vm, nos_scan* scan, const double R[9], const double t[3], int max_neighbors,
                                 int dtype, int sort_by_voxel, nos_dataset** out_ds, size_t* n_matches) {
   nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
-  // the rejections of nos_voxel_map_match, in its order
-  if (!vm || !scan || !R || !t || !out_ds) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (vm->ctx != scan->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map and scan belong to different contexts");
-  if (dtype != NOS_F64 && dtype != NOS_F32) return fail(NOS_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
-  if (max_neighbors < 1 || max_neighbors > 2) return fail(NOS_ERR_UNSUPPORTED, "max_neighbors must be 1 or 2");
-  nos_ctx* ctx = vm->ctx;
-  if (ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "matching against a voxel store needs a single-device context");
-  const int rc_span = check_match_span(match_span(vm));
-  if (rc_span != NOS_OK) return rc_span;
-  if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+  int rc = check_store_match(vm, scan, R, t, out_ds, max_neighbors, dtype);
+  if (rc != NOS_OK) return rc;
+  const StoreSource src{live_store(vm)};
   const size_t n = scan->n;
   if (n >= (size_t(1) << 31)) return fail(NOS_ERR_UNSUPPORTED, "too many points for one indexed dataset");
+  nos_ctx* ctx = vm->ctx;
   DeviceSlot& slot = ctx->slots[0];
-  hipStream_t st = slot.stream;
-  nos::PosePod pose;
-  for (int k = 0; k < 9; ++k) pose.R[k] = R[k];
-  for (int k = 0; k < 3; ++k) pose.t[k] = t[k];
-  const nos::VoxelMatchView view = match_view(vm);
-  unsigned long long* d_count = reinterpret_cast<unsigned long long*>(vm->d_info + nos::kInfoMatches);
-  unsigned int* d_error = vm->d_info + nos::kInfoProbeError;
-  // Everything below is sized by the scan: the id planes, their sorted copy, the distinct list and rocPRIM's temporaries
-  // come from the context's arena, nothing from the store.
-  const size_t n_keys = n * size_t(max_neighbors);  // plane 1 is all -1 when max_neighbors = 1: not sorted, not ranked
-  int key_bits = 1;                                 // a slot is < capacity = 2^c, and -1 has bit c set: c + 1 bits order both
-  while ((size_t(1) << (key_bits - 1)) < vm->capacity) ++key_bits;
-  DeviceBuffers buf(&slot);
-  int32_t* d_idx = nullptr;
-  uint32_t *sorted = nullptr, *rows = nullptr, *d_rows_n = nullptr;
-  void* tmp = nullptr;
-  size_t t_sort = 0, t_unique = 0;
-  long launches = 0;
-  hipError_t e = hipSetDevice(slot.device);
+  const size_t n_keys = n * size_t(max_neighbors);
+  DeviceBuffers buf(&slot);  // the id planes, their sorted copy, the distinct list and rocPRIM's temporaries
   buf.reserve(2 * n * sizeof(int32_t) + 2 * n_keys * sizeof(uint32_t) + (size_t(1) << 20));
-  if (e == hipSuccess) e = buf.alloc(&d_idx, 2 * n);
-  if (e == hipSuccess) e = buf.alloc(&sorted, n_keys);
-  if (e == hipSuccess) e = buf.alloc(&rows, n_keys);
-  if (e == hipSuccess) e = buf.alloc(&d_rows_n, 1);
-  uint32_t* keys = reinterpret_cast<uint32_t*>(d_idx);  // -1 reads as 0xFFFFFFFF: after every slot
-  if (e == hipSuccess && n > 0) e = rocprim::radix_sort_keys(nullptr, t_sort, keys, sorted, n_keys, 0, key_bits, st);
-  if (e == hipSuccess && n > 0) e = rocprim::unique(nullptr, t_unique, sorted, rows, d_rows_n, n_keys, rocprim::equal_to<uint32_t>(), st);
-  if (e == hipSuccess) e = buf.alloc_bytes(&tmp, std::max(std::max(t_sort, t_unique), size_t(16)));
-  if (e == hipSuccess) e = hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_error, 0, sizeof(unsigned int), st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_rows_n, 0, sizeof(uint32_t), st);
-  if (e == hipSuccess && n > 0) {
-    // 1. the search: store slots (or -1) per point and slot plane
-    hipLaunchKernelGGL(voxel_match_index_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, view, scan->d_planes,
-                       scan->d_planes + n, scan->d_planes + 2 * n, uint64_t(n), pose, max_neighbors, d_idx, d_idx + n, d_count,
-                       d_error);
-    slot.last_kernel = reinterpret_cast<const void*>(&voxel_match_index_kernel);
-    e = hipGetLastError();
-    // 2. the distinct referenced slots, ascending: radix sort over the bits a slot can have, then unique
-    if (e == hipSuccess) e = rocprim::radix_sort_keys(tmp, t_sort, keys, sorted, n_keys, 0, key_bits, st);
-    if (e == hipSuccess) e = rocprim::unique(tmp, t_unique, sorted, rows, d_rows_n, n_keys, rocprim::equal_to<uint32_t>(), st);
-    // 3. every id → its rank among them
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(voxel_rank_ids_kernel, dim3(unsigned((n_keys + 255) / 256)), dim3(256), 0, st, d_idx, uint64_t(n_keys),
-                         rows, d_rows_n);
-      e = hipGetLastError();
-    }
-    launches += 4;
-  }
-  // bracket profiling: SELF-REPORTED like nos_voxel_map_match's tally — the two kernels above and one per rocPRIM call
-  // (whose own launches depend on the number of keys and key bits), not the dataset build's, which
-  // nos_ndt_match_indexed does not tally either
-  if (slot.prof_on && slot.prof_every == 0) slot.prof_launches += launches;
-  unsigned long long count = 0;
-  unsigned int probe_error = 0;
-  uint32_t n_rows = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(&probe_error, d_error, sizeof probe_error, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(&n_rows, d_rows_n, sizeof n_rows, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);  // wait 1 of 2: the table's size
-  if (e != hipSuccess) return hip_fail(e, "indexed matching against the voxel store");
-  if (probe_error != 0)
-    return fail(NOS_ERR_HIP, "indexed matching against the voxel store failed: a table probe ran through the whole table");
+  int32_t* d_idx = nullptr;
+  uint32_t *rows = nullptr, n_rows = 0;
+  size_t count = 0;
+  // 1. the search: store slots (or -1) per point and slot plane; 2. the compact table behind it, before the wait (1 of 2)
+  rc = run_match_ids(src, voxel_match_index_kernel, ctx, buf, scan, make_pose(R, t), max_neighbors, &d_idx, &count,
+                     [&](int32_t* ids) { return compact_ids(vm->capacity, slot, buf, ids, n_keys, &rows, &n_rows); });
+  if (rc != NOS_OK) return rc;
   // the list ends with the key of -1 exactly when some id is absent, i.e. when fewer than n_keys ids matched
   const size_t n_voxels = n_rows - ((n_rows > 0 && count < n_keys) ? 1u : 0u);
-  // 4. points, ids and the gathered table rows into one dataset (wait 2 of 2 inside); the sources are the store's own arrays
-  const int rc = indexed_from_device(ctx, n, scan->d_planes, max_neighbors, d_idx, n_voxels, view.mean, view.sqrt_info, rows,
-                                     dtype, sort_by_voxel, out_ds);
+  // 3. points, ids and the gathered table rows into one dataset (wait 2 of 2 inside); the sources are the store's own arrays
+  rc = indexed_from_device(ctx, n, scan->d_planes, max_neighbors, d_idx, n_voxels, src.view.mean, src.view.sqrt_info, rows, dtype,
+                           sort_by_voxel, out_ds);
   if (rc != NOS_OK) return rc;
-  if (n_matches) *n_matches = size_t(count);
+  if (n_matches) *n_matches = count;
   return NOS_OK;
 }
 

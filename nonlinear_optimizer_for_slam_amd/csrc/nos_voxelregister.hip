@@ -13,13 +13,13 @@ namespace {
 struct LiveLauncher {
   const LiveStore& store;
   static constexpr bool kTallyLaunch = true;
-  hipError_t prepare(hipStream_t stream) const { return hipMemsetAsync(store.d_probe_error, 0, sizeof(unsigned int), stream); }
+  hipError_t prepare(hipStream_t stream) const { return hipMemsetAsync(store.d_error, 0, sizeof(unsigned int), stream); }
   template <typename Problem, typename T>
   const void* launch(uint32_t n_blocks, const nos::RegisterDesc<typename Problem::Params>* d_descs,
                      nos::RegisterResult* d_results, nos::RegisterRound* d_log, const nos_register_options* ropt,
                      hipStream_t stream) const {
     const auto kernel = nos::register_live_kernel<Problem, T, kRegisterBlock>;
-    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kRegisterBlock), 0, stream, store.view, store.d_probe_error, d_descs,
+    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kRegisterBlock), 0, stream, store.view, store.d_error, d_descs,
                        d_results, d_log, ropt->max_outer_iterations, ropt->max_neighbors, ropt->keep_multiple);
     return reinterpret_cast<const void*>(kernel);
   }
@@ -32,12 +32,7 @@ int register_live(int dof, const LiveStore* store, nos_scan* const* scans, int32
                   nos_register_report* reports) {
   static const LiveStore no_store{};  // never launched with: a NULL map is rejected first
   const LiveStore& s = store ? *store : no_store;
-  auto more_checks = [&s] {  // what nos_voxel_map_match rejects, in its order
-    const int rc = check_match_span(s.span);
-    if (rc != NOS_OK) return rc;
-    if (s.broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
-    return int(NOS_OK);
-  };
+  auto more_checks = [&s] { return check_live_store(s); };  // what nos_voxel_map_match rejects, in its order
   return register_batch({dof, s.ctx, scans, n_problems, R, t, loss, ropt, options, reports}, more_checks, LiveLauncher{s});
 }
 

@@ -7,15 +7,16 @@
 // (voxel_table_find's probe sequence) in VoxelStoreView::table_key / table_slot.  Nothing is sorted, gathered or built
 // per frame: the work of a match follows the scan, not the size of the map.
 //
-// The result is, bit for bit, what match_kernel gives on a snapshot of the same store: the same warp (warp_point), the
-// same distance (match_dist), the same strict radius test, the same (distance, voxel id) order in TwoNearest — the slot
-// number IS the id a snapshot carries for the voxel — and the same record writer (write_match_records) reading the same
-// mean and sqrt-information values.  TwoNearest::offer keeps the two smallest (distance, id) pairs of whatever it is
-// offered, in any order, so only the SET of candidates matters: the visited cells must hold every valid voxel whose
-// mean can pass the radius test.  That is the guard band `g` (kVoxelMatchGuard of a cell edge; the argument is in
-// DESIGN.md §15): a mean lies in its own cell only up to the rounding of the sums and of the cell assignment.
+// The result is, bit for bit, what match_kernel gives on a snapshot of the same store: this header adds one overload of
+// find_two_nearest and nothing else of the matcher (match_point and match_point_ids of match_kernels.hpp, instantiated for
+// this view), with the same distance (match_dist), the same strict radius test and the same (distance, voxel id) order
+// in TwoNearest — the slot number IS the id a snapshot carries for the voxel, view.mean / view.sqrt_info the values it
+// copies.  TwoNearest::offer keeps the two smallest (distance, id) pairs of whatever it is offered, in any order, so only
+// the SET of candidates matters: the visited cells must hold every valid voxel whose mean can pass the radius test.  That
+// is the guard band `g` (kVoxelMatchGuard of a cell edge; the argument is in DESIGN.md §15): a mean lies in its own cell
+// only up to the rounding of the sums and of the cell assignment.
 //
-// Memory side: per (x, 3 x 3 block of y, z) step a lane of voxel_match_kernel issues NINE independent probes — key and slot of the first
+// Memory side: per (x, 3 x 3 block of y, z) step a lane issues NINE independent probes — key and slot of the first
 // table entry of every cell are loaded together, then valid flag and mean of every hit — so a 27-cell search is three
 // rounds of dependent loads, not 27; a collision (the table is at most half full) is resolved by a bounded loop
 // afterwards.  Consecutive z cells differ in the lowest key bits only, but the hash scatters them: what makes the lanes of
@@ -45,15 +46,12 @@ struct VoxelMatchView {
   double radius_sq;
 };
 
-// The search of the live matcher: scan point (x, y, z) warped by `pose`, the cells its ball touches, and the nine-probe
-// rounds into `best` — best.j[k] is the store slot of the k-th nearest valid voxel mean within the radius (ties by slot),
-// or 0xFFFFFFFF.  error: the store's kInfoProbeError word.  What voxel_match_point turns into records and
-// voxel_match_index_kernel (nos_voxelmap.hip) into slot ids: one search, so both forms name the same voxels.
-__device__ __forceinline__ void voxel_find_two_nearest(const VoxelMatchView& map, const PosePod& pose, double x, double y,
-                                                       double z, TwoNearest& best, unsigned int* __restrict__ error) {
+// find_two_nearest on the live store: the cells the ball around the warped point q touches, and the nine-probe rounds
+// into `best` — best.j[k] is the store slot of the k-th nearest valid voxel mean within the radius (ties by slot), or
+// 0xFFFFFFFF.  error: the store's kInfoProbeError word, raised when a probe runs through the whole table.
+__device__ __forceinline__ void find_two_nearest(const VoxelMatchView& map, const double (&q)[3], TwoNearest& best,
+                                                 unsigned int* __restrict__ error) {
   constexpr int kProbes = 9;  // the 3 x 3 block of (y, z) cells probed together per step
-  double q[3];
-  warp_point(pose, x, y, z, q[0], q[1], q[2]);
   // cells floor((q - r - g) inv_res) … floor((q + r + g) inv_res) per axis, clamped to the addressable grid
   // [-2^20, 2^20) that voxel_points_kernel admits — no voxel lives outside it, and pack_cell would fold a cell beyond
   // it onto a real key.  A point that is not finite, or whose range misses the grid altogether, visits no cell.
@@ -136,22 +134,6 @@ __device__ __forceinline__ void voxel_find_two_nearest(const VoxelMatchView& map
       }
 }
 
-// Scan point i (i < n_points) warped by `pose` and matched against the live store: writes slots 2i and 2i + 1 of the
-// dataset and returns the number of real matches among them (0-2) — match_point (match_kernels.hpp) on the store's table.
-// error: the store's kInfoProbeError word.  voxel_match_kernel (one thread per point) and register_live_kernel
-// (assemble_register_live.hpp, the lanes of one workgroup striding over a scan) both call this, so their records are the
-// same bits.
-template <typename DST>
-__device__ __forceinline__ int voxel_match_point(const VoxelMatchView& map, const double* __restrict__ px,
-                                                 const double* __restrict__ py, const double* __restrict__ pz, uint64_t i,
-                                                 const PosePod& pose, int max_neighbors, const TiledLayout& L,
-                                                 DST* __restrict__ dst, unsigned int* __restrict__ error) {
-  const double x = px[i], y = py[i], z = pz[i];
-  TwoNearest best;
-  voxel_find_two_nearest(map, pose, x, y, z, best, error);
-  return write_match_records<DST>(map.mean, map.sqrt_info, best.j, x, y, z, i, max_neighbors, L, dst);
-}
-
 // One thread per scan point.  points: 3 planes of n doubles (local frame).  error: the store's kInfoProbeError word.
 template <typename DST>
 __global__ __launch_bounds__(256) void voxel_match_kernel(VoxelMatchView map, const double* __restrict__ px,
@@ -160,8 +142,45 @@ __global__ __launch_bounds__(256) void voxel_match_kernel(VoxelMatchView map, co
                                                           DST* __restrict__ dst, unsigned long long* __restrict__ n_matches,
                                                           unsigned int* __restrict__ error) {
   const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
-  const int found = i < n_points ? voxel_match_point<DST>(map, px, py, pz, i, pose, max_neighbors, L, dst, error) : 0;
+  const int found = i < n_points ? match_point<DST>(map, px, py, pz, i, pose, max_neighbors, L, dst, error) : 0;
   add_match_count(found, n_matches);
 }
 
 }  // namespace nos
+
+// The two kernels of the voxel-indexed match against the store.  Not templates, so every unit that sees
+// the definitions compiles a copy: nos_voxelmap.hip, the one unit that launches them, asks for them.
+#ifdef NOS_WITH_VOXEL_INDEX_KERNELS
+namespace {
+// voxel_match_kernel emitting store slots instead of records: what match_index_kernel is to match_kernel.
+__global__ __launch_bounds__(256) void voxel_match_index_kernel(nos::VoxelMatchView map, const double* __restrict__ px,
+                                                                const double* __restrict__ py, const double* __restrict__ pz,
+                                                                uint64_t n_points, nos::PosePod pose, int max_neighbors,
+                                                                int32_t* __restrict__ idx0, int32_t* __restrict__ idx1,
+                                                                unsigned long long* __restrict__ n_matches,
+                                                                unsigned int* __restrict__ error) {
+  const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+  const int found = i < n_points ? nos::match_point_ids<false>(map, px, py, pz, i, pose, max_neighbors, idx0, idx1, error) : 0;
+  nos::add_match_count(found, n_matches);
+}
+
+// ids[i] (a store slot, or -1 which stays) → its rank in `rows`, the ascending list of the *n_rows distinct values of
+// ids (0xFFFFFFFF, the key of -1, last when present): a binary search in a list the size of the scan's footprint, which
+// stays in L2.  Every id is in the list.
+__global__ __launch_bounds__(256) void voxel_rank_ids_kernel(int32_t* __restrict__ ids, uint64_t n_ids,
+                                                             const uint32_t* __restrict__ rows,
+                                                             const uint32_t* __restrict__ n_rows) {
+  const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n_ids) return;
+  const int32_t id = ids[i];
+  if (id < 0) return;
+  uint32_t lo = 0, hi = *n_rows;  // first position with rows[pos] >= id
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (rows[mid] < uint32_t(id)) lo = mid + 1;
+    else hi = mid;
+  }
+  ids[i] = int32_t(lo);
+}
+}  // namespace
+#endif

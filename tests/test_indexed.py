@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle_scene as scene
-from tests import helpers
+from tests import exact_inputs, helpers
 
 pytestmark = pytest.mark.gpu
 LOSSES = [None, ("exponential", 1.0, 1.0), ("huber", 1.2)]
@@ -115,3 +115,85 @@ def test_indexed_empty_and_download(ctx):
     order = np.argsort(np.where(idx[0] < 0, 1 << 30, idx[0]), kind="stable")
     assert np.array_equal(got, pts[:, order])
     ds.close()
+
+
+def _exact_lattice_case():
+    """A 4 x 4 x 4 lattice of voxels with means on quarter positions (cell faces included) and the integer, upper-triangular
+    S of exact_inputs (U of S = QU is then S itself, so a table row holds the flat record's numbers), three of them
+    invalid; about 300 world points: named ones at the radius itself, one ulp-scale step inside and outside it, on ties,
+    far away, and a quarter lattice that brings ties and exact-radius candidates in numbers; the pose: a quarter turn
+    about z and a dyadic translation, so local = R^T (world - t) and the device's warp back are both exact.
+    → (means, S, valid, r2, local, R, t, idx [n][2] original voxel ids by (d2, id) or -1, d2 [n][2])"""
+    rng = np.random.default_rng(1812)
+    cells = np.array([[x, y, z] for x in range(4) for y in range(4) for z in range(4)], dtype=np.float64)
+    means = cells + rng.integers(0, 4, size=cells.shape) / 4.0
+    means[0] = [0.5, 0.5, 0.5]  # the corner voxel the named points probe from outside the lattice, and its neighbours
+    means[1] = [0.5, 0.5, 1.5]
+    means[4], means[16], means[20] = [0.75, 1.75, 0.75], [1.75, 0.75, 0.75], [1.75, 1.75, 0.75]
+    _, _, S = exact_inputs._ndt_chunk(5, 0, len(means), 3)
+    S = np.ascontiguousarray(np.moveaxis(S, 2, 0), dtype=np.float64)
+    valid = np.ones(len(means), dtype=bool)
+    valid[[7, 21, 40]] = False
+    r2, tiny = 1.0, 2.0 ** -40
+    a = means[0]
+    named = np.array([
+        a - [1.0, 0, 0], a - [0, 1.0, 0],                    # the radius itself: d2 = 1 is no match
+        a - [1.0 - tiny, 0, 0], a - [0, 0, 1.0 - tiny],      # just inside: d2 rounds to 1 - 2^-39
+        a - [1.0 + tiny, 0, 0], a - [0, 1.0 + tiny, 0],      # just outside
+        [0.5, 0.5, 1.0],                                     # equidistant from voxels 0 and 1: the lower id first
+        [40.0, 40.0, 40.0], [-9.0, 2.0, 2.0],                # nothing near
+    ])
+    world = np.concatenate([named, rng.integers(-4, 21, size=(290, 3)) / 4.0])
+    R = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+    t = np.array([0.5, -0.25, 0.125])
+    local = (world - t) @ R  # rows R^T (w - t)
+    assert np.array_equal(local @ R.T + t, world)
+    e = world[:, None, :] - means[None, :, :]
+    d = e[:, :, 0] * e[:, :, 0] + e[:, :, 1] * e[:, :, 1] + e[:, :, 2] * e[:, :, 2]  # one product is inexact at the most
+    d[:, ~valid] = np.inf
+    order = np.argsort(d, axis=1, kind="stable")[:, :2]  # ties: the lower id first
+    d2 = np.take_along_axis(d, order, axis=1)
+    idx = np.where(d2 < r2, order, -1)  # strict
+    assert idx[:9].tolist() == [[-1, -1], [-1, -1], [0, -1], [0, -1], [-1, -1], [-1, -1], [0, 1], [-1, -1], [-1, -1]]
+    assert d2[0, 0] == 1.0 and d2[2, 0] < 1.0 < d2[4, 0] and d2[6, 0] == d2[6, 1] == 0.25
+    assert int((d == r2).any(axis=1).sum()) > 5 and int(((d2[:, 0] == d2[:, 1]) & (d2[:, 0] < r2)).sum()) > 5  # and more of both
+    assert (idx[:, 0] < 0).sum() > 10 and ((idx[:, 0] >= 0) & (idx[:, 1] < 0)).sum() > 10
+    return means, S, valid, r2, local, R, t, idx, d2
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("k", [1, 2])
+def test_snapshot_indexed_names_the_voxels_the_flat_matcher_writes(ctx, k, dtype):
+    """On a snapshot map, under a pose that is not the identity, nos_ndt_match_indexed names — through its table — exactly
+    the voxels whose records nos_ndt_match writes: same count; table row ids[s][i] = the mean and sqrt-information planes
+    of flat record 2i + s, bit for bit (fp32: both narrowed the same way); -1 exactly where the flat record is all zero.
+    Both are the numpy brute force's voxels, with no tolerance."""
+    from nonlinear_optimizer_for_slam_amd import api
+    means, S, valid, r2, local, R, t, idx, _ = _exact_lattice_case()
+    n = len(local)
+    gm = api.NdtMap(ctx, means, S, valid, r2)
+    sc = api.Scan(ctx, local)
+    flat, n_flat = gm.match(sc, R, t, k, dtype)
+    ind, n_ind = gm.match_indexed(sc, R, t, k, dtype, sort_by_voxel=False)
+    planes, ids, table = api.download(flat), ind.ids(), ind.table()
+    for h in (flat, ind, sc, gm):
+        h.close()
+    assert planes.shape == (15, 2 * n) and ids.shape == (k, n) and table.shape == (int(valid.sum()), 16)
+    want = idx[:, :k]
+    assert n_flat == n_ind == int((want >= 0).sum())
+    upper, lower = [0, 1, 2, 4, 5, 8], [3, 6, 7]  # of the row-major S: the table holds U = S, the triangle
+    for s in range(2):
+        rec = planes[:, s::2]  # records 2i + s
+        empty = ~rec.any(axis=0)
+        if s >= k:
+            assert empty.all()
+            continue
+        assert np.array_equal(ids[s] < 0, empty) and np.array_equal(empty, want[:, s] < 0)
+        hit = ~empty
+        rows = table[ids[s][hit]]
+        assert rows[:, :3].tobytes() == np.ascontiguousarray(rec[3:6, hit].T).tobytes()
+        assert rows[:, 3:9].tobytes() == np.ascontiguousarray(rec[6:15, hit][upper].T).tobytes()
+        assert not rec[6:15][lower].any() and not rows[:, 9:].any()
+        assert np.array_equal(rec[0:3, hit].T, local[hit].astype(np.float32 if dtype == "f32" else np.float64))  # as stored
+        # the brute force's voxel: means are distinct, so the mean names it
+        assert np.array_equal(rows[:, :3], means[want[hit, s]]) and np.array_equal(rows[:, 3:9], S[want[hit, s]].reshape(-1, 9)[:, upper])
