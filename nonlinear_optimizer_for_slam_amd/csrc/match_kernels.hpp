@@ -58,6 +58,13 @@ __host__ __device__ __forceinline__ uint64_t pack_cell(int64_t ix, int64_t iy, i
          (uint64_t(iz + int64_t(bias)) & 0x1FFFFFull);
 }
 
+__host__ __device__ __forceinline__ void unpack_cell(uint64_t key, int32_t c[3]) {
+  const int32_t bias = 1 << 20;
+  c[0] = int32_t((key >> 42) & 0x1FFFFFull) - bias;
+  c[1] = int32_t((key >> 21) & 0x1FFFFFull) - bias;
+  c[2] = int32_t(key & 0x1FFFFFull) - bias;
+}
+
 __host__ __device__ __forceinline__ uint32_t hash_cell(uint64_t k) {
   k ^= k >> 33;
   k *= 0xff51afd7ed558ccdull;

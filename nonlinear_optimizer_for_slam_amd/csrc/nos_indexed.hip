@@ -1,8 +1,7 @@
-// nos_indexed.hip — voxel-indexed NDT datasets.  Kernel: assemble_indexed_kernel in assemble_kernels.hpp.
+// nos_indexed.hip — voxel-indexed NDT datasets (sort by voxel: group_host.hpp).  Kernel: assemble_indexed_kernel, assemble_kernels.hpp.
 #define NOS_WITH_MATCH_INDEX_KERNEL  // match_kernels.hpp: this unit compiles (and launches) match_index_kernel
+#include "group_host.hpp"
 #include "match_host.hpp"
-
-#include <rocprim/rocprim.hpp>
 
 using namespace nosd;
 
@@ -141,11 +140,10 @@ int nosd::indexed_from_device(nos_ctx* ctx, size_t n, const double* d_points, in
                          keys, ids);
       e = hipGetLastError();
     }
-    size_t tb = 0;
-    void* scratch = nullptr;
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tb, keys, keys_sorted, ids, perm, n, 0, 32, st);
-    if (e == hipSuccess) e = tmp.alloc_bytes(&scratch, std::max<size_t>(tb, 16));
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(scratch, tb, keys, keys_sorted, ids, perm, n, 0, 32, st);
+    PrimTmp t_sort;
+    const auto sort = [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, keys, keys_sorted, ids, perm, n, 0, 32, st); };
+    if (e == hipSuccess) e = prim_plan(tmp, sort, t_sort);
+    if (e == hipSuccess) e = prim_run(sort, t_sort);
   }
   if (e == hipSuccess) {
     const dim3 grid(unsigned((n_padded + 255) / 256));

@@ -1,7 +1,6 @@
-// nos_mapbuild.hip — NDT map construction on the device.
-#include "nos_internal.hpp"
-
-#include <rocprim/rocprim.hpp>
+// nos_mapbuild.hip — NDT map construction on the device and the scan's sort by cell.  Both key
+// their points through cell_keys and group them through group_host.hpp.
+#include "group_host.hpp"
 
 #include "mapbuild_kernels.hpp"
 
@@ -23,6 +22,62 @@ hipError_t nosd::launch_voxel_sums(const double* d_records, const uint32_t* sort
                      none, none, d_records, sorted_idx, seg_offset, seg_count, n_voxels, acc_out);
   return hipGetLastError();
 }
+
+namespace {
+
+// The cell keys of a point set, n > 0 points in three planes: keys[i] orders point i by its cell, lexicographically in
+// (x, y, z); idx[i] = i.  Box kernel, ONE wait, then the key kernel of the form the box admits — compact (the cell's index
+// inside the box, voxel_compact_key_kernel: same order, a third of the bits to sort) when the context allows it
+// (map_compact_keys), the box is not empty or inverted and the index fits 62 bits; packed (pack_cell, 64 bits) otherwise.
+struct CellKeys {
+  long long box[6] = {0x7FFFFFFFFFFFFFFFll, 0x7FFFFFFFFFFFFFFFll, 0x7FFFFFFFFFFFFFFFll,
+                      -0x7FFFFFFFFFFFFFFFll - 1, -0x7FFFFFFFFFFFFFFFll - 1, -0x7FFFFFFFFFFFFFFFll - 1};  // min, max per axis
+  long long dims[3] = {1, 1, 1};
+  bool compact = false;
+  unsigned bits = 64;
+  void cell(uint64_t k, int64_t c[3]) const {
+    const uint64_t nyz = uint64_t(dims[1]) * uint64_t(dims[2]);
+    c[0] = int64_t(k / nyz) + box[0];
+    c[1] = int64_t((k % nyz) / uint64_t(dims[2])) + box[1];
+    c[2] = int64_t(k % uint64_t(dims[2])) + box[2];
+  }
+};
+
+hipError_t cell_keys(const nos_ctx* ctx, DeviceBuffers& buf, hipStream_t st, const double* planes, size_t n, double inv_res,
+                     uint64_t* keys, uint32_t* idx, CellKeys* ck) {
+  const double *px = planes, *py = planes + n, *pz = planes + 2 * n;
+  long long* d_box = nullptr;
+  hipError_t e = buf.alloc(&d_box, 6);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_box, ck->box, sizeof ck->box, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(nos::voxel_box_kernel, dim3(unsigned(std::min<size_t>((n + 255) / 256, 1024))), dim3(256), 0, st, px, py, pz,
+                       uint64_t(n), inv_res, d_box);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(ck->box, d_box, sizeof ck->box, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return e;
+  const long long* box = ck->box;
+  if (ctx->settings.map_compact_keys != 0 && box[0] <= box[3] && box[1] <= box[4] && box[2] <= box[5]) {
+    double total = 1.0;
+    for (int k = 0; k < 3; ++k) total *= double(box[3 + k]) - double(box[k]) + 1.0;
+    if (total < 4.0e18) {  // the cell index fits 62 bits
+      ck->compact = true;
+      for (int k = 0; k < 3; ++k) ck->dims[k] = box[3 + k] - box[k] + 1;
+      ck->bits = 1;
+      while (ck->bits < 64 && double(1ull << ck->bits) < total) ++ck->bits;
+    }
+  }
+  const dim3 grid(unsigned((n + 255) / 256));
+  if (ck->compact)
+    hipLaunchKernelGGL(nos::voxel_compact_key_kernel, grid, dim3(256), 0, st, px, py, pz, uint64_t(n), inv_res, box[0], box[1],
+                       box[2], ck->dims[0], ck->dims[1], ck->dims[2], keys, idx);
+  else
+    hipLaunchKernelGGL(nos::voxel_key_kernel, grid, dim3(256), 0, st, px, py, pz, uint64_t(n), inv_res, keys, idx);
+  return hipGetLastError();
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -50,49 +105,14 @@ int nos_scan_sort_by_cell(nos_scan* scan, double cell_edge) {
   if (e == hipSuccess) e = buf.alloc(&idx, n);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&order), n * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sorted), n * 3 * sizeof(double));
-  // compact keys (see voxel_compact_key_kernel): the cell's index inside the scan's bounding box, same order, fewer bits
-  long long h_box[6] = {0x7FFFFFFFFFFFFFFFll, 0x7FFFFFFFFFFFFFFFll, 0x7FFFFFFFFFFFFFFFll,
-                        -0x7FFFFFFFFFFFFFFFll - 1, -0x7FFFFFFFFFFFFFFFll - 1, -0x7FFFFFFFFFFFFFFFll - 1};
-  long long dims[3] = {1, 1, 1};
-  bool compact = false;
-  unsigned key_bits = 64;
-  if (e == hipSuccess) {
-    long long* d_box = nullptr;
-    e = buf.alloc(&d_box, 6);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_box, h_box, sizeof h_box, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(nos::voxel_box_kernel, dim3(unsigned(std::min<size_t>((n + 255) / 256, 1024))), dim3(256), 0, st,
-                         scan->d_planes, scan->d_planes + n, scan->d_planes + 2 * n, uint64_t(n), 1.0 / cell_edge, d_box);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(h_box, d_box, sizeof h_box, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && scan->ctx->settings.map_compact_keys != 0 && h_box[0] <= h_box[3] && h_box[1] <= h_box[4] && h_box[2] <= h_box[5]) {
-      double total = 1.0;
-      for (int k = 0; k < 3; ++k) total *= double(h_box[3 + k]) - double(h_box[k]) + 1.0;
-      if (total < 4.0e18) {
-        compact = true;
-        for (int k = 0; k < 3; ++k) dims[k] = h_box[3 + k] - h_box[k] + 1;
-        key_bits = 1;
-        while (key_bits < 64 && double(1ull << key_bits) < total) ++key_bits;
-      }
-    }
-  }
+  CellKeys ck;
+  if (e == hipSuccess) e = cell_keys(scan->ctx, buf, st, scan->d_planes, n, 1.0 / cell_edge, keys, idx, &ck);
   if (e == hipSuccess) {
     const dim3 grid(unsigned((n + 255) / 256));
-    if (compact)
-      hipLaunchKernelGGL(nos::voxel_compact_key_kernel, grid, dim3(256), 0, st, scan->d_planes, scan->d_planes + n,
-                         scan->d_planes + 2 * n, uint64_t(n), 1.0 / cell_edge, h_box[0], h_box[1], h_box[2], dims[0], dims[1],
-                         dims[2], keys, idx);
-    else
-      hipLaunchKernelGGL(nos::voxel_key_kernel, grid, dim3(256), 0, st, scan->d_planes, scan->d_planes + n,
-                         scan->d_planes + 2 * n, uint64_t(n), 1.0 / cell_edge, keys, idx);
-    e = hipGetLastError();
-    size_t tmp_bytes = 0;
-    void* tmp = nullptr;
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys_sorted, idx, order, n, 0, key_bits, st);
-    if (e == hipSuccess) e = buf.alloc_bytes(&tmp, std::max(tmp_bytes, size_t(16)));
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_sorted, idx, order, n, 0, key_bits, st);
+    PrimTmp t_sort;
+    const auto sort = [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, keys, keys_sorted, idx, order, n, 0, ck.bits, st); };
+    e = prim_plan(buf, sort, t_sort);
+    if (e == hipSuccess) e = prim_run(sort, t_sort);
     for (int f = 0; f < 3 && e == hipSuccess; ++f) {
       hipLaunchKernelGGL((nos::gather_plane_kernel<double, double>), grid, dim3(256), 0, st, scan->d_planes + size_t(f) * n,
                          order, uint64_t(n), uint64_t(n), 0.0, sorted + size_t(f) * n);
@@ -183,73 +203,20 @@ int nos_ndt_map_build(nos_ctx* ctx, size_t n_points, const double* points_xyz, d
   DeviceSlot& slot = ctx->slots[0];
   hipStream_t st = slot.stream;
   DeviceBuffers buf(&slot);  // arena: slabs from the slot's buffer pool instead of ≈ 20 hipMalloc / hipFree pairs per build
-  uint64_t *keys = nullptr, *keys_sorted = nullptr, *uniq = nullptr;
-  uint32_t *idx = nullptr, *idx_sorted = nullptr, *counts = nullptr, *offsets = nullptr, *n_runs = nullptr;
+  KeyGroups<uint64_t> g;   // the points grouped by voxel: g.uniq = the voxels' keys, g.counts / g.offsets = their points in g.idx_sorted
+  CellKeys ck;
   hipError_t e = hipSetDevice(slot.device);
   const size_t n = n_points;
   buf.reserve(n * (3 * sizeof(uint64_t) + 4 * sizeof(uint32_t)) + (size_t(64) << 20));  // the seven n-sized arrays + sort temporaries
-  if (e == hipSuccess) e = buf.alloc(&keys, n);
-  if (e == hipSuccess) e = buf.alloc(&keys_sorted, n);
-  if (e == hipSuccess) e = buf.alloc(&idx, n);
-  if (e == hipSuccess) e = buf.alloc(&idx_sorted, n);
-  if (e == hipSuccess) e = buf.alloc(&uniq, n);
-  if (e == hipSuccess) e = buf.alloc(&counts, n);
-  if (e == hipSuccess) e = buf.alloc(&offsets, n);
-  if (e == hipSuccess) e = buf.alloc(&n_runs, 1);
-  const double* px = scan->d_planes;
-  const double* py = scan->d_planes + n;
-  const double* pz = scan->d_planes + 2 * n;
+  if (e == hipSuccess) e = g.arrays(buf, st, n);
+  const double *px = scan->d_planes, *py = px + n, *pz = py + n;
   uint32_t V = 0;
-  // compact keys: cell index inside the points' bounding box (voxel_compact_key_kernel) — same order, a third of the bits
-  long long h_box[6] = {0x7FFFFFFFFFFFFFFFll, 0x7FFFFFFFFFFFFFFFll, 0x7FFFFFFFFFFFFFFFll,
-                        -0x7FFFFFFFFFFFFFFFll - 1, -0x7FFFFFFFFFFFFFFFll - 1, -0x7FFFFFFFFFFFFFFFll - 1};
-  long long dims[3] = {1, 1, 1};
-  bool compact = false;
-  unsigned key_bits = 64;
   if (e == hipSuccess && n > 0) {
-    long long* d_box = nullptr;
-    e = buf.alloc(&d_box, 6);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_box, h_box, sizeof h_box, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-      const unsigned blocks = unsigned(std::min<size_t>((n + 255) / 256, 1024));
-      hipLaunchKernelGGL(nos::voxel_box_kernel, dim3(blocks), dim3(256), 0, st, px, py, pz, uint64_t(n), 1.0 / voxel_resolution, d_box);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(h_box, d_box, sizeof h_box, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && ctx->settings.map_compact_keys != 0 && h_box[0] <= h_box[3] && h_box[1] <= h_box[4] && h_box[2] <= h_box[5]) {
-      double total = 1.0;
-      for (int k = 0; k < 3; ++k) {
-        const double d = double(h_box[3 + k]) - double(h_box[k]) + 1.0;
-        total *= d;
-      }
-      if (total < 4.0e18) {  // the cell index fits 62 bits
-        compact = true;
-        for (int k = 0; k < 3; ++k) dims[k] = h_box[3 + k] - h_box[k] + 1;
-        key_bits = 1;
-        while (key_bits < 64 && double(1ull << key_bits) < total) ++key_bits;
-      }
-    }
-  }
-  if (e == hipSuccess && n > 0) {
-    if (compact)
-      hipLaunchKernelGGL(nos::voxel_compact_key_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, px, py, pz, uint64_t(n),
-                         1.0 / voxel_resolution, h_box[0], h_box[1], h_box[2], dims[0], dims[1], dims[2], keys, idx);
-    else
-      hipLaunchKernelGGL(nos::voxel_key_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, px, py, pz, uint64_t(n),
-                         1.0 / voxel_resolution, keys, idx);
-    e = hipGetLastError();
-    size_t t1 = 0, t2 = 0, t3 = 0;
-    void* tmp = nullptr;
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, t1, keys, keys_sorted, idx, idx_sorted, n, 0, key_bits, st);
-    if (e == hipSuccess) e = rocprim::run_length_encode(nullptr, t2, keys_sorted, n, uniq, counts, n_runs, st);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, t3, counts, offsets, 0u, n, rocprim::plus<uint32_t>(), st);
-    if (e == hipSuccess) e = buf.alloc_bytes(&tmp, std::max(std::max(t1, t2), std::max(t3, size_t(16))));
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, t1, keys, keys_sorted, idx, idx_sorted, n, 0, key_bits, st);
-    if (e == hipSuccess) e = rocprim::run_length_encode(tmp, t2, keys_sorted, n, uniq, counts, n_runs, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&V, n_runs, sizeof V, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && V > 0) e = rocprim::exclusive_scan(tmp, t3, counts, offsets, 0u, size_t(V), rocprim::plus<uint32_t>(), st);
+    e = cell_keys(ctx, buf, st, scan->d_planes, n, 1.0 / voxel_resolution, g.keys, g.idx, &ck);  // the box wait
+    if (e == hipSuccess) e = g.temporaries(buf, ck.bits);
+    if (e == hipSuccess) e = g.queue(&V);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // the run-count wait
+    if (e == hipSuccess) e = g.queue_offsets(V);
   }
   std::unique_ptr<nos_map_stats> stats(new (std::nothrow) nos_map_stats());
   if (!stats) e = hipErrorOutOfMemory;
@@ -266,7 +233,7 @@ int nos_ndt_map_build(nos_ctx* ctx, size_t n_points, const double* points_xyz, d
     if (e == hipSuccess) e = buf.alloc(&d_evecs, size_t(V) * 9);
     if (e == hipSuccess) e = buf.alloc(&d_first, size_t(V));
     if (e == hipSuccess)
-      e = launch_map_exact(px, py, pz, idx_sorted, offsets, counts, V, ctx->settings.map_fma_mask,
+      e = launch_map_exact(px, py, pz, g.idx_sorted, g.offsets, g.counts, V, ctx->settings.map_fma_mask,
                            ctx->settings.map_eigen_version, d_acc, d_mean, d_S, d_valid, d_evals, d_evecs, d_first, st);
   } else if (e == hipSuccess && V > 0) {
     const nos::MapBuildParams prm{5, 0.01, 0.01, (flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0};
@@ -281,9 +248,9 @@ int nos_ndt_map_build(nos_ctx* ctx, size_t n_points, const double* points_xyz, d
         d_rec = nullptr;
       }
       const unsigned blocks = unsigned((size_t(V) * nos::kWave + 255) / 256);
-      hipLaunchKernelGGL(nos::voxel_sums_kernel, dim3(blocks), dim3(256), 0, st, px, py, pz, d_rec, idx_sorted, offsets, counts, V,
+      hipLaunchKernelGGL(nos::voxel_sums_kernel, dim3(blocks), dim3(256), 0, st, px, py, pz, d_rec, g.idx_sorted, g.offsets, g.counts, V,
                          d_acc);
-      hipLaunchKernelGGL(nos::voxel_eigen_kernel, dim3(unsigned((size_t(V) + 255) / 256)), dim3(256), 0, st, d_acc, counts, V,
+      hipLaunchKernelGGL(nos::voxel_eigen_kernel, dim3(unsigned((size_t(V) + 255) / 256)), dim3(256), 0, st, d_acc, g.counts, V,
                          prm, d_mean, d_S, d_valid);
       e = hipGetLastError();
     }
@@ -292,27 +259,14 @@ int nos_ndt_map_build(nos_ctx* ctx, size_t n_points, const double* points_xyz, d
   // and hash table are built there); they travel to the host only for the caller's nos_map_stats and for the reference-exact
   // mode, whose voxel list is re-ordered to first-seen order before the tables are built.
   const bool want_stats = out_stats != nullptr || exact;
-  std::vector<uint64_t> h_keys(want_stats ? V : 0);
+  std::vector<uint64_t> h_keys;
   std::vector<uint32_t> h_first;
+  if (e == hipSuccess && want_stats) e = download_stats(V, d_mean, d_S, d_valid, g.counts, g.uniq, st, stats.get(), &h_keys);
   if (e == hipSuccess && exact) {
     stats->evals.resize(size_t(V) * 3);
     stats->evecs.resize(size_t(V) * 9);
     h_first.resize(V);
-  }
-  if (e == hipSuccess && want_stats) {
-    stats->means.resize(size_t(V) * 3);
-    stats->sqrt_infos.resize(size_t(V) * 9);
-    stats->valid.resize(V);
-    stats->counts.resize(V);
-    stats->cells.resize(size_t(V) * 3);
-  }
-  if (e == hipSuccess && V > 0 && want_stats) {
-    e = hipMemcpyAsync(stats->means.data(), d_mean, size_t(V) * 3 * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(stats->sqrt_infos.data(), d_S, size_t(V) * 9 * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(stats->valid.data(), d_valid, V, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(stats->counts.data(), counts, size_t(V) * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_keys.data(), uniq, size_t(V) * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && exact) {
+    if (V > 0) {
       e = hipMemcpyAsync(stats->evals.data(), d_evals, size_t(V) * 3 * sizeof(double), hipMemcpyDeviceToHost, st);
       if (e == hipSuccess) e = hipMemcpyAsync(stats->evecs.data(), d_evecs, size_t(V) * 9 * sizeof(double), hipMemcpyDeviceToHost, st);
       if (e == hipSuccess) e = hipMemcpyAsync(h_first.data(), d_first, size_t(V) * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
@@ -329,19 +283,9 @@ int nos_ndt_map_build(nos_ctx* ctx, size_t n_points, const double* points_xyz, d
   nos_scan_destroy(scan);
   if (e != hipSuccess)
     return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "map build failed: %s", hipGetErrorString(e));
-  const int64_t bias = int64_t(1) << 20;
-  for (uint32_t v = 0; v < V && want_stats; ++v) {
-    if (compact) {
-      const uint64_t k = h_keys[v], nyz = uint64_t(dims[1]) * uint64_t(dims[2]);
-      stats->cells[3 * size_t(v) + 0] = int64_t(k / nyz) + h_box[0];
-      stats->cells[3 * size_t(v) + 1] = int64_t((k % nyz) / uint64_t(dims[2])) + h_box[1];
-      stats->cells[3 * size_t(v) + 2] = int64_t(k % uint64_t(dims[2])) + h_box[2];
-    } else {
-      stats->cells[3 * size_t(v) + 0] = int64_t((h_keys[v] >> 42) & 0x1FFFFFull) - bias;
-      stats->cells[3 * size_t(v) + 1] = int64_t((h_keys[v] >> 21) & 0x1FFFFFull) - bias;
-      stats->cells[3 * size_t(v) + 2] = int64_t(h_keys[v] & 0x1FFFFFull) - bias;
-    }
-  }
+  if (want_stats && !ck.compact) cells_from_packed_keys(h_keys, stats.get());
+  if (want_stats && ck.compact)
+    for (uint32_t v = 0; v < V; ++v) ck.cell(h_keys[v], &stats->cells[3 * size_t(v)]);
   if (exact && V > 1) {
     // the reference's map lists its voxels as they were first seen (our restatement of its unordered_map walk): voxel
     // ids — the matcher's tie-break — then agree with the reference-exact CPU restatement's

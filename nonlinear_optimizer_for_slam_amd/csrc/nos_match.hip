@@ -1,7 +1,7 @@
-// nos_match.hip — device correspondence matcher, scans, dataset download.
+// nos_match.hip — the matcher's tables from device-resident voxel statistics (grouped by cell through group_host.hpp), the
+// snapshot matcher, scans, dataset download.
+#include "group_host.hpp"
 #include "match_host.hpp"
-
-#include <rocprim/rocprim.hpp>
 
 using namespace nosd;
 
@@ -121,9 +121,12 @@ __global__ __launch_bounds__(256) void map_cell_tables_kernel(const uint64_t* __
   }
 }
 
-// Builds the map object from DEVICE arrays of voxel statistics (means [V][3], sqrt-informations [V][9], valid [V] or null).
-int map_create_from_device(nos_ctx* ctx, size_t n_voxels, const double* d_means, const double* d_S, const unsigned char* d_valid,
-                           double search_radius_sq, nos_ndt_map** out_map) {
+}  // namespace
+
+// Builds the map object from DEVICE arrays of voxel statistics (means [V][3], sqrt-informations [V][9], valid [V] or null):
+// nos_ndt_map_create's uploaded copies, the build's (nos_mapbuild.hip) and the store's own (nos_voxelmap.hip).
+int nosd::map_create_device(nos_ctx* ctx, size_t n_voxels, const double* d_means, const double* d_S, const unsigned char* d_valid,
+                            double search_radius_sq, nos_ndt_map** out_map) {
   const double inv_cell = 1.0 / std::sqrt(search_radius_sq);
   DeviceSlot& slot = ctx->slots[0];
   hipStream_t st = slot.stream;
@@ -133,43 +136,29 @@ int map_create_from_device(nos_ctx* ctx, size_t n_voxels, const double* d_means,
   map->ctx = ctx;
   DeviceBuffers buf(&slot);  // arena (pooled slabs) for the temporaries
   buf.reserve(std::max<size_t>(V, 1) * (3 * sizeof(uint64_t) + 3 * sizeof(uint32_t)) + (size_t(16) << 20));
-  uint64_t *keys = nullptr, *keys_sorted = nullptr, *uniq = nullptr;
-  uint32_t *idx = nullptr, *run_count = nullptr, *run_start = nullptr, *n_runs = nullptr;
+  // the voxels grouped by matcher cell, a cell's in index order (stable sort, as std::sort on (key, index) pairs left them)
+  KeyGroups<uint64_t> g;
   unsigned int *flags = nullptr, *box = nullptr;
   hipError_t e = hipSetDevice(slot.device);
-  const size_t cap = std::max<size_t>(V, 1);
-  if (e == hipSuccess) e = buf.alloc(&keys, cap);
-  if (e == hipSuccess) e = buf.alloc(&keys_sorted, cap);
-  if (e == hipSuccess) e = buf.alloc(&uniq, cap);
-  if (e == hipSuccess) e = buf.alloc(&idx, cap);
-  if (e == hipSuccess) e = buf.alloc(&run_count, cap);
-  if (e == hipSuccess) e = buf.alloc(&run_start, cap);
-  if (e == hipSuccess) e = buf.alloc(&n_runs, 1);
-  if (e == hipSuccess) e = buf.alloc(&flags, 4);
-  if (e == hipSuccess) e = buf.alloc(&box, 6);
+  const size_t cap = std::max<size_t>(V, 1);  // of d_orig_id, which the map keeps; the arena's arrays hold at least one too
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&map->d_orig_id), cap * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&map->d_n_matches), sizeof(unsigned long long));
+  if (e == hipSuccess) e = g.arrays(buf, st, V, map->d_orig_id);
+  if (e == hipSuccess) e = g.temporaries(buf, 64);
+  if (e == hipSuccess) e = buf.alloc(&flags, 4);
+  if (e == hipSuccess) e = buf.alloc(&box, 6);
   uint32_t runs = 0, n_cells = 0, n_valid = 0;
   unsigned int h_flags[4] = {0, 0, 0, 0}, h_box[6] = {0, 0, 0, 0, 0, 0};
-  size_t t_sort = 0, t_rle = 0, t_scan = 0;
-  void* tmp = nullptr;
   if (e == hipSuccess && V > 0) {
     const unsigned int box_init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
     e = hipMemsetAsync(flags, 0, 4 * sizeof(unsigned int), st);
     if (e == hipSuccess) e = hipMemcpyAsync(box, box_init, sizeof box_init, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(map_cell_key_kernel, dim3((V + 255) / 256), dim3(256), 0, st, d_means, d_valid, V, inv_cell, keys, idx,
+      hipLaunchKernelGGL(map_cell_key_kernel, dim3((V + 255) / 256), dim3(256), 0, st, d_means, d_valid, V, inv_cell, g.keys, g.idx,
                          flags);
       e = hipGetLastError();
     }
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, t_sort, keys, keys_sorted, idx, map->d_orig_id, size_t(V), 0, 64, st);
-    if (e == hipSuccess) e = rocprim::run_length_encode(nullptr, t_rle, keys_sorted, size_t(V), uniq, run_count, n_runs, st);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, t_scan, run_count, run_start, 0u, size_t(V), rocprim::plus<uint32_t>(), st);
-    if (e == hipSuccess) e = buf.alloc_bytes(&tmp, std::max(std::max(t_sort, t_rle), std::max(t_scan, size_t(16))));
-    // stable: the voxels of a cell stay in index order, as std::sort on (key, index) pairs left them
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, t_sort, keys, keys_sorted, idx, map->d_orig_id, size_t(V), 0, 64, st);
-    if (e == hipSuccess) e = rocprim::run_length_encode(tmp, t_rle, keys_sorted, size_t(V), uniq, run_count, n_runs, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&runs, n_runs, sizeof runs, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = g.queue(&runs);
     if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, sizeof h_flags, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess && h_flags[0] != 0) {
@@ -184,16 +173,16 @@ int map_create_from_device(nos_ctx* ctx, size_t n_voxels, const double* d_means,
       // the invalid voxels, if any, form the last run (key = all ones)
       uint64_t last_key = 0;
       uint32_t last_count = 0;
-      e = hipMemcpyAsync(&last_key, uniq + (runs - 1), sizeof last_key, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(&last_count, run_count + (runs - 1), sizeof last_count, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, t_scan, run_count, run_start, 0u, size_t(runs), rocprim::plus<uint32_t>(), st);
+      e = hipMemcpyAsync(&last_key, g.uniq + (runs - 1), sizeof last_key, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(&last_count, g.counts + (runs - 1), sizeof last_count, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = g.queue_offsets(runs);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
       const bool has_invalid = last_key == nos::kEmptyCell;
       n_cells = has_invalid ? runs - 1 : runs;
       n_valid = has_invalid ? V - last_count : V;
     }
     if (e == hipSuccess && n_cells > 0) {
-      hipLaunchKernelGGL(map_cell_box_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, st, uniq, n_cells, box);
+      hipLaunchKernelGGL(map_cell_box_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, st, g.uniq, n_cells, box);
       e = hipGetLastError();
       if (e == hipSuccess) e = hipMemcpyAsync(h_box, box, sizeof h_box, hipMemcpyDeviceToHost, st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -243,17 +232,16 @@ int map_create_from_device(nos_ctx* ctx, size_t n_voxels, const double* d_means,
   if (e == hipSuccess && n_valid > 0) {
     hipLaunchKernelGGL(map_gather_kernel, dim3((n_valid + 255) / 256), dim3(256), 0, st, d_means, d_S, map->d_orig_id, n_valid,
                        map->d_mean, map->d_sqrt_info, map->d_record);
-    hipLaunchKernelGGL(map_cell_tables_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, st, uniq, run_count, run_start, n_cells,
+    hipLaunchKernelGGL(map_cell_tables_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, st, g.uniq, g.counts, g.offsets, n_cells,
                        uint32_t(table_size - 1), reinterpret_cast<unsigned long long*>(map->d_cell_key), map->d_cell_start,
                        map->d_cell_count, map->d_dense_begin, lo[0], lo[1], lo[2], dim[1], dim[2]);
     e = hipGetLastError();
     if (e == hipSuccess && n_dense > 0) {
-      size_t t_inc = 0;
-      void* tmp2 = nullptr;
-      e = rocprim::inclusive_scan(nullptr, t_inc, map->d_dense_begin, map->d_dense_begin, n_dense + 1, rocprim::plus<uint32_t>(), st);
-      if (e == hipSuccess) e = buf.alloc_bytes(&tmp2, std::max<size_t>(t_inc, 16));
-      if (e == hipSuccess)
-        e = rocprim::inclusive_scan(tmp2, t_inc, map->d_dense_begin, map->d_dense_begin, n_dense + 1, rocprim::plus<uint32_t>(), st);
+      PrimTmp t_dense;  // counts per dense cell → where each cell's records end
+      uint32_t* dense = map->d_dense_begin;
+      const auto dense_ends = [&](void* t, size_t& b) { return rocprim::inclusive_scan(t, b, dense, dense, n_dense + 1, rocprim::plus<uint32_t>(), st); };
+      e = prim_plan(buf, dense_ends, t_dense);
+      if (e == hipSuccess) e = prim_run(dense_ends, t_dense);
     }
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);  // the temporaries go out of scope
@@ -282,14 +270,6 @@ int map_create_from_device(nos_ctx* ctx, size_t n_voxels, const double* d_means,
   return NOS_OK;
 }
 
-}  // namespace
-
-// nos_mapbuild.hip: the voxel statistics are already on the device
-int nosd::map_create_device(nos_ctx* ctx, size_t n_voxels, const double* d_means, const double* d_S, const unsigned char* d_valid,
-                            double search_radius_sq, nos_ndt_map** out_map) {
-  return map_create_from_device(ctx, n_voxels, d_means, d_S, d_valid, search_radius_sq, out_map);
-}
-
 extern "C" {
 
 int nos_ndt_map_create(nos_ctx* ctx, size_t n_voxels, const double* means_xyz, const double* sqrt_infos,
@@ -302,7 +282,7 @@ int nos_ndt_map_create(nos_ctx* ctx, size_t n_voxels, const double* means_xyz, c
   if (!(search_radius_sq > 0.0) || !std::isfinite(search_radius_sq)) return fail(NOS_ERR_INVALID_ARGUMENT, "bad search radius");
   if (n_voxels >= 0xFFFFFFFFull) return fail(NOS_ERR_UNSUPPORTED, "too many voxels");
   // the voxel statistics go to the device as they are; bucketing by matcher cell, the hash table and the dense grid are
-  // built there (map_create_from_device)
+  // built there (map_create_device)
   DeviceSlot& slot = ctx->slots[0];
   DeviceBuffers buf(&slot);
   double *d_means = nullptr, *d_S = nullptr;
@@ -317,7 +297,7 @@ int nos_ndt_map_create(nos_ctx* ctx, size_t n_voxels, const double* means_xyz, c
     if (e == hipSuccess && valid) e = hipMemcpyAsync(d_valid, valid, n_voxels, hipMemcpyHostToDevice, slot.stream);
   }
   if (e != hipSuccess) return hip_fail(e, "map upload");
-  return map_create_from_device(ctx, n_voxels, d_means, d_S, d_valid, search_radius_sq, out_map);
+  return map_create_device(ctx, n_voxels, d_means, d_S, d_valid, search_radius_sq, out_map);
 }
 
 int nos_ndt_map_destroy(nos_ndt_map* map) {

@@ -1,8 +1,6 @@
 // nos_scanfilter.hip — voxel-grid filter of a device-resident scan (nos_scan_filter) and the way back to the host
-// (nos_scan_points).  The kernels and the algorithm: scan_filter_kernels.hpp.
-#include "nos_internal.hpp"
-
-#include <rocprim/rocprim.hpp>
+// (nos_scan_points).  The kernels and the algorithm: scan_filter_kernels.hpp; the select: a rocPRIM call through group_host.hpp.
+#include "group_host.hpp"
 
 #include "scan_filter_kernels.hpp"
 
@@ -48,8 +46,7 @@ int nos_scan_filter(nos_scan* scan, double voxel_size, nos_scan** out_scan) {
     void* table = nullptr;
     uint32_t *entry = nullptr, *kept = nullptr, *d_count = nullptr;
     unsigned int* info = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
+    PrimTmp t_select;
     e = buf.alloc_bytes(&table, table_size * (sizeof(uint64_t) + sizeof(uint32_t)));
     if (e == hipSuccess) e = buf.alloc(&entry, n);
     if (e == hipSuccess) e = buf.alloc(&kept, n);
@@ -59,8 +56,8 @@ int nos_scan_filter(nos_scan* scan, double voxel_size, nos_scan** out_scan) {
     uint32_t* tab_first = reinterpret_cast<uint32_t*>(tab_key + table_size);
     const nos::ScanFilterKeep keep{tab_first, entry, scan->d_order};
     const rocprim::counting_iterator<uint32_t> positions(0u);
-    if (e == hipSuccess) e = rocprim::select(nullptr, tmp_bytes, positions, kept, d_count, n, keep, st);
-    if (e == hipSuccess) e = buf.alloc_bytes(&tmp, std::max(tmp_bytes, size_t(16)));
+    const auto select = [&](void* tmp, size_t& bytes) { return rocprim::select(tmp, bytes, positions, kept, d_count, n, keep, st); };
+    if (e == hipSuccess) e = prim_plan(buf, select, t_select);
     // free entries are kEmptyCell and first = 0xFFFFFFFF: one fill of all-ones bytes over both arrays
     if (e == hipSuccess) e = hipMemsetAsync(table, 0xFF, table_size * (sizeof(uint64_t) + sizeof(uint32_t)), st);
     if (e == hipSuccess) e = hipMemsetAsync(info, 0, sizeof h_info, st);
@@ -70,7 +67,7 @@ int nos_scan_filter(nos_scan* scan, double voxel_size, nos_scan** out_scan) {
                          uint32_t(table_size - 1), entry, info);
       e = hipGetLastError();
     }
-    if (e == hipSuccess) e = rocprim::select(tmp, tmp_bytes, positions, kept, d_count, n, keep, st);
+    if (e == hipSuccess) e = prim_run(select, t_select);
     if (e == hipSuccess) e = hipMemcpyAsync(&n_kept, d_count, sizeof n_kept, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(h_info, info, sizeof h_info, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);  // the one wait: the kept count sizes the new scan

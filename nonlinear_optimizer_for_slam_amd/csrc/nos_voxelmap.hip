@@ -1,8 +1,8 @@
-// nos_voxelmap.hip — incremental NDT voxel store: a device-resident map that grows scan by scan.
+// nos_voxelmap.hip — incremental NDT voxel store: a device-resident map that grows scan by scan; a batch
+// is grouped by voxel through group_host.hpp (§19), matched against through match_host.hpp (§18).
 #define NOS_WITH_VOXEL_INDEX_KERNELS  // voxelmatch_kernels.hpp: this unit compiles (and launches) the two index kernels
+#include "group_host.hpp"
 #include "match_host.hpp"
-
-#include <rocprim/rocprim.hpp>
 
 #include "voxelmap_kernels.hpp"
 #include "voxelmatch_kernels.hpp"
@@ -63,6 +63,24 @@ hipError_t store_alloc(size_t capacity, hipStream_t st, void** block, size_t* bl
   return hipSuccess;
 }
 
+// How store_reserve and store_prune end (e, probe_error: what filling the new block gave, after the wait that lets the old
+// one go): a failure frees the new block and leaves the store untouched; else the store's arrays and table are the new ones.
+int adopt_block(nos_voxel_map* vm, hipError_t e, unsigned int probe_error, const char* what, const char* overflow, void* block,
+                size_t block_bytes, const nos::VoxelStoreView& view, size_t capacity) {
+  if (e != hipSuccess || probe_error != 0) {
+    (void)hipFree(block);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return fail(NOS_ERR_HIP, "%s", overflow);
+  }
+  (void)hipFree(vm->d_block);
+  vm->d_block = block;
+  vm->block_bytes = block_bytes;
+  vm->view = view;
+  vm->capacity = capacity;
+  ++vm->generation;
+  return NOS_OK;
+}
+
 // Room for `need` slots: arrays and table double (new allocation, device copies, every key hashed into the new table)
 // until they hold them.  The store is untouched when this fails.
 int store_reserve(nos_voxel_map* vm, size_t need) {
@@ -96,19 +114,9 @@ int store_reserve(nos_voxel_map* vm, size_t need) {
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&err, vm->d_info + nos::kInfoProbeError, sizeof err, hipMemcpyDeviceToHost, st);
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the old block is freed below
-  if (e != hipSuccess || err != 0) {
-    (void)hipFree(block);
-    if (e != hipSuccess) return hip_fail(e, "growing the voxel store");
-    return fail(NOS_ERR_HIP, "growing the voxel store failed: the new table overflowed");
-  }
-  (void)hipFree(vm->d_block);
-  vm->d_block = block;
-  vm->block_bytes = block_bytes;
-  vm->view = nv;
-  vm->capacity = capacity;
-  ++vm->generation;
-  return NOS_OK;
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the old block is freed by adopt_block
+  return adopt_block(vm, e, err, "growing the voxel store", "growing the voxel store failed: the new table overflowed", block,
+                     block_bytes, nv, capacity);
 }
 
 // One insert.  host_xyz != nullptr: [n][3] in the map frame; otherwise d_planes = 3 planes of n doubles in a local frame,
@@ -125,27 +133,14 @@ int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const doub
   hipStream_t st = slot.stream;
   DeviceBuffers buf(&slot);  // arena: every temporary comes from the slot's buffer pool — no hipMalloc / hipFree per insert
   double *rec = nullptr, *staged = nullptr, *seg_acc = nullptr;
-  uint64_t *keys = nullptr, *keys_sorted = nullptr, *uniq = nullptr;
-  uint32_t *idx = nullptr, *idx_sorted = nullptr, *counts = nullptr, *offsets = nullptr, *n_runs = nullptr;
+  KeyGroups<uint64_t> g;  // the batch grouped by voxel: a run = the points of one voxel, in point order
   uint32_t *run_slot = nullptr, *miss = nullptr, *rank = nullptr;
   hipError_t e = hipSetDevice(slot.device);
   buf.reserve(n * (7 * sizeof(double) + 3 * sizeof(uint64_t) + 4 * sizeof(uint32_t)) + (size_t(16) << 20));
   if (e == hipSuccess) e = buf.alloc(&rec, n * 4);
   if (e == hipSuccess && host_xyz) e = buf.alloc(&staged, n * 3);
-  if (e == hipSuccess) e = buf.alloc(&keys, n);
-  if (e == hipSuccess) e = buf.alloc(&keys_sorted, n);
-  if (e == hipSuccess) e = buf.alloc(&uniq, n);
-  if (e == hipSuccess) e = buf.alloc(&idx, n);
-  if (e == hipSuccess) e = buf.alloc(&idx_sorted, n);
-  if (e == hipSuccess) e = buf.alloc(&counts, n);
-  if (e == hipSuccess) e = buf.alloc(&offsets, n);
-  if (e == hipSuccess) e = buf.alloc(&n_runs, 1);
-  size_t t1 = 0, t2 = 0, t3 = 0;
-  void* tmp = nullptr;
-  if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, t1, keys, keys_sorted, idx, idx_sorted, n, 0, 63, st);
-  if (e == hipSuccess) e = rocprim::run_length_encode(nullptr, t2, keys_sorted, n, uniq, counts, n_runs, st);
-  if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, t3, counts, offsets, 0u, n, rocprim::plus<uint32_t>(), st);
-  if (e == hipSuccess) e = buf.alloc_bytes(&tmp, std::max(std::max(t1, t2), std::max(t3, size_t(16))));
+  if (e == hipSuccess) e = g.arrays(buf, st, n);
+  if (e == hipSuccess) e = g.temporaries(buf, 63);  // all planning ahead of the first kernel
   // step 1: records, keys, the finite / in-range check
   unsigned int h_info[nos::kInfoWords] = {};
   uint32_t U = 0;
@@ -155,18 +150,16 @@ int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const doub
     const dim3 grid(unsigned((n + 255) / 256));
     const double inv_res = 1.0 / vm->voxel_resolution;
     if (host_xyz)
-      hipLaunchKernelGGL((nos::voxel_points_kernel<false>), grid, dim3(256), 0, st, staged, uint64_t(n), pose, inv_res, rec, keys,
-                         idx, vm->d_info);
+      hipLaunchKernelGGL((nos::voxel_points_kernel<false>), grid, dim3(256), 0, st, staged, uint64_t(n), pose, inv_res, rec, g.keys,
+                         g.idx, vm->d_info);
     else
-      hipLaunchKernelGGL((nos::voxel_points_kernel<true>), grid, dim3(256), 0, st, d_planes, uint64_t(n), pose, inv_res, rec, keys,
-                         idx, vm->d_info);
+      hipLaunchKernelGGL((nos::voxel_points_kernel<true>), grid, dim3(256), 0, st, d_planes, uint64_t(n), pose, inv_res, rec, g.keys,
+                         g.idx, vm->d_info);
     e = hipGetLastError();
   }
   // step 2: stable sort of (packed key, index), run-length encode.  The packed key orders cells exactly as the build's
   // compact in-box key does, so a run's points are summed in the order the build sums them.
-  if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, t1, keys, keys_sorted, idx, idx_sorted, n, 0, 63, st);
-  if (e == hipSuccess) e = rocprim::run_length_encode(tmp, t2, keys_sorted, n, uniq, counts, n_runs, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(&U, n_runs, sizeof U, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = g.queue(&U);
   if (e == hipSuccess) e = hipMemcpyAsync(h_info, vm->d_info, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);  // the one wait in the middle: run count and flags
   if (e != hipSuccess) return hip_fail(e, "voxel store insert (sort)");
@@ -179,26 +172,25 @@ int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const doub
   int rc = store_reserve(vm, size_t(vm->n_voxels) + U);  // load factor <= 1/2 whatever the number of new voxels
   if (rc != NOS_OK) return rc;
   buf.reserve(size_t(U) * (9 * sizeof(double) + 3 * sizeof(uint32_t)) + (size_t(1) << 20));
-  size_t t4 = 0;
-  void* tmp4 = nullptr;
+  PrimTmp t_rank;
+  const auto rank_misses = [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, miss, rank, 0u, size_t(U), rocprim::plus<uint32_t>(), st); };
   e = buf.alloc(&seg_acc, size_t(U) * 9);
   if (e == hipSuccess) e = buf.alloc(&run_slot, U);
   if (e == hipSuccess) e = buf.alloc(&miss, U);
   if (e == hipSuccess) e = buf.alloc(&rank, U);
-  if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, t4, miss, rank, 0u, size_t(U), rocprim::plus<uint32_t>(), st);
-  if (e == hipSuccess) e = buf.alloc_bytes(&tmp4, std::max(t4, size_t(16)));
-  if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, t3, counts, offsets, 0u, size_t(U), rocprim::plus<uint32_t>(), st);
+  if (e == hipSuccess) e = prim_plan(buf, rank_misses, t_rank);
+  if (e == hipSuccess) e = g.queue_offsets(U);
   if (e != hipSuccess) return hip_fail(e, "voxel store insert (segments)");
   // step 3: the build's sums kernel on the batch; step 4: lookup, rank of the misses, merge + finish
   const nos::MapBuildParams prm{5, 0.01, 0.01, (vm->flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0};
-  e = launch_voxel_sums(rec, idx_sorted, offsets, counts, U, seg_acc, st);
+  e = launch_voxel_sums(rec, g.idx_sorted, g.offsets, g.counts, U, seg_acc, st);
   if (e != hipSuccess) return hip_fail(e, "voxel store insert (sums)");
   const dim3 ugrid(unsigned((size_t(U) + 255) / 256));
-  hipLaunchKernelGGL(nos::voxel_lookup_kernel, ugrid, dim3(256), 0, st, vm->view, uniq, U, run_slot, miss, vm->d_info);
+  hipLaunchKernelGGL(nos::voxel_lookup_kernel, ugrid, dim3(256), 0, st, vm->view, g.uniq, U, run_slot, miss, vm->d_info);
   e = hipGetLastError();
-  if (e == hipSuccess) e = rocprim::exclusive_scan(tmp4, t4, miss, rank, 0u, size_t(U), rocprim::plus<uint32_t>(), st);
+  if (e == hipSuccess) e = prim_run(rank_misses, t_rank);
   if (e != hipSuccess) return hip_fail(e, "voxel store insert (lookup)");  // still nothing written
-  hipLaunchKernelGGL(nos::voxel_merge_kernel, ugrid, dim3(256), 0, st, vm->view, uniq, counts, seg_acc, run_slot, rank, U, prm,
+  hipLaunchKernelGGL(nos::voxel_merge_kernel, ugrid, dim3(256), 0, st, vm->view, g.uniq, g.counts, seg_acc, run_slot, rank, U, prm,
                      uint32_t(vm->epoch + 1), vm->d_info);
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(h_info, vm->d_info, 5 * sizeof(unsigned int), hipMemcpyDeviceToHost, st);
@@ -229,14 +221,13 @@ int store_prune(nos_voxel_map* vm, const nos::VoxelKeepRule& rule, size_t* n_rem
   hipStream_t st = slot.stream;
   DeviceBuffers buf(&slot);
   uint32_t *keep = nullptr, *new_slot = nullptr;
-  size_t t1 = 0;
-  void* tmp = nullptr;
+  PrimTmp t_slots;
+  const auto new_slots = [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, keep, new_slot, 0u, V, rocprim::plus<uint32_t>(), st); };
   hipError_t e = hipSetDevice(slot.device);
   buf.reserve(V * 2 * sizeof(uint32_t) + (size_t(1) << 20));
   if (e == hipSuccess) e = buf.alloc(&keep, V);
   if (e == hipSuccess) e = buf.alloc(&new_slot, V);
-  if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, t1, keep, new_slot, 0u, V, rocprim::plus<uint32_t>(), st);
-  if (e == hipSuccess) e = buf.alloc_bytes(&tmp, std::max(t1, size_t(16)));
+  if (e == hipSuccess) e = prim_plan(buf, new_slots, t_slots);
   // removed voxels, their points (two words), valid voxels kept: words kInfoRemoved … kInfoKeptValid
   unsigned int totals[4] = {0, 0, 0, 0};
   static_assert(nos::kInfoKeptValid == nos::kInfoRemoved + 3 && nos::kInfoRemovedPoints == nos::kInfoRemoved + 1, "info layout");
@@ -246,7 +237,7 @@ int store_prune(nos_voxel_map* vm, const nos::VoxelKeepRule& rule, size_t* n_rem
     hipLaunchKernelGGL(nos::voxel_keep_kernel, grid, dim3(256), 0, st, vm->view, rule, keep, vm->d_info);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, t1, keep, new_slot, 0u, V, rocprim::plus<uint32_t>(), st);
+  if (e == hipSuccess) e = prim_run(new_slots, t_slots);
   if (e == hipSuccess) e = hipMemcpyAsync(totals, vm->d_info + nos::kInfoRemoved, sizeof totals, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);  // the one wait: what goes?
   if (e != hipSuccess) return hip_fail(e, "voxel store prune (keep)");
@@ -276,28 +267,19 @@ int store_prune(nos_voxel_map* vm, const nos::VoxelKeepRule& rule, size_t* n_rem
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(&err, vm->d_info + nos::kInfoProbeError, sizeof err, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the closing wait: the old block is freed below
-  if (e != hipSuccess || err != 0) {
-    (void)hipFree(block);
-    if (e != hipSuccess) return hip_fail(e, "voxel store prune (compact)");
-    return fail(NOS_ERR_HIP, "voxel store prune failed: the new table overflowed");
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the closing wait: the old block is freed by adopt_block
+  const char* what = "voxel store prune (compact)";
+  if (e == hipSuccess && err == 0) {
+    // the device-side valid counter follows (in stream order before any later merge)
+    e = hipMemcpyAsync(vm->d_info + nos::kInfoValid, vm->d_info + nos::kInfoKeptValid, sizeof(unsigned int),
+                       hipMemcpyDeviceToDevice, st);
+    what = "voxel store prune (counter)";
   }
-  // the device-side valid counter follows (in stream order before any later merge)
-  e = hipMemcpyAsync(vm->d_info + nos::kInfoValid, vm->d_info + nos::kInfoKeptValid, sizeof(unsigned int),
-                     hipMemcpyDeviceToDevice, st);
-  if (e != hipSuccess) {
-    (void)hipFree(block);
-    return hip_fail(e, "voxel store prune (counter)");
-  }
-  (void)hipFree(vm->d_block);
-  vm->d_block = block;
-  vm->block_bytes = block_bytes;
-  vm->view = nv;
-  vm->capacity = capacity;
+  const int rc = adopt_block(vm, e, err, what, "voxel store prune failed: the new table overflowed", block, block_bytes, nv, capacity);
+  if (rc != NOS_OK) return rc;
   vm->n_voxels = uint32_t(kept);
   vm->n_valid = totals[3];
   vm->n_points -= removed_points;
-  ++vm->generation;
   if (n_removed) *n_removed = removed;
   return NOS_OK;
 }
@@ -343,20 +325,20 @@ hipError_t compact_ids(size_t capacity, DeviceSlot& slot, DeviceBuffers& buf, in
   int key_bits = 1;  // a slot is < capacity = 2^c, and -1 has bit c set: c + 1 bits order both
   while ((size_t(1) << (key_bits - 1)) < capacity) ++key_bits;
   uint32_t *sorted = nullptr, *d_n_rows = nullptr;
-  void* tmp = nullptr;
-  size_t t_sort = 0, t_unique = 0;
+  PrimTmp t_sort, t_unique;
   uint32_t* keys = reinterpret_cast<uint32_t*>(ids);  // -1 reads as 0xFFFFFFFF: after every slot
+  const auto sort = [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, keys, sorted, n_keys, 0, key_bits, st); };
+  const auto unique = [&](void* t, size_t& b) { return rocprim::unique(t, b, sorted, *rows, d_n_rows, n_keys, rocprim::equal_to<uint32_t>(), st); };
   hipError_t e = buf.alloc(&sorted, n_keys);
   if (e == hipSuccess) e = buf.alloc(rows, n_keys);
   if (e == hipSuccess) e = buf.alloc(&d_n_rows, 1);
-  if (e == hipSuccess && n_keys > 0) e = rocprim::radix_sort_keys(nullptr, t_sort, keys, sorted, n_keys, 0, key_bits, st);
-  if (e == hipSuccess && n_keys > 0)
-    e = rocprim::unique(nullptr, t_unique, sorted, *rows, d_n_rows, n_keys, rocprim::equal_to<uint32_t>(), st);
-  if (e == hipSuccess) e = buf.alloc_bytes(&tmp, std::max(std::max(t_sort, t_unique), size_t(16)));
+  if (e == hipSuccess && n_keys > 0) e = prim_size(sort, t_sort);
+  if (e == hipSuccess && n_keys > 0) e = prim_size(unique, t_unique);
+  if (e == hipSuccess) e = prim_share(buf, {&t_sort, &t_unique});
   if (e == hipSuccess) e = hipMemsetAsync(d_n_rows, 0, sizeof(uint32_t), st);
   if (e == hipSuccess && n_keys > 0) {
-    e = rocprim::radix_sort_keys(tmp, t_sort, keys, sorted, n_keys, 0, key_bits, st);
-    if (e == hipSuccess) e = rocprim::unique(tmp, t_unique, sorted, *rows, d_n_rows, n_keys, rocprim::equal_to<uint32_t>(), st);
+    e = prim_run(sort, t_sort);
+    if (e == hipSuccess) e = prim_run(unique, t_unique);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(voxel_rank_ids_kernel, dim3(unsigned((n_keys + 255) / 256)), dim3(256), 0, st, ids, uint64_t(n_keys),
                          *rows, d_n_rows);
@@ -552,32 +534,14 @@ int nos_voxel_map_stats(nos_voxel_map* vm, nos_map_stats** out_stats) {
   *out_stats = nullptr;
   std::unique_ptr<nos_map_stats> stats(new (std::nothrow) nos_map_stats());
   if (!stats) return fail(NOS_ERR_OUT_OF_MEMORY, "host allocation failed");
-  const size_t V = vm->n_voxels;
-  std::vector<uint64_t> h_keys(V);
-  stats->means.resize(V * 3);
-  stats->sqrt_infos.resize(V * 9);
-  stats->valid.resize(V);
-  stats->counts.resize(V);
-  stats->cells.resize(V * 3);
-  if (V > 0) {
-    DeviceSlot& slot = vm->ctx->slots[0];
-    hipStream_t st = slot.stream;
-    const nos::VoxelStoreView& v = vm->view;
-    hipError_t e = hipSetDevice(slot.device);
-    if (e == hipSuccess) e = hipMemcpyAsync(stats->means.data(), v.mean, V * 3 * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(stats->sqrt_infos.data(), v.sqrt_info, V * 9 * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(stats->valid.data(), v.valid, V, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(stats->counts.data(), v.count, V * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_keys.data(), v.key, V * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(e, "voxel store download");
-  }
-  const int64_t bias = int64_t(1) << 20;
-  for (size_t s = 0; s < V; ++s) {
-    stats->cells[3 * s + 0] = int64_t((h_keys[s] >> 42) & 0x1FFFFFull) - bias;
-    stats->cells[3 * s + 1] = int64_t((h_keys[s] >> 21) & 0x1FFFFFull) - bias;
-    stats->cells[3 * s + 2] = int64_t(h_keys[s] & 0x1FFFFFull) - bias;
-  }
+  std::vector<uint64_t> h_keys;
+  DeviceSlot& slot = vm->ctx->slots[0];
+  const nos::VoxelStoreView& v = vm->view;
+  hipError_t e = vm->n_voxels > 0 ? hipSetDevice(slot.device) : hipSuccess;
+  if (e == hipSuccess) e = download_stats(vm->n_voxels, v.mean, v.sqrt_info, v.valid, v.count, v.key, slot.stream, stats.get(), &h_keys);
+  if (e == hipSuccess && vm->n_voxels > 0) e = hipStreamSynchronize(slot.stream);
+  if (e != hipSuccess) return hip_fail(e, "voxel store download");
+  cells_from_packed_keys(h_keys, stats.get());
   *out_stats = stats.release();
   return NOS_OK;
 }

@@ -214,13 +214,6 @@ struct VoxelKeepRule {
   int use_box, use_age;
 };
 
-__host__ __device__ __forceinline__ void unpack_cell(uint64_t key, int32_t c[3]) {
-  const int32_t bias = 1 << 20;
-  c[0] = int32_t((key >> 42) & 0x1FFFFFull) - bias;
-  c[1] = int32_t((key >> 21) & 0x1FFFFFull) - bias;
-  c[2] = int32_t(key & 0x1FFFFFull) - bias;
-}
-
 // Prune, step 1.  One lane per slot in use: keep[v] = 1 iff the voxel passes every test the rule asks for.  The totals
 // (voxels removed, their points, valid voxels kept) move by one integer atomic per wave each.  Nothing of the store is written.
 __global__ __launch_bounds__(256) void voxel_keep_kernel(VoxelStoreView s, VoxelKeepRule rule, uint32_t* __restrict__ keep,

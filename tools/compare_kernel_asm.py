@@ -1,12 +1,15 @@
 """Are the matcher and registration kernels of two source trees the same kernels?  Compares gfx950 assembly as TEXT.
 
-usage: python tools/compare_kernel_asm.py OLD_CSRC NEW_CSRC [--jobs N]        (the table goes to stdout)
+usage: python tools/compare_kernel_asm.py OLD_CSRC NEW_CSRC [--jobs N] [--units a,b,...] [--all-kernels]
+                                                                               (the table goes to stdout)
 
 Every unit that holds a matcher or registration kernel (UNITS) is compiled from both csrc directories with the Makefile's
 flags and `-S --cuda-device-only`; the body of each kernel named in KERNELS — from its label to its s_endpgm — is looked up
 by demangled name and compared line for line.  Two things are normalised, both of them numbering, not code: the index of
 the function inside its unit in local labels (.LBB12_3 → .LBB_3: a kernel that moved from a .hip file into a header is
 emitted at another position) and trailing comments.  Exit status 1 when a body differs or a kernel is missing.
+--units replaces UNITS (names without .hip); --all-kernels compares every kernel the units emit — every .amdhsa_kernel,
+rocPRIM's instantiations included — instead of those of KERNELS.
 """
 import os
 import re
@@ -30,16 +33,18 @@ def assembly(csrc, unit, out_dir):
         return f.read()
 
 
-def kernel_bodies(text):
-    """→ {demangled name: [normalised lines from the kernel's label to s_endpgm]} for the kernels of KERNELS."""
+def kernel_bodies(text, every=False):
+    """→ {demangled name: [normalised lines from the kernel's label to s_endpgm]} for the kernels of KERNELS (every: for
+    each symbol the unit declares a kernel)."""
     lines = text.split("\n")
+    entry_points = set(re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M))
     starts = [(i, m.group(1)) for i, line in enumerate(lines) for m in [re.match(r"^(_Z\w+):", line)] if m]
     names = subprocess.run(["c++filt"], input="\n".join(s for _, s in starts), capture_output=True, text=True).stdout.split("\n")
     bodies = {}
-    for (i, _), name in zip(starts, names):
+    for (i, symbol), name in zip(starts, names):
         name = re.sub(r"^void ", "", name.strip())
         # the function's own name, not a type among its arguments: "nos::match_kernel<" must not match voxel_match_kernel
-        if not any(re.search(r"(^|::)" + re.escape(k), name) for k in KERNELS):
+        if not (symbol in entry_points if every else any(re.search(r"(^|::)" + re.escape(k), name) for k in KERNELS)):
             continue
         body = []
         for line in lines[i + 1:]:
@@ -56,18 +61,20 @@ def kernel_bodies(text):
 def main():
     old_csrc, new_csrc = sys.argv[1], sys.argv[2]
     jobs = int(sys.argv[sys.argv.index("--jobs") + 1]) if "--jobs" in sys.argv else 4
+    units = tuple(sys.argv[sys.argv.index("--units") + 1].split(",")) if "--units" in sys.argv else UNITS
+    every = "--all-kernels" in sys.argv
     with tempfile.TemporaryDirectory() as d:
         dirs = {"old": os.path.join(d, "old"), "new": os.path.join(d, "new")}
         for p in dirs.values():
             os.mkdir(p)
         with ThreadPoolExecutor(jobs) as pool:
             work = {(side, u): pool.submit(assembly, csrc, u, dirs[side])
-                    for side, csrc in (("old", old_csrc), ("new", new_csrc)) for u in UNITS}
+                    for side, csrc in (("old", old_csrc), ("new", new_csrc)) for u in units}
             text = {k: f.result() for k, f in work.items()}
     bad = 0
     print("%-18s %6s %6s %-9s %s" % ("unit", "old", "new", "identical", "kernel"))
-    for u in UNITS:
-        old, new = kernel_bodies(text[("old", u)]), kernel_bodies(text[("new", u)])
+    for u in units:
+        old, new = kernel_bodies(text[("old", u)], every), kernel_bodies(text[("new", u)], every)
         for name in sorted(set(old) | set(new)):
             a, b = old.get(name), new.get(name)
             same = a is not None and a == b
