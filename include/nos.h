@@ -661,6 +661,43 @@ int nos_voxel_map_register3_batch(nos_voxel_map* map, nos_scan* const* scans, in
                                   const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
                                   nos_register_report* reports);
 
+/* ---- how well a scan fits the map at a pose: many poses scored in one call -------------
+ * nos_ndt_score_batch: n_problems (scan, pose) pairs against one map, three numbers each, nothing written in between.
+ * They are taken over the correspondences nos_ndt_match (nos_voxel_map_match for the store) produces for
+ * (scans[b], R[b], t[b], max_neighbors) with dtype = NOS_F64:
+ *   matches         that call's *n_matches;
+ *   matched_points  the scan points with at least one match (a non-empty slot 2i);
+ *   cost            Σ ρ over those correspondences — every term is, bit for bit, the value nos_ndt6_accumulate adds to
+ *                   out[27] for the record the matcher writes (the same search, the same U, the item's own arithmetic);
+ *                   only the order of the sum differs from that route.
+ * The sum is deterministic and its shape follows the scan's point count alone (chunks of 1 024 points, one workgroup
+ * each, the chunks of a problem added in ascending order): a row is the same bits from run to run, whatever
+ * n_problems is, wherever the row stands in the batch and whatever the other rows are; and for the same arguments the
+ * rows of nos_voxel_map_score_batch and of nos_ndt_score_batch on that store's nos_voxel_map_snapshot are equal bit
+ * for bit (subject to the guard-band caveat of nos_voxel_map_match).
+ * The same scan may appear several times (one scan, many poses); scans and map are only read — of the store, only its
+ * internal probe-error flag is written, as in nos_voxel_map_register6_batch.  Descriptors, chunk partials and rows
+ * come from the context's buffer pool: one upload, the launches, one copy back, one synchronisation; nothing is
+ * allocated or iterated in proportion to the map.  loss: NULL = none; one loss for the whole call.
+ * Rejected before anything runs, scores unwritten: NULL arrays with n_problems > 0, n_problems < 0, a scan of another
+ * context than the map's, an unknown loss kind (NOS_ERR_INVALID_ARGUMENT); max_neighbors outside 1-2, a multi-device
+ * context, and for the store a search ball that spans more than 9 cells per axis (NOS_ERR_UNSUPPORTED); a store an
+ * earlier failure left undefined (NOS_ERR_HIP).  n_problems == 0 returns NOS_OK; an empty scan gives a zero row, an
+ * empty map or store zero rows.  A table probe that runs through the whole table (it cannot at the store's load
+ * factor) makes the call return NOS_ERR_HIP with scores unwritten.
+ * Not covered: fp32 scoring, the planar cost, H and g per pose, one map per problem, multi-device contexts. */
+typedef struct nos_pose_score {
+  uint64_t matches;
+  uint64_t matched_points;
+  double cost;
+  double reserved;   /* 0 */
+} nos_pose_score;
+
+int nos_ndt_score_batch(nos_ndt_map* map, nos_scan* const* scans, int32_t n_problems, const double* R /*[n][9]*/,
+                        const double* t /*[n][3]*/, const nos_loss* loss, int max_neighbors, nos_pose_score* scores);
+int nos_voxel_map_score_batch(nos_voxel_map* map, nos_scan* const* scans, int32_t n_problems, const double* R /*[n][9]*/,
+                              const double* t /*[n][3]*/, const nos_loss* loss, int max_neighbors, nos_pose_score* scores);
+
 /* Test hook: ONE step of the device-resident loop on given sums and a given loop state — the stand-alone step kernel
  * (the same single-lane function every device loop form calls).  dof 6: sums[28], dof 3: sums[10].
  * state[22] = R (9, row-major; planar: R[0..3] = the 2x2 rotation) | t (3) | q w x y z (4) | lambda | previous_cost | cost |

@@ -42,6 +42,7 @@ C_ABI_SYMBOLS = (
     "nos_ndt6_solve", "nos_ndt3_solve", "nos_reproj_solve",
     "nos_ndt6_solve_batch", "nos_ndt3_solve_batch", "nos_reproj_solve_batch",
     "nos_ndt6_register_batch", "nos_ndt3_register_batch", "nos_voxel_map_register6_batch", "nos_voxel_map_register3_batch",
+    "nos_ndt_score_batch", "nos_voxel_map_score_batch",
     "nos_ctx_set_launch", "nos_ctx_set_option", "nos_ctx_get_option", "nos_runtime_info", "nos_ctx_comm_rccl_count",
     "nos_ctx_last_kernel", "nos_ctx_profile_begin", "nos_ctx_profile_end", "nos_ndt6_time_kernel", "nos_reproj_time_kernel",
     "nos_ndt3_time_kernel", "nos_status_string", "nos_last_error", "nos_version",
@@ -78,6 +79,11 @@ class NosRegisterOptions(ctypes.Structure):
 
 class NosRegisterReport(ctypes.Structure):
     _fields_ = [("outer_iter", ctypes.c_int32), ("rounds", ctypes.c_int32), ("ok", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class NosPoseScore(ctypes.Structure):
+    _fields_ = [("matches", ctypes.c_uint64), ("matched_points", ctypes.c_uint64), ("cost", ctypes.c_double),
+                ("reserved", ctypes.c_double)]
 
 
 NOS_PRUNE_BOX = 1
@@ -238,6 +244,10 @@ def _declare(lib):
         if hasattr(lib, "nos_voxel_map_register6_batch"):  # against the live voxel store: absent from builds older still
             lib.nos_voxel_map_register6_batch.argtypes = [vp, c_void_pp, ctypes.c_int32, dp, dp, lp, ro, lmo, rr]
             lib.nos_voxel_map_register3_batch.argtypes = [vp, c_void_pp, ctypes.c_int32, dp, dp, lp, ro, lmo, rr]
+    if hasattr(lib, "nos_ndt_score_batch"):  # pose scoring: absent from older builds loaded through NOS_HIP_LIB
+        sp = ctypes.POINTER(NosPoseScore)
+        lib.nos_ndt_score_batch.argtypes = [vp, c_void_pp, ctypes.c_int32, dp, dp, lp, i, sp]
+        lib.nos_voxel_map_score_batch.argtypes = [vp, c_void_pp, ctypes.c_int32, dp, dp, lp, i, sp]
     lib.nos_ndt6_time_kernel.argtypes = [vp, dp, dp, lp, i, dp, dp]
     lib.nos_ndt3_time_kernel.argtypes = [vp, dp, dp, lp, i, dp, dp]
     lib.nos_reproj_time_kernel.argtypes = [vp, dp, dp, dp, lp, ctypes.c_double, i, dp, dp]

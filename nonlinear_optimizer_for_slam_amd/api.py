@@ -346,6 +346,42 @@ def register3_batch(ndt_map, scans, R, t, loss, max_outer_iterations=10, keep_mu
                           max_iterations, gradient_tolerance, parameter_tolerance)
 
 
+SCORE_CHUNK_POINTS = 1024  # kScoreChunkPoints of csrc/score_kernels.hpp: points per workgroup of a score call
+SCORE_DTYPE = np.dtype([("matches", np.uint64), ("matched_points", np.uint64), ("cost", np.float64),
+                        ("reserved", np.float64)])  # nos_pose_score
+
+
+def _score_entry(ndt_map):
+    """The C entry point of a score call by the kind of map, as _register_entry."""
+    name = "nos_voxel_map_score_batch" if isinstance(ndt_map, VoxelMap) else "nos_ndt_score_batch"
+    return getattr(hip_lib(), name), name  # a library without the symbol: AttributeError, no other route is tried
+
+
+def score_batch(ndt_map, scans, R, t, loss, max_neighbors=2):
+    """How well scans[b] fits the map at (R[b], t[b]), for B problems in one call (nos_ndt_score_batch; for a VoxelMap
+    nos_voxel_map_score_batch, against the live store).  scans: B Scans of the map's context (the same one may repeat:
+    one scan, many poses); R [B, 9] or [B, 3, 3], t [B, 3].  → structured array [B] with fields matches (what
+    match(...) counts), matched_points (points with at least one match) and cost (Σ ρ, the [27] of match(..., "f64")
+    + accumulate6: the same terms bit for bit, summed in a fixed order that depends on the scan's size alone).  A row does
+    not depend on B, on its position or on the other rows."""
+    scans = list(scans)
+    B = len(scans)
+    R = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(-1))
+    t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1))
+    if R.size != B * 9 or t.size != B * 3:
+        raise ValueError("expected R [%d, 9] and t [%d, 3], got %d and %d values" % (B, B, R.size, t.size))
+    handles = (ctypes.c_void_p * max(B, 1))(*[s._h for s in scans])
+    out = np.zeros(max(B, 1), dtype=SCORE_DTYPE)
+    fn, name = _score_entry(ndt_map)
+    l = make_loss(loss)
+    check(fn(ndt_map._h, handles, B, _dp(R), _dp(t), ctypes.byref(l), int(max_neighbors),
+             out.ctypes.data_as(ctypes.POINTER(_lib.NosPoseScore))), name)
+    rows = np.zeros(B, dtype=[(f, SCORE_DTYPE[f]) for f in ("matches", "matched_points", "cost")])  # packed: 24 bytes
+    for field in rows.dtype.names:
+        rows[field] = out[field][:B]
+    return rows
+
+
 class _Dataset:
     _n_planes = 0
     _create = _create_dev = _create_rec = None
@@ -726,6 +762,11 @@ class NdtMap:
               "nos_ndt_match_indexed")
         return NdtIndexedDataset(self._ctx, h), int(n.value)
 
+    def score(self, scan, R, t, loss, max_neighbors=2):
+        """score_batch for one pose → (matches, matched_points, cost)."""
+        row = score_batch(self, [scan], _dvec(R, 9), _dvec(t, 3), loss, max_neighbors)[0]
+        return int(row["matches"]), int(row["matched_points"]), float(row["cost"])
+
     def close(self):
         if self._h:
             self._lib.nos_ndt_map_destroy(self._h)
@@ -831,6 +872,11 @@ class VoxelMap:
                                                     int(bool(sort_by_voxel)), ctypes.byref(h), ctypes.byref(n)),
               "nos_voxel_map_match_indexed")
         return NdtIndexedDataset(self._ctx, h), int(n.value)
+
+    def score(self, scan, R, t, loss, max_neighbors=2):
+        """score_batch for one pose → (matches, matched_points, cost)."""
+        row = score_batch(self, [scan], _dvec(R, 9), _dvec(t, 3), loss, max_neighbors)[0]
+        return int(row["matches"]), int(row["matched_points"]), float(row["cost"])
 
     def stats(self):
         """→ dict with means, sqrt_infos, valid, counts, cells in voxel-id order (the keys NdtMap.build returns)."""

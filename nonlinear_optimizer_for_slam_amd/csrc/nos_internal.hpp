@@ -493,6 +493,9 @@ inline int check_live_store(const LiveStore& s) {
 int register_live(int dof, const LiveStore* store, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
                   const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
                   nos_register_report* reports);
+// nos_score.hip: a batch of (scan, pose) problems scored against the store.  store == NULL: the map argument was NULL.
+int score_live(const LiveStore* store, nos_scan* const* scans, int32_t n_problems, const double* R, const double* t,
+               const nos_loss* loss, int max_neighbors, nos_pose_score* scores);
 // nos_indexed.hip
 // A voxel-indexed dataset from device-resident inputs (point planes [3][n], id planes [n_slots][n], voxel arrays), all on
 // the context's stream; one host wait.  d_rows == NULL: table row r is row r of d_means / d_sqrt_infos and ids index them

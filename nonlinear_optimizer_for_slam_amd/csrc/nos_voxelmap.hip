@@ -527,6 +527,14 @@ int nos_voxel_map_register3_batch(nos_voxel_map* vm, nos_scan* const* scans, int
   return voxel_map_register(3, vm, scans, n_problems, R, t, loss, ropt, options, reports);
 }
 
+int nos_voxel_map_score_batch(nos_voxel_map* vm, nos_scan* const* scans, int32_t n_problems, const double* R, const double* t,
+                              const nos_loss* loss, int max_neighbors, nos_pose_score* scores) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!vm) return score_live(nullptr, scans, n_problems, R, t, loss, max_neighbors, scores);
+  const LiveStore store = live_store(vm);
+  return score_live(&store, scans, n_problems, R, t, loss, max_neighbors, scores);
+}
+
 int nos_voxel_map_stats(nos_voxel_map* vm, nos_map_stats** out_stats) {
   nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
   if (!vm || !out_stats) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");

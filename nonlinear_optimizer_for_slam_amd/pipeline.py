@@ -8,7 +8,7 @@ less than 1e-5 in translation and in the quaternion vector part.
 """
 import numpy as np
 
-from .api import NdtMap, Scan, VoxelMap, register3_batch, register6_batch
+from .api import NdtMap, Scan, VoxelMap, register3_batch, register6_batch, score_batch
 from .solvers import MahalanobisDistanceMinimizerHip, MahalanobisDistanceMinimizerHip3DOF, Options, Pose
 
 
@@ -124,6 +124,60 @@ def scan_to_map_batch(ctx, ndt_map, scans, initial_poses=None, loss=("exponentia
                    "printed_cost": r["printed_cost"]} for r in rep["rounds"]]
         out.append((Pose(R[i].reshape(3, 3), t[i]), rounds, rep["outer_iter"]))
     return out
+
+
+def _ndt_fitness(scores, loss):
+    """The NDT fitness a · matches − cost of score_batch rows under the exponential loss (a, b): a Σ exp(−b s) over the
+    correspondences, higher is better."""
+    return float(loss[1]) * scores["matches"].astype(np.float64) - scores["cost"]
+
+
+def relocalize(ctx, ndt_map, scan, candidates, loss=("exponential", 1.0, 1.0), top_k=8, score_scan=None, key=None,
+               **scan_to_map_batch_kwargs):
+    """Which of many candidate poses is the scan at?  Score them all in one call, register the best few, score again.
+    ndt_map: api.NdtMap or api.VoxelMap (the live store); scan: api.Scan; candidates: list of Poses.
+    1. every candidate is scored with score_scan (default: scan; a coarser scan.filtered(...) is the intended use) by
+       api.score_batch — one launch, one number per pose;
+    2. they are ranked by key(scores) → [len(candidates)] floats, higher is better, ties by lower candidate index.  The
+       default key is the NDT fitness a · matches − cost (_ndt_fitness), which needs the exponential loss: another loss
+       without a key raises ValueError;
+    3. scan_to_map_batch registers the full scan from the top_k candidates (scan_to_map_batch_kwargs go to it unchanged);
+    4. the final poses of the registrations that did not fail are scored with the full scan in one more score_batch call;
+    5. → (Pose, info) of the best final key, ties by lower candidate index.  info: scores and fitness (stage 1, per
+       candidate), chosen (candidate indices registered, best first), registrations (scan_to_map_batch's rows for them),
+       final_scores and final_fitness (per chosen candidate; a failed registration: a zero row and -inf), winner (the
+       candidate index the returned pose started from).
+    If every registration failed, RuntimeError, as scan_to_map raises."""
+    candidates = list(candidates)
+    if key is None:
+        if loss is None or loss[0] != "exponential":
+            raise ValueError("the default key is the NDT fitness a * matches - cost of the exponential loss: "
+                             "pass key= with loss %r" % (loss,))
+        key = lambda scores: _ndt_fitness(scores, loss)  # noqa: E731
+    if not candidates:
+        raise ValueError("relocalize needs at least one candidate pose")
+    n = len(candidates)
+    R = np.array([p.R.reshape(9) for p in candidates]).reshape(n, 9)
+    t = np.array([p.t.reshape(3) for p in candidates]).reshape(n, 3)
+    scores = score_batch(ndt_map, [scan if score_scan is None else score_scan] * n, R, t, loss)
+    fitness = np.asarray(key(scores), dtype=np.float64).reshape(n)
+    chosen = sorted(range(n), key=lambda i: (-fitness[i], i))[:max(int(top_k), 1)]
+    rows = scan_to_map_batch(ctx, ndt_map, [scan] * len(chosen), [candidates[i] for i in chosen], loss=loss,
+                             **scan_to_map_batch_kwargs)
+    alive = [k for k, row in enumerate(rows) if row is not None]
+    if not alive:
+        raise RuntimeError("SolveDataset failed for every candidate (each registration returned ok = 0)")
+    Rf = np.array([rows[k][0].R.reshape(9) for k in alive]).reshape(len(alive), 9)
+    tf = np.array([rows[k][0].t.reshape(3) for k in alive]).reshape(len(alive), 3)
+    alive_scores = score_batch(ndt_map, [scan] * len(alive), Rf, tf, loss)
+    final_scores = np.zeros(len(chosen), dtype=alive_scores.dtype)
+    final_fitness = np.full(len(chosen), -np.inf)
+    final_scores[alive] = alive_scores
+    final_fitness[alive] = np.asarray(key(alive_scores), dtype=np.float64).reshape(len(alive))
+    best = min(alive, key=lambda k: (-final_fitness[k], chosen[k]))
+    info = {"scores": scores, "fitness": fitness, "chosen": list(chosen), "registrations": rows,
+            "final_scores": final_scores, "final_fitness": final_fitness, "winner": chosen[best]}
+    return rows[best][0], info
 
 
 _ONE_LAUNCH_KWARGS = ("loss", "options", "max_outer_iterations", "dof", "dtype", "keep_multiple")
