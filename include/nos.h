@@ -315,7 +315,10 @@ int nos_indexed_dataset_download(nos_dataset* ds, int32_t* const index_planes[],
  * sqrt_information = diag(eigvals^-1/2) * eigenvectors; a voxel is valid with >= 5 points and a
  * largest eigenvalue >= 0.01.  The result is a ready-to-match nos_ndt_map; *out_stats (optional)
  * gives the per-voxel numbers back (voxels ordered by ascending integer cell coordinates).
- * Voxel coordinates are limited to +-2^20 cells per axis. */
+ * Voxel coordinates are limited to +-2^20 cells per axis, and the statistics are as accurate at that limit as at the
+ * origin: count / sum / moment are taken about the corner of the point's cell (cell * voxel_resolution), where the
+ * harness's cov = moment / n - mean mean^T cancels eps * resolution^2 instead of eps * |p|^2 (6.7e-4 at 2^20 cells of 1 m,
+ * against a floored eigenvalue of 8e-4), and mean = corner + sum / n.  NOS_MAP_REFERENCE_EXACT keeps the raw sums. */
 typedef struct nos_map_stats nos_map_stats;
 /* flags: 0 reproduces the harness formula sqrt_information = D^-1/2 * V (:275-276), whose result
  * depends on the eigenvector sign convention (here: the first near-largest component of every
@@ -355,12 +358,13 @@ int nos_map_stats_destroy(nos_map_stats* stats);
  * batch of points to the count / sum / moment of the voxels they fall into, in a map that already exists (:240-252), and
  * re-derives mean, covariance, eigen-decomposition and sqrt-information for the touched voxels only
  * (updated_voxel_key_set, :254-280).  nos_ndt_map_build above is the one-shot form; a nos_voxel_map is the map that
- * exists between calls: a growable, device-resident store of per-voxel key, count, the nine sums, mean, sqrt-information
- * and validity.  An insert costs what its batch costs, never what the points already absorbed would.
+ * exists between calls: a growable, device-resident store of per-voxel key, count, the nine sums about the cell corner,
+ * mean, sqrt-information and validity.  An insert costs what its batch costs, never what the points already absorbed would.
  *   flags: 0 (harness formula) or NOS_MAP_PROPER_SQRT_INFORMATION.  NOS_MAP_REFERENCE_EXACT is rejected with
  *   NOS_ERR_UNSUPPORTED: its sequential, calibrated accumulation in point order is a different piece of work (one-shot
  *   builds only).  capacity_hint (voxels) only avoids early growth: arrays and table double as needed.  Single-device
- *   contexts only, like the map build; voxel coordinates are limited to +-2^20 cells per axis, a voxel to 2^32 - 1 points.
+ *   contexts only, like the map build; voxel coordinates are limited to +-2^20 cells per axis (with the accuracy of the
+ *   origin throughout, as for the map build: sums about the cell corner), a voxel to 2^32 - 1 points.
  * Voxel ids (the order of nos_voxel_map_stats, the matcher's tie-break in a snapshot) are a function of the sequence of
  * batches alone: batch of first appearance, then ascending integer cell coordinates.  One insert into an empty store
  * gives the statistics of nos_ndt_map_build bit for bit; sums are merged per voxel as store + batch, so results after
@@ -704,6 +708,14 @@ int nos_voxel_map_score_batch(nos_voxel_map* map, nos_scan* const* scans, int32_
  * iteration | done | ok; settings[4] = max_iterations | gradient_tolerance | parameter_tolerance | float_schedule.
  * state is updated in place.  The host's own step for the same arguments: nos_host_lm_advance in libnos_host.so. */
 int nos_debug_lm_step(nos_ctx* ctx, int dof, const double* sums, const double settings[4], double state[22]);
+
+/* Test hook: the per-voxel finish of the map build and the voxel store — mean, covariance, eigen-decomposition, validity,
+ * flooring, sqrt-information — computed ON THE HOST by the function the kernels call (no GPU call, no context).
+ * sums[9] = sx sy sz | mxx mxy mxz myy myz mzz of d = p - cell * voxel_resolution over the voxel's `count` points;
+ * params[3] = min_points | min largest eigenvalue | eigenvalue floor ratio (5, 0.01, 0.01 in the build);
+ * flags: 0 or NOS_MAP_PROPER_SQRT_INFORMATION.  An invalid voxel: sqrt_information identity, *valid = 0 (and mean 0 below min_points). */
+int nos_debug_voxel_finish(uint32_t count, const double sums[9], const int64_t cell[3], double voxel_resolution,
+                           const double params[3], int flags, double mean[3], double sqrt_information[9], unsigned char* valid);
 
 /* ---- pose-graph optimisation (BASELINE.json configs[4]) --------
  * The reference's PoseGraphOptimizerAnalytic::Solve is an empty loop

@@ -4,6 +4,8 @@
 // (nonlinear_optimizer/mahalanobis_distance_minimizer/tests/simple_optimization_test.cc:236-281):
 //   per point:  voxel key, ++count, sum += p, moment += p pᵀ   (moment starts at IDENTITY, MDM/types.h:14)
 //   per voxel:  count < 5 → invalid;  mean = sum / count;  cov = moment / count − mean meanᵀ;
+//               (here with d = p − the cell's corner in place of p, and mean = corner + sum / count: the same covariance
+//               without the cancellation of eps |p|² far from the origin, voxel_finish.hpp)
 //               eigen-decomposition (ascending);  largest eigenvalue < 0.01 → invalid;
 //               the two smaller eigenvalues are floored at 0.01 × largest (:268-273);
 //               sqrt_information = diag(eigvals^-1/2) · eigenvectors (:275-276)
@@ -114,13 +116,15 @@ __global__ __launch_bounds__(256) void points_to_records_kernel(const double* __
 }
 
 // (1) One wave per voxel: count / sum / moment in a fixed order.  seg_offset[v] .. + seg_count[v] index into sorted_idx.
-//     acc_out: [n_voxels][9] = sx sy sz | mxx mxy mxz myy myz mzz.  rec != nullptr: the points as records (above).
+//     acc_out: [n_voxels][9] = sx sy sz | mxx mxy mxz myy myz mzz of d = p − corner of p's cell, which every lane forms from
+//     its own point (the expressions of the key kernels and of voxel_finish: floor(x inv_res), cell_origin).
+//     rec != nullptr: the points as records (above).
 __global__ __launch_bounds__(256) void voxel_sums_kernel(const double* __restrict__ px, const double* __restrict__ py,
                                                          const double* __restrict__ pz, const double* __restrict__ rec,
                                                          const uint32_t* __restrict__ sorted_idx,
                                                          const uint32_t* __restrict__ seg_offset,
                                                          const uint32_t* __restrict__ seg_count, uint32_t n_voxels,
-                                                         double* __restrict__ acc_out) {
+                                                         double inv_res, double res, double* __restrict__ acc_out) {
   const uint32_t v = (blockIdx.x * 256 + threadIdx.x) / kWave;
   const int lane = threadIdx.x & (kWave - 1);
   if (v >= n_voxels) return;  // wave-uniform
@@ -137,6 +141,9 @@ __global__ __launch_bounds__(256) void voxel_sums_kernel(const double* __restric
     } else {
       x = px[i], y = py[i], z = pz[i];
     }
+    x -= cell_origin(floor(x * inv_res), res);
+    y -= cell_origin(floor(y * inv_res), res);
+    z -= cell_origin(floor(z * inv_res), res);
     acc[0] += x;
     acc[1] += y;
     acc[2] += z;
@@ -157,10 +164,19 @@ __global__ __launch_bounds__(256) void voxel_sums_kernel(const double* __restric
   }
 }
 
-// (2) One LANE per voxel: the finish above.
+// How voxel_eigen_kernel reads a voxel's cell out of its sort key: the packed key (pack_cell), or the compact key
+// ((x − x0) ny + (y − y0)) nz + (z − z0) of voxel_compact_key_kernel.
+struct CellKeyForm {
+  long long x0, y0, z0;
+  unsigned long long ny, nz;
+  int compact;
+};
+
+// (2) One LANE per voxel: the finish (voxel_finish.hpp), with the voxel's cell decoded from its key.
 __global__ __launch_bounds__(256) void voxel_eigen_kernel(const double* __restrict__ acc_in,
-                                                          const uint32_t* __restrict__ seg_count, uint32_t n_voxels,
-                                                          MapBuildParams prm, double* __restrict__ mean_out,
+                                                          const uint32_t* __restrict__ seg_count,
+                                                          const uint64_t* __restrict__ seg_key, CellKeyForm form,
+                                                          uint32_t n_voxels, MapBuildParams prm, double* __restrict__ mean_out,
                                                           double* __restrict__ sqrt_info_out,
                                                           unsigned char* __restrict__ valid_out) {
   const uint32_t v = blockIdx.x * 256 + threadIdx.x;
@@ -169,8 +185,20 @@ __global__ __launch_bounds__(256) void voxel_eigen_kernel(const double* __restri
   double acc[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) acc[k] = acc_in[9 * size_t(v) + k];
+  int64_t cell[3];
+  const uint64_t key = seg_key[v];
+  if (form.compact) {
+    const uint64_t nyz = form.ny * form.nz;
+    cell[0] = int64_t(key / nyz) + form.x0;
+    cell[1] = int64_t((key % nyz) / form.nz) + form.y0;
+    cell[2] = int64_t(key % form.nz) + form.z0;
+  } else {
+    int32_t c[3];
+    unpack_cell(key, c);
+    for (int k = 0; k < 3; ++k) cell[k] = c[k];
+  }
   double S[9], mean[3];
-  const unsigned char ok = voxel_finish(acc, count, prm, mean, S);
+  const unsigned char ok = voxel_finish(acc, count, cell, prm, mean, S);
   for (int k = 0; k < 3; ++k) mean_out[3 * size_t(v) + k] = mean[k];
   for (int k = 0; k < 9; ++k) sqrt_info_out[9 * size_t(v) + k] = S[k];
   valid_out[v] = ok;

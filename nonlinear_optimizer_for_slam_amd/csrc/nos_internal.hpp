@@ -465,9 +465,10 @@ int lm_solve(nos_dataset* ds, const Request& rq, const nos_lm_options* opt, doub
 int map_create_device(nos_ctx* ctx, size_t n_voxels, const double* d_means, const double* d_S, const unsigned char* d_valid,
                       double search_radius_sq, nos_ndt_map** out_map);
 // nos_mapbuild.hip: voxel_sums_kernel on device-resident 32-byte point records (the incremental store's batches run the
-// build's own kernel, so a segment's nine sums are the same bits from either)
+// build's own kernel, so a segment's nine sums — about the cell corner, voxel_finish.hpp — are the same bits from either)
 hipError_t launch_voxel_sums(const double* d_records, const uint32_t* sorted_idx, const uint32_t* seg_offset,
-                             const uint32_t* seg_count, uint32_t n_voxels, double* acc_out, hipStream_t stream);
+                             const uint32_t* seg_count, uint32_t n_voxels, double inv_res, double res, double* acc_out,
+                             hipStream_t stream);
 // The live voxel store as whatever matches against it is handed it — the matcher of nos_voxelmap.hip (which owns struct
 // nos_voxel_map; its match source, match_host.hpp, derives from this) and the batched registration of
 // nos_voxelregister.hip.

@@ -15,11 +15,12 @@ hipError_t launch_map_exact(const double* px, const double* py, const double* pz
 }  // namespace nosd
 
 hipError_t nosd::launch_voxel_sums(const double* d_records, const uint32_t* sorted_idx, const uint32_t* seg_offset,
-                                   const uint32_t* seg_count, uint32_t n_voxels, double* acc_out, hipStream_t stream) {
+                                   const uint32_t* seg_count, uint32_t n_voxels, double inv_res, double res, double* acc_out,
+                                   hipStream_t stream) {
   if (n_voxels == 0) return hipSuccess;
   const double* none = nullptr;
   hipLaunchKernelGGL(nos::voxel_sums_kernel, dim3(unsigned((size_t(n_voxels) * nos::kWave + 255) / 256)), dim3(256), 0, stream, none,
-                     none, none, d_records, sorted_idx, seg_offset, seg_count, n_voxels, acc_out);
+                     none, none, d_records, sorted_idx, seg_offset, seg_count, n_voxels, inv_res, res, acc_out);
   return hipGetLastError();
 }
 
@@ -185,6 +186,24 @@ int nos_map_stats_get_eigen(const nos_map_stats* stats, double* eigenvalues, dou
   return NOS_OK;
 }
 
+// Test hook: the per-voxel finish on the HOST — voxel_finish as the kernels compile it, no GPU call.
+int nos_debug_voxel_finish(uint32_t count, const double sums[9], const int64_t cell[3], double voxel_resolution,
+                           const double params[3], int flags, double mean[3], double sqrt_information[9], unsigned char* valid) {
+  if (!sums || !cell || !params || !mean || !sqrt_information || !valid) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (!(voxel_resolution > 0.0) || !std::isfinite(voxel_resolution)) return fail(NOS_ERR_INVALID_ARGUMENT, "bad voxel resolution");
+  if ((flags & ~NOS_MAP_PROPER_SQRT_INFORMATION) != 0)
+    return fail(NOS_ERR_INVALID_ARGUMENT, "flags: 0 or NOS_MAP_PROPER_SQRT_INFORMATION");
+  const nos::MapBuildParams prm{int(params[0]), params[1], params[2], (flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0,
+                                voxel_resolution};
+  double acc[9], m[3], S[9];
+  for (int k = 0; k < 9; ++k) acc[k] = sums[k];
+  const int64_t c[3] = {cell[0], cell[1], cell[2]};
+  *valid = nos::voxel_finish(acc, count, c, prm, m, S);
+  for (int k = 0; k < 3; ++k) mean[k] = m[k];
+  for (int k = 0; k < 9; ++k) sqrt_information[k] = S[k];
+  return NOS_OK;
+}
+
 int nos_ndt_map_build(nos_ctx* ctx, size_t n_points, const double* points_xyz, double voxel_resolution,
                       double search_radius_sq, int flags, nos_ndt_map** out_map, nos_map_stats** out_stats) {
   nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
@@ -236,7 +255,9 @@ int nos_ndt_map_build(nos_ctx* ctx, size_t n_points, const double* points_xyz, d
       e = launch_map_exact(px, py, pz, g.idx_sorted, g.offsets, g.counts, V, ctx->settings.map_fma_mask,
                            ctx->settings.map_eigen_version, d_acc, d_mean, d_S, d_valid, d_evals, d_evecs, d_first, st);
   } else if (e == hipSuccess && V > 0) {
-    const nos::MapBuildParams prm{5, 0.01, 0.01, (flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0};
+    const nos::MapBuildParams prm{5, 0.01, 0.01, (flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0, voxel_resolution};
+    const nos::CellKeyForm form{ck.box[0], ck.box[1], ck.box[2], (unsigned long long)ck.dims[1], (unsigned long long)ck.dims[2],
+                                ck.compact ? 1 : 0};
     e = buf.alloc(&d_acc, size_t(V) * 9);
     if (e == hipSuccess) {
       // the points as 32-byte records for the gather (one sector per point instead of three); without room for them: planes
@@ -249,9 +270,9 @@ int nos_ndt_map_build(nos_ctx* ctx, size_t n_points, const double* points_xyz, d
       }
       const unsigned blocks = unsigned((size_t(V) * nos::kWave + 255) / 256);
       hipLaunchKernelGGL(nos::voxel_sums_kernel, dim3(blocks), dim3(256), 0, st, px, py, pz, d_rec, g.idx_sorted, g.offsets, g.counts, V,
-                         d_acc);
-      hipLaunchKernelGGL(nos::voxel_eigen_kernel, dim3(unsigned((size_t(V) + 255) / 256)), dim3(256), 0, st, d_acc, g.counts, V,
-                         prm, d_mean, d_S, d_valid);
+                         1.0 / voxel_resolution, voxel_resolution, d_acc);
+      hipLaunchKernelGGL(nos::voxel_eigen_kernel, dim3(unsigned((size_t(V) + 255) / 256)), dim3(256), 0, st, d_acc, g.counts, g.uniq,
+                         form, V, prm, d_mean, d_S, d_valid);
       e = hipGetLastError();
     }
   }

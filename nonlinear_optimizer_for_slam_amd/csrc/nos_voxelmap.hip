@@ -182,8 +182,8 @@ int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const doub
   if (e == hipSuccess) e = g.queue_offsets(U);
   if (e != hipSuccess) return hip_fail(e, "voxel store insert (segments)");
   // step 3: the build's sums kernel on the batch; step 4: lookup, rank of the misses, merge + finish
-  const nos::MapBuildParams prm{5, 0.01, 0.01, (vm->flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0};
-  e = launch_voxel_sums(rec, g.idx_sorted, g.offsets, g.counts, U, seg_acc, st);
+  const nos::MapBuildParams prm{5, 0.01, 0.01, (vm->flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0, vm->voxel_resolution};
+  e = launch_voxel_sums(rec, g.idx_sorted, g.offsets, g.counts, U, 1.0 / vm->voxel_resolution, vm->voxel_resolution, seg_acc, st);
   if (e != hipSuccess) return hip_fail(e, "voxel store insert (sums)");
   const dim3 ugrid(unsigned((size_t(U) + 255) / 256));
   hipLaunchKernelGGL(nos::voxel_lookup_kernel, ugrid, dim3(256), 0, st, vm->view, g.uniq, U, run_slot, miss, vm->d_info);

@@ -1,7 +1,14 @@
 // voxel_finish.hpp — what one NDT voxel's count / sum / moment become: mean, covariance, eigen-decomposition, validity,
 // sqrt-information (UpdateNdtMap of the reference's test harness,
-// nonlinear_optimizer/mahalanobis_distance_minimizer/tests/simple_optimization_test.cc:254-280).  Device functions only, no
-// kernels: shared by the one-shot build (mapbuild_kernels.hpp) and the incremental store (voxelmap_kernels.hpp).
+// nonlinear_optimizer/mahalanobis_distance_minimizer/tests/simple_optimization_test.cc:254-280).  Host / device functions
+// only, no kernels: shared by the one-shot build (mapbuild_kernels.hpp), the incremental store (voxelmap_kernels.hpp) and
+// the host test hook nos_debug_voxel_finish.
+//
+// The sums are taken ABOUT THE CELL CORNER: for a point p in cell c, d = p - cell_origin(c, res), and the nine sums are
+// those of d and d dᵀ.  The harness sums raw p and p pᵀ, and cov = moment / n - mean meanᵀ then cancels about eps |p|²:
+// 6.7e-4 at 2^20 cells, against a floored eigenvalue of 8e-4.  About the corner |d| <= res whatever the cell, the
+// covariance is the same number (it is shift-invariant, the identity the moment starts from included) and
+// mean = origin + Σd / n.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -93,6 +100,15 @@ __host__ __device__ inline void symmetric_eigen3(const double* A, double* w, dou
   for (int i = 0; i < 9; ++i) V[i] = Vs[i];
 }
 
+// The corner of cell c on one axis (c = floor(x / res), integer-valued): a function of the cell and the resolution alone,
+// and this one expression wherever a corner is formed — by a lane of voxel_sums_kernel from its own point's cell, by
+// voxel_finish from the voxel's cell.  Exact when res is a power of two and |c| <= 2^53 / res; never fused with the
+// subtraction that follows it, so that both places see the same rounded product.
+__host__ __device__ inline double cell_origin(double c, double res) {
+#pragma clang fp contract(off)
+  return c * res;
+}
+
 struct MapBuildParams {
   int min_points;        // 5   (:258)
   double min_eigenvalue; // 0.01 on the largest eigenvalue (:264)
@@ -100,28 +116,32 @@ struct MapBuildParams {
   int proper_transpose;  // 0: sqrt_information = D^-1/2 V (the harness formula, :275-276);
                          // 1: D^-1/2 V^T (the actual square root of the inverse covariance — invariant to
                          //    eigenvector signs and to rotations inside degenerate eigenspaces)
+  double resolution;     // the voxel edge: cell_origin's res
 };
 
 // The per-voxel finish: mean, covariance (the moment starts at identity, MDM/types.h:14), eigen-decomposition, validity
-// rules (:258, :264), eigenvalue flooring (:268-273), sqrt-information (:275-276).  acc = sx sy sz | mxx mxy mxz myy myz mzz.
-// voxel_eigen_kernel (one-shot build) and voxel_merge_kernel (incremental store, voxelmap_kernels.hpp) both call this, so a
-// voxel with the same count and sums gets the same bits from either.  → NDT::is_valid
-__device__ __forceinline__ unsigned char voxel_finish(const double (&acc)[9], uint32_t count, const MapBuildParams& prm,
-                                                      double (&mean)[3], double (&S)[9]) {
+// rules (:258, :264), eigenvalue flooring (:268-273), sqrt-information (:275-276).  acc = sx sy sz | mxx mxy mxz myy myz mzz,
+// about the corner of `cell` (file header).  voxel_eigen_kernel (one-shot build) and voxel_merge_kernel (incremental store,
+// voxelmap_kernels.hpp) both call this, so a voxel with the same cell, count and sums gets the same bits from either.
+// → NDT::is_valid
+__host__ __device__ __forceinline__ unsigned char voxel_finish(const double (&acc)[9], uint32_t count, const int64_t (&cell)[3],
+                                                               const MapBuildParams& prm, double (&mean)[3], double (&S)[9]) {
   for (int k = 0; k < 9; ++k) S[k] = (k % 4 == 0) ? 1.0 : 0.0;
   for (int k = 0; k < 3; ++k) mean[k] = 0.0;
   unsigned char ok = 0;
   if (count >= uint32_t(prm.min_points)) {
     const double inv = 1.0 / double(count);
-    for (int k = 0; k < 3; ++k) mean[k] = acc[k] * inv;
-    // moment = Identity + sum p p^T
+    double m[3];  // the mean about the corner
+    for (int k = 0; k < 3; ++k) m[k] = acc[k] * inv;
+    for (int k = 0; k < 3; ++k) mean[k] = cell_origin(double(cell[k]), prm.resolution) + m[k];
+    // moment = Identity + sum d d^T
     double cov[9];
-    cov[0] = (acc[3] + 1.0) * inv - mean[0] * mean[0];
-    cov[1] = cov[3] = acc[4] * inv - mean[0] * mean[1];
-    cov[2] = cov[6] = acc[5] * inv - mean[0] * mean[2];
-    cov[4] = (acc[6] + 1.0) * inv - mean[1] * mean[1];
-    cov[5] = cov[7] = acc[7] * inv - mean[1] * mean[2];
-    cov[8] = (acc[8] + 1.0) * inv - mean[2] * mean[2];
+    cov[0] = (acc[3] + 1.0) * inv - m[0] * m[0];
+    cov[1] = cov[3] = acc[4] * inv - m[0] * m[1];
+    cov[2] = cov[6] = acc[5] * inv - m[0] * m[2];
+    cov[4] = (acc[6] + 1.0) * inv - m[1] * m[1];
+    cov[5] = cov[7] = acc[7] * inv - m[1] * m[2];
+    cov[8] = (acc[8] + 1.0) * inv - m[2] * m[2];
     double w[3], V[9];
     symmetric_eigen3(cov, w, V);
     if (!(w[2] < prm.min_eigenvalue)) {

@@ -57,7 +57,7 @@ enum VoxelInfoWord {
 struct VoxelStoreView {
   uint64_t* key;          // [capacity] packed cell key (pack_cell)
   uint32_t* count;        // [capacity]
-  double* acc;            // [capacity][9] sx sy sz | mxx mxy mxz myy myz mzz (voxel_sums_kernel's order)
+  double* acc;            // [capacity][9] sx sy sz | mxx mxy mxz myy myz mzz about the cell corner (voxel_sums_kernel's)
   double* mean;           // [capacity][3]
   double* sqrt_info;      // [capacity][9]
   unsigned char* valid;   // [capacity]
@@ -151,8 +151,9 @@ __global__ __launch_bounds__(256) void voxel_lookup_kernel(VoxelStoreView s, con
 // Step 4b.  One lane per touched voxel: a miss takes slot n_voxels + rank (rank = exclusive scan of `miss`, i.e. its
 // place among the batch's new voxels in ascending cell order) and enters the table; then count += n and
 // acc[k] = acc[k] + seg[k] with plain loads and stores (a new voxel's sums ARE the segment's: the bits of a one-shot
-// build), the finish for this slot only, and stamp = this insert's number.  The valid-voxel counter moves by an integer
-// atomic per wave.
+// build), the finish for this slot only, and stamp = this insert's number.  Store and segment both hold their sums about the
+// corner of the slot's cell (voxel_finish.hpp), a function of the key alone, so they add as they are; the finish gets the
+// cell from unpack_cell of the key.  The valid-voxel counter moves by an integer atomic per wave.
 __global__ __launch_bounds__(256) void voxel_merge_kernel(VoxelStoreView s, const uint64_t* __restrict__ run_key,
                                                           const uint32_t* __restrict__ run_count,
                                                           const double* __restrict__ seg_acc /* [n_runs][9] */,
@@ -186,8 +187,11 @@ __global__ __launch_bounds__(256) void voxel_merge_kernel(VoxelStoreView s, cons
     s.count[slot] = count;
 #pragma unroll
     for (int k = 0; k < 9; ++k) s.acc[9 * size_t(slot) + k] = acc[k];
+    int32_t c[3];
+    unpack_cell(key, c);
+    const int64_t cell[3] = {c[0], c[1], c[2]};
     double S[9], mean[3];
-    const unsigned char ok = voxel_finish(acc, count, prm, mean, S);
+    const unsigned char ok = voxel_finish(acc, count, cell, prm, mean, S);
     for (int k = 0; k < 3; ++k) s.mean[3 * size_t(slot) + k] = mean[k];
     for (int k = 0; k < 9; ++k) s.sqrt_info[9 * size_t(slot) + k] = S[k];
     s.valid[slot] = ok;
