@@ -224,10 +224,30 @@ def _lm_call(fn, where, pre_args, post_args, R, t, max_iterations, gradient_tole
                        float(parameter_tolerance), _dp(hist))
     rep = NosLmReport()
     check(fn(*pre_args, _dp(R), _dp(t), *post_args, ctypes.byref(opt), ctypes.byref(rep)), where)
-    executed = int(np.count_nonzero(~np.isnan(hist[:max(int(max_iterations), 0)])))
-    return R, t, {"iterations": rep.iterations, "ok": bool(rep.ok), "launches": rep.launches, "fallback": bool(rep.fallback),
-                  "printed_cost": rep.printed_cost, "last_cost": rep.last_cost, "final_lambda": rep.final_lambda,
-                  "cost_history": hist[:executed].copy()}
+    return R, t, _lm_report(rep, hist[:max(int(max_iterations), 0)])
+
+
+def _lm_report(rep, hist_row):
+    """The report dict of one solve: a NosLmReport and its row of the cost history (NaN where no iteration ran)."""
+    executed = int(np.count_nonzero(~np.isnan(hist_row)))
+    return {"iterations": rep.iterations, "ok": bool(rep.ok), "launches": rep.launches, "fallback": bool(rep.fallback),
+            "printed_cost": rep.printed_cost, "last_cost": rep.last_cost, "final_lambda": rep.final_lambda,
+            "cost_history": hist_row[:executed].copy()}
+
+
+def _poses(R, t, B, nR, nt, copy):
+    """The poses of a batched call as contiguous R [B, nR] and t [B, nt]; copy: the call writes them, the inputs stay."""
+    R = np.array(R, dtype=np.float64) if copy else np.asarray(R, dtype=np.float64)
+    t = np.array(t, dtype=np.float64) if copy else np.asarray(t, dtype=np.float64)
+    if R.size != B * nR or t.size != B * nt:
+        got = "%s and %s" % (R.shape, t.shape) if copy else "%d and %d values" % (R.size, t.size)
+        raise ValueError("expected R [%d, %d] and t [%d, %d], got %s" % (B, nR, B, nt, got))
+    return np.ascontiguousarray(R.reshape(B, nR)), np.ascontiguousarray(t.reshape(B, nt))
+
+
+def _handles(objs):
+    """The handle array a batched entry point takes (never of length 0)."""
+    return (ctypes.c_void_p * max(len(objs), 1))(*[o._h for o in objs])
 
 
 def _batch_call(fn, where, datasets, R, t, nR, nt, post_args, max_iterations, gradient_tolerance, parameter_tolerance):
@@ -235,26 +255,13 @@ def _batch_call(fn, where, datasets, R, t, nR, nt, post_args, max_iterations, gr
     from ._lib import NosLmOptions, NosLmReport
     datasets = list(datasets)
     B = len(datasets)
-    R = np.array(R, dtype=np.float64)  # copies: the inputs are not modified
-    t = np.array(t, dtype=np.float64)
-    if R.size != B * nR or t.size != B * nt:
-        raise ValueError("expected R [%d, %d] and t [%d, %d], got %s and %s" % (B, nR, B, nt, R.shape, t.shape))
-    R = np.ascontiguousarray(R.reshape(B, nR))
-    t = np.ascontiguousarray(t.reshape(B, nt))
-    handles = (ctypes.c_void_p * max(B, 1))(*[d._h for d in datasets])
+    R, t = _poses(R, t, B, nR, nt, copy=True)
     m = max(int(max_iterations), 1)
     hist = np.full((B, m), np.nan)  # row i starts at i * max_iterations
     opt = NosLmOptions(int(max_iterations), 0, float(gradient_tolerance), float(parameter_tolerance), _dp(hist))
     reps = (NosLmReport * max(B, 1))()
-    check(fn(handles, B, _dp(R), _dp(t), *post_args, ctypes.byref(opt), reps), where)
-    out = []
-    for i in range(B):
-        rep = reps[i]
-        executed = int(np.count_nonzero(~np.isnan(hist[i, :max(int(max_iterations), 0)])))
-        out.append({"iterations": rep.iterations, "ok": bool(rep.ok), "launches": rep.launches, "fallback": bool(rep.fallback),
-                    "printed_cost": rep.printed_cost, "last_cost": rep.last_cost, "final_lambda": rep.final_lambda,
-                    "cost_history": hist[i, :executed].copy()})
-    return R, t, out
+    check(fn(_handles(datasets), B, _dp(R), _dp(t), *post_args, ctypes.byref(opt), reps), where)
+    return R, t, [_lm_report(reps[i], hist[i, :max(int(max_iterations), 0)]) for i in range(B)]
 
 
 def solve6_batch(datasets, R, t, loss=None, max_iterations=100, gradient_tolerance=1e-6, parameter_tolerance=1e-6):
@@ -293,20 +300,14 @@ def _register_call(fn, where, ndt_map, scans, R, t, loss, max_outer_iterations, 
     from ._lib import NosLmOptions, NosRegisterOptions, NosRegisterReport, NosRegisterRound
     scans = list(scans)
     B = len(scans)
-    R = np.array(R, dtype=np.float64)  # copies: the inputs are not modified
-    t = np.array(t, dtype=np.float64)
-    if R.size != B * 9 or t.size != B * 3:
-        raise ValueError("expected R [%d, 9] and t [%d, 3], got %s and %s" % (B, B, R.shape, t.shape))
-    R = np.ascontiguousarray(R.reshape(B, 9))
-    t = np.ascontiguousarray(t.reshape(B, 3))
-    handles = (ctypes.c_void_p * max(B, 1))(*[s._h for s in scans])
+    R, t = _poses(R, t, B, 9, 3, copy=True)
     m = max(int(max_outer_iterations), 1)
     log = (NosRegisterRound * (max(B, 1) * m))()  # row i starts at i * max_outer_iterations
     ropt = NosRegisterOptions(int(max_outer_iterations), int(max_neighbors), int(keep_multiple or 0), _DTYPES[dtype], log)
     opt = NosLmOptions(int(max_iterations), 0, float(gradient_tolerance), float(parameter_tolerance), None)
     reps = (NosRegisterReport * max(B, 1))()
     l = make_loss(loss)
-    check(fn(ndt_map._h, handles, B, _dp(R), _dp(t), ctypes.byref(l), ctypes.byref(ropt), ctypes.byref(opt), reps), where)
+    check(fn(ndt_map._h, _handles(scans), B, _dp(R), _dp(t), ctypes.byref(l), ctypes.byref(ropt), ctypes.byref(opt), reps), where)
     out = []
     for i in range(B):
         rep = reps[i]
@@ -366,15 +367,11 @@ def score_batch(ndt_map, scans, R, t, loss, max_neighbors=2):
     not depend on B, on its position or on the other rows."""
     scans = list(scans)
     B = len(scans)
-    R = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(-1))
-    t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1))
-    if R.size != B * 9 or t.size != B * 3:
-        raise ValueError("expected R [%d, 9] and t [%d, 3], got %d and %d values" % (B, B, R.size, t.size))
-    handles = (ctypes.c_void_p * max(B, 1))(*[s._h for s in scans])
+    R, t = _poses(R, t, B, 9, 3, copy=False)
     out = np.zeros(max(B, 1), dtype=SCORE_DTYPE)
     fn, name = _score_entry(ndt_map)
     l = make_loss(loss)
-    check(fn(ndt_map._h, handles, B, _dp(R), _dp(t), ctypes.byref(l), int(max_neighbors),
+    check(fn(ndt_map._h, _handles(scans), B, _dp(R), _dp(t), ctypes.byref(l), int(max_neighbors),
              out.ctypes.data_as(ctypes.POINTER(_lib.NosPoseScore))), name)
     rows = np.zeros(B, dtype=[(f, SCORE_DTYPE[f]) for f in ("matches", "matched_points", "cost")])  # packed: 24 bytes
     for field in rows.dtype.names:

@@ -3,7 +3,7 @@
 // B independent pose problems: the small flat ones in ONE launch, one workgroup each (nos::solve_batch_kernel, the loop of
 // the lone single-workgroup solve), the others one at a time through the lone solve (lm_solve) after it.  Every problem ends
 // with what nos_*_solve would give it.
-#include "nos_internal.hpp"
+#include "batch_host.hpp"
 
 namespace nosd {
 namespace {
@@ -26,100 +26,53 @@ struct BatchCall {
   nos_lm_report* reports;
 };
 
-template <typename Problem, typename T>
-int launch_batch_kernel(uint32_t n_blocks, const void* d_descs, nos::BatchResult* d_results, double* d_history,
-                        int history_stride, hipStream_t stream, const void** kernel_out) {
-  const auto kernel = nos::solve_batch_kernel<Problem, T, kBatchBlock>;
-  *kernel_out = reinterpret_cast<const void*>(kernel);
-  hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(kBatchBlock), 0, stream,
-                     static_cast<const nos::BatchDesc<typename Problem::Params>*>(d_descs), d_results, d_history,
-                     history_stride);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(NOS_ERR_HIP, "batched solve launch failed: %s", hipGetErrorString(e));
-  return NOS_OK;
-}
-
 // The batch launch over the problems listed in `members`: descriptors up through pinned memory, one launch, results and
-// cost histories down in one copy, one synchronisation, then the caller's arrays.
+// cost histories down in one copy, one synchronisation (BatchTrip), then the caller's arrays.
 template <template <typename, int> class ProblemT, typename T>
 int run_batch(const BatchCall& c, const std::vector<Request>& rq, const std::vector<int>& members) {
   using Desc = nos::BatchDesc<typename ProblemT<T, nos::kLossNone>::Params>;
   DeviceSlot& slot = c.ds[0]->ctx->slots[0];
-  hipStream_t stream = slot.stream;
   const size_t B = members.size();
   const int max_it = c.opt->max_iterations;
   const bool with_history = c.opt->cost_history != nullptr;
-  auto round_up = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t desc_bytes = round_up(B * sizeof(Desc));
-  const size_t result_bytes = round_up(B * sizeof(nos::BatchResult));
-  const size_t history_bytes = with_history ? B * size_t(max_it) * sizeof(double) : 0;
-  const size_t total = desc_bytes + result_bytes + history_bytes;
-
-  NOS_HIP_CHECK(hipSetDevice(slot.device));
-  if (slot.batch_pinned_bytes < total) {  // grows only; freed with the context
-    if (slot.batch_pinned != nullptr) (void)hipHostFree(slot.batch_pinned);
-    slot.batch_pinned = nullptr;
-    slot.batch_pinned_bytes = 0;
-    NOS_HIP_CHECK(hipHostMalloc(&slot.batch_pinned, total, hipHostMallocDefault));
-    slot.batch_pinned_bytes = total;
-  }
-  unsigned char* const pinned = static_cast<unsigned char*>(slot.batch_pinned);
+  BatchTrip trip(slot);
+  const auto descs = trip.section(BatchTrip::kUp, B * sizeof(Desc));
+  const auto results = trip.section(BatchTrip::kDown, B * sizeof(nos::BatchResult));
+  const auto history = trip.section(BatchTrip::kDown, with_history ? B * size_t(max_it) * sizeof(double) : 0);
+  const int rc = trip.open();
+  if (rc != NOS_OK) return rc;
   for (size_t j = 0; j < B; ++j) {
     const int i = members[j];
     const nos_dataset* ds = c.ds[i];
-    Desc& d = *new (pinned + j * sizeof(Desc)) Desc{};
+    Desc& d = *new (trip.host<Desc>(descs) + j) Desc{};
     d.L = ds->shards[0].layout;
     fill_params(d.P, rq[size_t(i)], ds);
     d.n_chunks = uint32_t((std::max<uint64_t>(d.L.n, 1) + kBatchBlock - 1) / kBatchBlock);
     d.init = make_lm_init(ds, rq[size_t(i)], c.opt, c.R + size_t(i) * c.nR, c.nR, c.t + size_t(i) * c.nt, c.nt);  // as lm_solve
   }
-
-  void* dev = nullptr;
-  size_t dev_capacity = 0;
-  int rc = pool_alloc(slot, total, &dev, &dev_capacity);
-  if (rc != NOS_OK) return rc;
-  unsigned char* const dev_bytes = static_cast<unsigned char*>(dev);
-  nos::BatchResult* const d_results = reinterpret_cast<nos::BatchResult*>(dev_bytes + desc_bytes);
-  double* const d_history = with_history ? reinterpret_cast<double*>(dev_bytes + desc_bytes + result_bytes) : nullptr;
-  const void* kernel = nullptr;
-  const uint32_t n_blocks = uint32_t(B);
-  hipError_t e = hipMemcpyAsync(dev, pinned, desc_bytes, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) {
-    switch (rq[size_t(members[0])].loss_kind) {  // one loss for the whole call
-      case NOS_LOSS_NONE:
-        rc = launch_batch_kernel<ProblemT<T, nos::kLossNone>, T>(n_blocks, dev, d_results, d_history, max_it, stream, &kernel);
-        break;
-      case NOS_LOSS_EXPONENTIAL:
-        rc = launch_batch_kernel<ProblemT<T, nos::kLossExponential>, T>(n_blocks, dev, d_results, d_history, max_it, stream,
-                                                                        &kernel);
-        break;
-      default:
-        rc = launch_batch_kernel<ProblemT<T, nos::kLossHuber>, T>(n_blocks, dev, d_results, d_history, max_it, stream, &kernel);
-        break;
-    }
-    if (rc == NOS_OK) {
+  if (trip.send()) {
+    const void* const kernel = with_loss(rq[size_t(members[0])].loss_kind, [&](auto loss) {  // one loss for the whole call
+      const auto k = nos::solve_batch_kernel<ProblemT<T, decltype(loss)::value>, T, kBatchBlock>;
+      hipLaunchKernelGGL(k, dim3(uint32_t(B)), dim3(kBatchBlock), 0, slot.stream, trip.dev<const Desc>(descs),
+                         trip.dev<nos::BatchResult>(results), with_history ? trip.dev<double>(history) : nullptr, max_it);
+      return reinterpret_cast<const void*>(k);
+    });
+    if (trip.launched()) {
       slot.last_kernel = kernel;
-      e = hipMemcpyAsync(pinned + desc_bytes, dev_bytes + desc_bytes, result_bytes + history_bytes, hipMemcpyDeviceToHost,
-                         stream);
+      trip.fetch();
     }
   }
-  const hipError_t es = hipStreamSynchronize(stream);  // before the buffer goes back to the pool, after a failure too
-  pool_release(slot, dev, dev_capacity);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess)
-    return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "batched solve: %s", hipGetErrorString(e));
-  if (rc != NOS_OK) return rc;
+  const int status = trip.close("batched solve");
+  if (status != NOS_OK) return status;
 
-  const nos::BatchResult* const results = reinterpret_cast<const nos::BatchResult*>(pinned + desc_bytes);
-  const double* const history = reinterpret_cast<const double*>(pinned + desc_bytes + result_bytes);
   for (size_t j = 0; j < B; ++j) {
     const int i = members[j];
-    const nos::BatchResult& r = results[j];
+    const nos::BatchResult& r = trip.host<const nos::BatchResult>(results)[j];
     for (int k = 0; k < c.nR; ++k) c.R[size_t(i) * c.nR + k] = r.st.R[k];
     for (int k = 0; k < c.nt; ++k) c.t[size_t(i) * c.nt + k] = r.st.t[k];
     if (with_history)
       for (int k = 0; k < r.executed && k < max_it; ++k)
-        c.opt->cost_history[size_t(i) * size_t(max_it) + k] = history[j * size_t(max_it) + k];
+        c.opt->cost_history[size_t(i) * size_t(max_it) + k] = trip.host<const double>(history)[j * size_t(max_it) + k];
     nos_lm_report& rep = c.reports[i];
     rep.iterations = r.st.iteration;
     rep.ok = r.st.ok;

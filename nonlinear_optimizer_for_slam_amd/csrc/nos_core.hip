@@ -208,21 +208,11 @@ template <template <typename, int> class ProblemT, typename T, typename ParamsT>
 int launch_by_loss(int loss_kind, int variant, int blocks_per_cu, int num_cus,
                    const nos::TiledLayout& L, const ParamsT& P, bool nt, double* partials,
                    const nos::FusedFinal& fin, hipStream_t stream, int* rows_out, const SingleBlockArgs* single = nullptr) {
-  switch (loss_kind) {
-    case NOS_LOSS_NONE:
-      if (single) return launch_single<ProblemT<T, nos::kLossNone>, T>(L, P, *single, stream);
-      return launch_by_variant<ProblemT<T, nos::kLossNone>, T>(variant, blocks_per_cu, num_cus, L, P, nt, partials,
-                                                               fin, stream, rows_out);
-    case NOS_LOSS_EXPONENTIAL:
-      if (single) return launch_single<ProblemT<T, nos::kLossExponential>, T>(L, P, *single, stream);
-      return launch_by_variant<ProblemT<T, nos::kLossExponential>, T>(variant, blocks_per_cu, num_cus, L, P, nt,
-                                                                      partials, fin, stream, rows_out);
-    case NOS_LOSS_HUBER:
-      if (single) return launch_single<ProblemT<T, nos::kLossHuber>, T>(L, P, *single, stream);
-      return launch_by_variant<ProblemT<T, nos::kLossHuber>, T>(variant, blocks_per_cu, num_cus, L, P, nt, partials,
-                                                                fin, stream, rows_out);
-  }
-  return fail(NOS_ERR_INVALID_ARGUMENT, "unknown loss kind %d", loss_kind);
+  return with_loss(loss_kind, [&](auto loss) {
+    using Problem = ProblemT<T, decltype(loss)::value>;
+    if (single) return launch_single<Problem, T>(L, P, *single, stream);
+    return launch_by_variant<Problem, T>(variant, blocks_per_cu, num_cus, L, P, nt, partials, fin, stream, rows_out);
+  });
 }
 
 int check_loss(const nos_loss* loss, int* kind_out) {

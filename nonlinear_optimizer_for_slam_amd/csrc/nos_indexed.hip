@@ -31,18 +31,11 @@ int launch_indexed_kernel(const nos::IndexedLayout& L, const typename Problem::P
 template <template <typename, int> class ProblemT, typename T, typename ParamsT>
 int launch_indexed_by_loss(int loss_kind, int n_slots, const nos::IndexedLayout& L, const ParamsT& P, int grid_cap,
                            int num_cus, double* partials, const nos::FusedFinal& fin, hipStream_t stream, int* rows_out) {
-#define NOS_IDX(LOSS_)                                                                                               \
-  return n_slots == 1 ? launch_indexed_kernel<ProblemT<T, LOSS_>, T, 1>(L, P, grid_cap, num_cus, partials, fin, stream, \
-                                                                       rows_out)                                      \
-                      : launch_indexed_kernel<ProblemT<T, LOSS_>, T, 2>(L, P, grid_cap, num_cus, partials, fin, stream, \
-                                                                       rows_out)
-  switch (loss_kind) {
-    case NOS_LOSS_NONE: NOS_IDX(nos::kLossNone);
-    case NOS_LOSS_EXPONENTIAL: NOS_IDX(nos::kLossExponential);
-    case NOS_LOSS_HUBER: NOS_IDX(nos::kLossHuber);
-  }
-#undef NOS_IDX
-  return fail(NOS_ERR_INVALID_ARGUMENT, "unknown loss kind %d", loss_kind);
+  return with_loss(loss_kind, [&](auto loss) {
+    using Problem = ProblemT<T, decltype(loss)::value>;
+    return n_slots == 1 ? launch_indexed_kernel<Problem, T, 1>(L, P, grid_cap, num_cus, partials, fin, stream, rows_out)
+                        : launch_indexed_kernel<Problem, T, 2>(L, P, grid_cap, num_cus, partials, fin, stream, rows_out);
+  });
 }
 
 // One problem in one element type: its item parameters from the request, then the launch by loss and slot count.

@@ -25,6 +25,7 @@
 #include <string>
 #include <thread>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nos.h"
@@ -121,7 +122,9 @@ struct DeviceSlot {
   size_t stage_bytes = 0;
   void* pack_pinned[2] = {nullptr, nullptr};  // pinned host staging of the host-pack ingestion: [n_fields][chunk] elements
   size_t pack_bytes = 0;
-  void* batch_pinned = nullptr;  // pinned host staging of the batched solve (nos_batch.hip): descriptors up, results down
+  // pinned host staging of a batched call (BatchTrip, batch_host.hpp: the batched solve, the batched registrations, the
+  // score batch): what goes up, then what comes down; grows only
+  void* batch_pinned = nullptr;
   size_t batch_pinned_bytes = 0;
   hipEvent_t pack_done[2] = {nullptr, nullptr};
   // Device-buffer pool for dataset storage: nos_dataset_destroy parks the buffer here, the next dataset of a similar
@@ -358,11 +361,16 @@ struct DeviceBuffers {
   }
 };
 
+// A 3-D pose into whatever holds one as double R[9], t[3]: a PosePod, the descriptor of a registration or of a score.
+template <typename Holder>
+inline void set_pose(Holder& h, const double R[9], const double t[3]) {
+  for (int k = 0; k < 9; ++k) h.R[k] = R[k];
+  for (int k = 0; k < 3; ++k) h.t[k] = t[k];
+}
 // The pose the matcher and the store's insert warp a scan by, as their kernels take it.
 inline nos::PosePod make_pose(const double R[9], const double t[3]) {
   nos::PosePod pose;
-  for (int k = 0; k < 9; ++k) pose.R[k] = R[k];
-  for (int k = 0; k < 3; ++k) pose.t[k] = t[k];
+  set_pose(pose, R, t);
   return pose;
 }
 
@@ -453,6 +461,16 @@ int unpack_records(int dtype, const unsigned char* d_rec, size_t stride, const n
                    size_t first, size_t count, const nos::TiledLayout& L, void* dst, hipStream_t stream);
 // nos_core.hip
 int check_loss(const nos_loss* loss, int* kind_out);
+// The one switch from a loss kind to its instantiation: f(std::integral_constant<int, LOSS>) → what f returns.
+// Precondition: check_loss accepted the kind (directly or through build_request), so what is neither is Huber.
+template <typename F>
+inline auto with_loss(int loss_kind, F&& f) {
+  switch (loss_kind) {
+    case NOS_LOSS_NONE: return f(std::integral_constant<int, nos::kLossNone>{});
+    case NOS_LOSS_EXPONENTIAL: return f(std::integral_constant<int, nos::kLossExponential>{});
+    default: return f(std::integral_constant<int, nos::kLossHuber>{});
+  }
+}
 int build_request(int problem, const nos_dataset* ds, const double* R, int nR, const double* t, int nt,
                   const double* intr, double min_depth, const nos_loss* loss, Request* rq);
 // mailbox descriptor for the in-launch cross-rank exchange, and the time-out flag the kernels raise in the pinned block
@@ -488,6 +506,14 @@ inline int check_live_store(const LiveStore& s) {
                 "the search ball spans more than %d voxel cells per axis (2 r / resolution + 2 = %g): match against a snapshot",
                 nos::kVoxelMatchMaxSpan, s.span);
   if (s.broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+  return NOS_OK;
+}
+// What a batched registration and a score batch reject of their scans: every scan there, and of the map's context.
+inline int check_scans(const nos_ctx* ctx, nos_scan* const* scans, int n) {
+  for (int i = 0; i < n; ++i) {
+    if (scans[i] == nullptr) return fail(NOS_ERR_INVALID_ARGUMENT, "scan %d is NULL", i);
+    if (scans[i]->ctx != ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "scan %d belongs to another context than the map", i);
+  }
   return NOS_OK;
 }
 // nos_voxelregister.hip: a batched registration against the store.  store == NULL: the map argument was NULL.

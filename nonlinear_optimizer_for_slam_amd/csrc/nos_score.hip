@@ -5,7 +5,7 @@
 // nos::score_batch_kernel (score_kernels.hpp): matches, matched points and the cost Σ ρ per problem, nothing written in
 // between.  One upload of descriptors, two launches on one stream (the chunks, then the per-problem sums), one copy back,
 // one host wait; the memory of a call follows the scans and the batch, never the map.
-#include "nos_internal.hpp"
+#include "batch_host.hpp"
 #include "score_kernels.hpp"
 
 static_assert(sizeof(nos_pose_score) == 32 && sizeof(nos::ScoreRow) == sizeof(nos_pose_score), "nos_pose_score layout");
@@ -27,66 +27,31 @@ struct ScoreCall {
   nos_pose_score* scores;
 };
 
-// The launch for one view: the six instantiations of a call's kernel, by loss.  → the kernel's host address.
-template <typename View>
-const void* launch_score(const View& view, unsigned int* d_error, int loss_kind, uint32_t n_blocks, const nos::ScoreDesc* d_descs,
-                         const uint2* d_blocks, const nos::ScoreLoss& loss, int max_neighbors, nos::ScorePartial* d_partials,
-                         hipStream_t stream) {
-  const auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(nos::kScoreBlock), 0, stream, view, d_error, d_descs, d_blocks, loss,
-                       max_neighbors, d_partials);
-    return reinterpret_cast<const void*>(kernel);
-  };
-  switch (loss_kind) {  // one loss for the whole call
-    case NOS_LOSS_NONE: return go(nos::score_batch_kernel<View, nos::kLossNone>);
-    case NOS_LOSS_EXPONENTIAL: return go(nos::score_batch_kernel<View, nos::kLossExponential>);
-    default: return go(nos::score_batch_kernel<View, nos::kLossHuber>);
-  }
-}
-
-// Descriptors and the block list up through pinned memory, one pooled device block for them, the chunk partials and the
-// rows, the two launches, the rows down in one copy, one synchronisation, then the caller's array.
+// Descriptors and the block list up through pinned memory, one pooled device block for them, the rows and the chunk
+// partials, the two launches, the rows down in one copy, one synchronisation (BatchTrip), then the caller's array.
 template <typename View>
 int run_score(const ScoreCall& c, int loss_kind, const View& view, unsigned int* d_error) {
-  nos_ctx* ctx = c.ctx;
-  DeviceSlot& slot = ctx->slots[0];
+  DeviceSlot& slot = c.ctx->slots[0];
   hipStream_t stream = slot.stream;
   const size_t B = size_t(c.n);
   uint64_t total_blocks = 0;
   for (size_t i = 0; i < B; ++i) total_blocks += (uint64_t(c.scans[i]->n) + nos::kScoreChunkPoints - 1) / nos::kScoreChunkPoints;
   if (total_blocks >= (uint64_t(1) << 31)) return fail(NOS_ERR_UNSUPPORTED, "too many points for one score call");
-  auto round_up = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t desc_bytes = round_up(B * sizeof(nos::ScoreDesc));
-  const size_t block_bytes = round_up(size_t(total_blocks) * sizeof(uint2));
-  const size_t row_bytes = round_up((B + 1) * sizeof(nos::ScoreRow));
-  const size_t partial_bytes = round_up(size_t(total_blocks) * sizeof(nos::ScorePartial));
-  const size_t up_bytes = desc_bytes + block_bytes;
-  const size_t pinned_total = up_bytes + row_bytes;
-
-  NOS_HIP_CHECK(hipSetDevice(slot.device));
-  if (slot.batch_pinned_bytes < pinned_total) {  // grows only; freed with the context
-    if (slot.batch_pinned != nullptr) (void)hipHostFree(slot.batch_pinned);
-    slot.batch_pinned = nullptr;
-    slot.batch_pinned_bytes = 0;
-    NOS_HIP_CHECK(hipHostMalloc(&slot.batch_pinned, pinned_total, hipHostMallocDefault));
-    slot.batch_pinned_bytes = pinned_total;
-  }
-  void* dev = nullptr;
-  size_t dev_capacity = 0;
-  int rc = pool_alloc(slot, pinned_total + partial_bytes, &dev, &dev_capacity);
+  BatchTrip trip(slot);
+  const auto descs = trip.section(BatchTrip::kUp, B * sizeof(nos::ScoreDesc));
+  const auto blocks = trip.section(BatchTrip::kUp, size_t(total_blocks) * sizeof(uint2));
+  const auto rows = trip.section(BatchTrip::kDown, (B + 1) * sizeof(nos::ScoreRow));
+  const auto partials = trip.section(BatchTrip::kDeviceOnly, size_t(total_blocks) * sizeof(nos::ScorePartial));
+  const int rc = trip.open();
   if (rc != NOS_OK) return rc;
-  unsigned char* const dev_bytes = static_cast<unsigned char*>(dev);
-  unsigned char* const pinned = static_cast<unsigned char*>(slot.batch_pinned);
-  nos::ScoreDesc* const h_descs = reinterpret_cast<nos::ScoreDesc*>(pinned);
-  uint2* const h_blocks = reinterpret_cast<uint2*>(pinned + desc_bytes);
+  uint2* const h_blocks = trip.host<uint2>(blocks);
   uint32_t next_block = 0;
   for (size_t i = 0; i < B; ++i) {
     const nos_scan* scan = c.scans[i];
-    nos::ScoreDesc& d = *new (h_descs + i) nos::ScoreDesc{};
+    nos::ScoreDesc& d = *new (trip.host<nos::ScoreDesc>(descs) + i) nos::ScoreDesc{};
     d.points = scan->d_planes;
     d.n_points = scan->n;
-    for (int k = 0; k < 9; ++k) d.R[k] = c.R[9 * i + k];
-    for (int k = 0; k < 3; ++k) d.t[k] = c.t[3 * i + k];
+    set_pose(d, c.R + 9 * i, c.t + 3 * i);
     d.first_block = next_block;
     d.n_chunks = uint32_t((uint64_t(scan->n) + nos::kScoreChunkPoints - 1) / nos::kScoreChunkPoints);
     for (uint32_t k = 0; k < d.n_chunks; ++k) h_blocks[next_block + k] = make_uint2(uint32_t(i), k);
@@ -94,33 +59,29 @@ int run_score(const ScoreCall& c, int loss_kind, const View& view, unsigned int*
   }
   nos::ScoreLoss loss{};
   fill_loss(c.loss, loss.la, loss.lb, loss.lc);
-  const nos::ScoreDesc* const d_descs = reinterpret_cast<const nos::ScoreDesc*>(dev_bytes);
-  const uint2* const d_blocks = reinterpret_cast<const uint2*>(dev_bytes + desc_bytes);
-  nos::ScoreRow* const d_rows = reinterpret_cast<nos::ScoreRow*>(dev_bytes + up_bytes);
-  nos::ScorePartial* const d_partials = reinterpret_cast<nos::ScorePartial*>(dev_bytes + pinned_total);
-  hipError_t e = hipMemcpyAsync(dev, pinned, up_bytes, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess && d_error != nullptr) e = hipMemsetAsync(d_error, 0, sizeof(unsigned int), stream);
-  if (e == hipSuccess) {
+  const nos::ScoreDesc* const d_descs = trip.dev<const nos::ScoreDesc>(descs);
+  nos::ScorePartial* const d_partials = trip.dev<nos::ScorePartial>(partials);
+  if (trip.send() && (d_error == nullptr || trip.check(hipMemsetAsync(d_error, 0, sizeof(unsigned int), stream)))) {
     if (next_block > 0) {
-      slot.last_kernel = launch_score(view, d_error, loss_kind, next_block, d_descs, d_blocks, loss, c.max_neighbors, d_partials, stream);
+      slot.last_kernel = with_loss(loss_kind, [&](auto kind) {  // one loss for the whole call
+        const auto kernel = nos::score_batch_kernel<View, decltype(kind)::value>;
+        hipLaunchKernelGGL(kernel, dim3(next_block), dim3(nos::kScoreBlock), 0, stream, view, d_error, d_descs,
+                           trip.dev<const uint2>(blocks), loss, c.max_neighbors, d_partials);
+        return reinterpret_cast<const void*>(kernel);
+      });
       if (slot.prof_on && slot.prof_every == 0) ++slot.prof_launches;  // SELF-REPORTED (bracket profiler)
     }
     hipLaunchKernelGGL(nos::score_finish_kernel, dim3(unsigned((B + nos::kScoreBlock - 1) / nos::kScoreBlock)),
-                       dim3(nos::kScoreBlock), 0, stream, d_descs, uint32_t(B), d_partials, d_error, d_rows);
+                       dim3(nos::kScoreBlock), 0, stream, d_descs, uint32_t(B), d_partials, d_error, trip.dev<nos::ScoreRow>(rows));
     if (slot.prof_on && slot.prof_every == 0) ++slot.prof_launches;
-    const hipError_t el = hipGetLastError();
-    if (el != hipSuccess) rc = fail(NOS_ERR_HIP, "score launch failed: %s", hipGetErrorString(el));
-    if (rc == NOS_OK) e = hipMemcpyAsync(pinned + up_bytes, d_rows, row_bytes, hipMemcpyDeviceToHost, stream);
+    if (trip.launched()) trip.fetch();
   }
-  const hipError_t es = hipStreamSynchronize(stream);  // before the buffer goes back to the pool, after a failure too
-  pool_release(slot, dev, dev_capacity);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return hip_fail(e, "score batch");
-  if (rc != NOS_OK) return rc;
-  const nos::ScoreRow* const rows = reinterpret_cast<const nos::ScoreRow*>(pinned + up_bytes);
-  if (rows[0].matches != 0)  // live store only; before anything of the caller's is written
+  const int status = trip.close("score batch");
+  if (status != NOS_OK) return status;
+  const nos::ScoreRow* const h_rows = trip.host<const nos::ScoreRow>(rows);
+  if (h_rows[0].matches != 0)  // live store only; before anything of the caller's is written
     return fail(NOS_ERR_HIP, "scoring against the voxel store failed: a table probe ran through the whole table");
-  memcpy(c.scores, rows + 1, B * sizeof(nos_pose_score));
+  memcpy(c.scores, h_rows + 1, B * sizeof(nos_pose_score));
   return NOS_OK;
 }
 
@@ -133,10 +94,8 @@ int score_batch(const ScoreCall& c, const Checks& more_checks, const View& view,
   if (!c.ctx || !c.scans || !c.R || !c.t || !c.scores) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL array");
   nos_ctx* ctx = c.ctx;
   CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  for (int i = 0; i < c.n; ++i) {
-    if (c.scans[i] == nullptr) return fail(NOS_ERR_INVALID_ARGUMENT, "scan %d is NULL", i);
-    if (c.scans[i]->ctx != ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "scan %d belongs to another context than the map", i);
-  }
+  const int rc_scans = check_scans(ctx, c.scans, c.n);
+  if (rc_scans != NOS_OK) return rc_scans;
   int loss_kind = 0;
   const int rc = check_loss(c.loss, &loss_kind);
   if (rc != NOS_OK) return rc;

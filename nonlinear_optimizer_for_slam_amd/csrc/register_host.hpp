@@ -3,7 +3,7 @@
 // the caller's Launcher, the copy back.  One copy of each step; the two units differ in the map view and the kernel only.
 #pragma once
 
-#include "nos_internal.hpp"
+#include "batch_host.hpp"
 #include "assemble_register.hpp"
 
 namespace nosd {
@@ -39,7 +39,7 @@ inline void fill_loss_params(nos::Ndt3Params<T>& P, const double R[9], const dou
 }
 
 // Descriptors up through pinned memory, one pooled device block for descriptors, results, round log and every problem's
-// scratch dataset, one launch, results and log down in one copy, one synchronisation, then the caller's arrays.
+// scratch dataset, one launch, results and log down in one copy, one synchronisation (BatchTrip), then the caller's arrays.
 // Launcher: the map and its kernel (SnapshotLauncher of nos_register.hip, LiveLauncher of nos_voxelregister.hip):
 //   static constexpr bool kTallyLaunch               whether the launch is added to the bracket profiler's tally
 //   hipError_t prepare(stream)                        what must be on the stream before the launch
@@ -52,98 +52,57 @@ int run_register(const RegisterCall& c, int loss_kind, const Launcher& launcher)
   hipStream_t stream = slot.stream;
   const size_t B = size_t(c.n);
   const int max_outer = c.ropt->max_outer_iterations;
-  auto round_up = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t desc_bytes = round_up(B * sizeof(Desc));
-  const size_t result_bytes = round_up(B * sizeof(nos::RegisterResult));
-  const size_t log_bytes = round_up(B * size_t(max_outer) * sizeof(nos::RegisterRound));
-  const size_t pinned_total = desc_bytes + result_bytes + log_bytes;
   // scratch datasets: the layout nos_ndt_match gives a dataset of 2n slots of this element type
   const int tile_log2 = dataset_tile_log2(ctx, c.ropt->dtype);
   if (tile_log2 != 0 && (tile_log2 < 10 || tile_log2 > 24)) return fail(NOS_ERR_INVALID_ARGUMENT, "tile_log2 out of range");
+  BatchTrip trip(slot);
+  const auto descs = trip.section(BatchTrip::kUp, B * sizeof(Desc));
+  const auto results = trip.section(BatchTrip::kDown, B * sizeof(nos::RegisterResult));
+  const auto log = trip.section(BatchTrip::kDown, B * size_t(max_outer) * sizeof(nos::RegisterRound));
   std::vector<nos::TiledLayout> layouts(B);
-  std::vector<size_t> offsets(B);
-  size_t scratch_bytes = 0;
+  std::vector<BatchTrip::Section> scratch(B);
   for (size_t i = 0; i < B; ++i) {
     layouts[i] = make_layout(2 * c.scans[i]->n, nos::kNdtStored, tile_log2, ctx->settings.plane_skew);
-    offsets[i] = scratch_bytes;
-    scratch_bytes += round_up(layout_elems(layouts[i], nos::kNdtStored) * sizeof(T));
+    scratch[i] = trip.section(BatchTrip::kDeviceOnly, layout_elems(layouts[i], nos::kNdtStored) * sizeof(T));
   }
-
-  NOS_HIP_CHECK(hipSetDevice(slot.device));
-  if (slot.batch_pinned_bytes < pinned_total) {  // grows only; freed with the context
-    if (slot.batch_pinned != nullptr) (void)hipHostFree(slot.batch_pinned);
-    slot.batch_pinned = nullptr;
-    slot.batch_pinned_bytes = 0;
-    NOS_HIP_CHECK(hipHostMalloc(&slot.batch_pinned, pinned_total, hipHostMallocDefault));
-    slot.batch_pinned_bytes = pinned_total;
-  }
-  void* dev = nullptr;
-  size_t dev_capacity = 0;
-  int rc = pool_alloc(slot, pinned_total + scratch_bytes, &dev, &dev_capacity);
+  const int rc = trip.open();
   if (rc != NOS_OK) return rc;
-  unsigned char* const dev_bytes = static_cast<unsigned char*>(dev);
-  unsigned char* const scratch = dev_bytes + pinned_total;
-  unsigned char* const pinned = static_cast<unsigned char*>(slot.batch_pinned);
   for (size_t i = 0; i < B; ++i) {
     const nos_scan* scan = c.scans[i];
-    Desc& d = *new (pinned + i * sizeof(Desc)) Desc{};
+    Desc& d = *new (trip.host<Desc>(descs) + i) Desc{};
     d.L = layouts[i];
-    d.L.base = scratch + offsets[i];
+    d.L.base = trip.dev<unsigned char>(scratch[i]);
     fill_loss_params(d.P, c.R + 9 * i, c.t + 3 * i, c.loss);
     d.points = scan->d_planes;
     d.n_points = scan->n;
     d.n_chunks = uint32_t((std::max<uint64_t>(d.L.n, 1) + kRegisterBlock - 1) / kRegisterBlock);
     d.dof = c.dof;
-    for (int k = 0; k < 9; ++k) d.R[k] = c.R[9 * i + k];
-    for (int k = 0; k < 3; ++k) d.t[k] = c.t[3 * i + k];
+    set_pose(d, c.R + 9 * i, c.t + 3 * i);
     d.settings = make_lm_settings(c.opt, 0, kKindNdt);  // as lm_solve; a matcher-written dataset has simd_class 0
   }
-  nos::RegisterResult* const d_results = reinterpret_cast<nos::RegisterResult*>(dev_bytes + desc_bytes);
-  nos::RegisterRound* const d_log = reinterpret_cast<nos::RegisterRound*>(dev_bytes + desc_bytes + result_bytes);
-  const void* kernel = nullptr;
-  hipError_t e = hipMemcpyAsync(dev, pinned, desc_bytes, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = launcher.prepare(stream);
-  if (e == hipSuccess) {
-    const Desc* const d_descs = static_cast<const Desc*>(dev);
-    const uint32_t n_blocks = uint32_t(B);
-    switch (loss_kind) {  // one loss for the whole call
-      case NOS_LOSS_NONE:
-        kernel = launcher.template launch<ProblemT<T, nos::kLossNone>, T>(n_blocks, d_descs, d_results, d_log, c.ropt, stream);
-        break;
-      case NOS_LOSS_EXPONENTIAL:
-        kernel = launcher.template launch<ProblemT<T, nos::kLossExponential>, T>(n_blocks, d_descs, d_results, d_log, c.ropt,
-                                                                                 stream);
-        break;
-      default:
-        kernel = launcher.template launch<ProblemT<T, nos::kLossHuber>, T>(n_blocks, d_descs, d_results, d_log, c.ropt, stream);
-        break;
-    }
-    const hipError_t el = hipGetLastError();
-    if (el != hipSuccess) rc = fail(NOS_ERR_HIP, "batched registration launch failed: %s", hipGetErrorString(el));
-    if (rc == NOS_OK) {
+  if (trip.send() && trip.check(launcher.prepare(stream))) {
+    const void* const kernel = with_loss(loss_kind, [&](auto loss) {  // one loss for the whole call
+      return launcher.template launch<ProblemT<T, decltype(loss)::value>, T>(
+          uint32_t(B), trip.dev<const Desc>(descs), trip.dev<nos::RegisterResult>(results), trip.dev<nos::RegisterRound>(log),
+          c.ropt, stream);
+    });
+    if (trip.launched()) {
       slot.last_kernel = kernel;
       // bracket profiling (nos_ctx_profile_begin with sample_every = 0): the call's one launch, SELF-REPORTED, for the
       // launchers that ask for it (the snapshot's never reported its launch and still does not)
       if (Launcher::kTallyLaunch && slot.prof_on && slot.prof_every == 0) ++slot.prof_launches;
-      e = hipMemcpyAsync(pinned + desc_bytes, dev_bytes + desc_bytes, result_bytes + log_bytes, hipMemcpyDeviceToHost, stream);
+      trip.fetch();
     }
   }
-  const hipError_t es = hipStreamSynchronize(stream);  // before the buffer goes back to the pool, after a failure too
-  pool_release(slot, dev, dev_capacity);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess)
-    return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "batched registration: %s",
-                hipGetErrorString(e));
-  if (rc != NOS_OK) return rc;
+  const int status = trip.close("batched registration");
+  if (status != NOS_OK) return status;
 
-  const nos::RegisterResult* const results = reinterpret_cast<const nos::RegisterResult*>(pinned + desc_bytes);
-  const nos::RegisterRound* const log = reinterpret_cast<const nos::RegisterRound*>(pinned + desc_bytes + result_bytes);
   static_assert(sizeof(nos::RegisterRound) == sizeof(nos_register_round), "round log entry layout");
   for (size_t i = 0; i < B; ++i)  // live store only; before anything of the caller's is written
-    if (results[i].probe_error != 0)
+    if (trip.host<const nos::RegisterResult>(results)[i].probe_error != 0)
       return fail(NOS_ERR_HIP, "batched registration against the voxel store failed: a table probe ran through the whole table");
   for (size_t i = 0; i < B; ++i) {
-    const nos::RegisterResult& r = results[i];
+    const nos::RegisterResult& r = trip.host<const nos::RegisterResult>(results)[i];
     for (int k = 0; k < 9; ++k) c.R[9 * i + k] = r.R[k];
     for (int k = 0; k < 3; ++k) c.t[3 * i + k] = r.t[k];
     nos_register_report& rep = c.reports[i];
@@ -156,7 +115,7 @@ int run_register(const RegisterCall& c, int loss_kind, const Launcher& launcher)
       for (int k = 0; k < max_outer; ++k) {
         nos_register_round& o = row[k];
         if (k < r.rounds) {
-          const nos::RegisterRound& g = log[i * size_t(max_outer) + size_t(k)];
+          const nos::RegisterRound& g = trip.host<const nos::RegisterRound>(log)[i * size_t(max_outer) + size_t(k)];
           o.matches = g.matches;
           o.used = g.used;
           o.iterations = g.iterations;
@@ -181,10 +140,8 @@ int register_batch(const RegisterCall& c, const Checks& more_checks, const Launc
   if (!c.ctx || !c.scans || !c.R || !c.t || !c.ropt || !c.opt || !c.reports) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL array");
   nos_ctx* ctx = c.ctx;
   CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
-  for (int i = 0; i < c.n; ++i) {
-    if (c.scans[i] == nullptr) return fail(NOS_ERR_INVALID_ARGUMENT, "scan %d is NULL", i);
-    if (c.scans[i]->ctx != ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "scan %d belongs to another context than the map", i);
-  }
+  const int rc_scans = check_scans(ctx, c.scans, c.n);
+  if (rc_scans != NOS_OK) return rc_scans;
   const nos_register_options& ro = *c.ropt;
   if (ro.max_outer_iterations < 1) return fail(NOS_ERR_INVALID_ARGUMENT, "max_outer_iterations < 1");
   if (ro.keep_multiple < 0) return fail(NOS_ERR_INVALID_ARGUMENT, "keep_multiple < 0");

@@ -1,9 +1,9 @@
-"""Are the matcher and registration kernels of two source trees the same kernels?  Compares gfx950 assembly as TEXT.
+"""Are the matcher, registration, batched-solve and score kernels of two source trees the same kernels?  Compares gfx950 assembly as TEXT.
 
 usage: python tools/compare_kernel_asm.py OLD_CSRC NEW_CSRC [--jobs N] [--units a,b,...] [--all-kernels]
                                                                                (the table goes to stdout)
 
-Every unit that holds a matcher or registration kernel (UNITS) is compiled from both csrc directories with the Makefile's
+Every unit that holds one of those kernels (UNITS) is compiled from both csrc directories with the Makefile's
 flags and `-S --cuda-device-only`; the body of each kernel named in KERNELS — from its label to its s_endpgm — is looked up
 by demangled name and compared line for line.  Two things are normalised, both of them numbering, not code: the index of
 the function inside its unit in local labels (.LBB12_3 → .LBB_3: a kernel that moved from a .hip file into a header is
@@ -20,9 +20,9 @@ from concurrent.futures import ThreadPoolExecutor
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall"]  # HIPFLAGS of csrc/Makefile
-UNITS = ("nos_match", "nos_indexed", "nos_voxelmap", "nos_register", "nos_voxelregister")
+UNITS = ("nos_match", "nos_indexed", "nos_voxelmap", "nos_register", "nos_voxelregister", "nos_batch", "nos_score")
 KERNELS = ("match_kernel<", "voxel_match_kernel<", "match_index_kernel(", "voxel_match_index_kernel(", "voxel_rank_ids_kernel(",
-           "register_batch_kernel<", "register_live_kernel<")
+           "register_batch_kernel<", "register_live_kernel<", "solve_batch_kernel<", "score_batch_kernel<", "score_finish_kernel(")
 
 
 def assembly(csrc, unit, out_dir):
