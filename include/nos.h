@@ -472,6 +472,32 @@ int nos_voxel_map_prune(nos_voxel_map* map, const nos_voxel_prune* what, size_t*
  * something). */
 int nos_voxel_map_memory(const nos_voxel_map* map, size_t* capacity, size_t* bytes,
                          unsigned long long* epoch, unsigned long long* generation);
+/* Merge one voxel store into another under a pose: every voxel of `src` (its count and nine sums, nothing else) is moved by
+ * p' = R p + t into the grid of `dst` and added to the voxel it lands in — submaps composed at corrected poses, two
+ * sessions joined, a coarser level of a map pyramid — at a cost that follows the VOXELS of src, not its points.
+ *   With n = count, s and M the sums about the corner o of the source cell, mu = o + s / n:
+ *   destination cell c' = floor((R mu + t)_k * inv_res) per axis, inv_res = 1.0 / dst's resolution and the multiply-adds
+ *   of nos_voxel_map_insert_scan's warp: the cell an insert_scan would put a point at the source voxel's mean into.  The
+ *   WHOLE voxel goes there (a voxel is never split); means that lie in their cell stay there under the convex
+ *   combinations a merge forms, which is what nos_voxel_map_match (see its caveat) relies on.
+ *   With o' the corner of c' and b = (R o + t) - o' (formed once):  s' = R s + n b,
+ *   M' = R M R^T + (R s) b^T + b (R s)^T + n b b^T;  source voxels that land in one cell are added in ascending source
+ *   voxel id, then count += n', sums += (s', M') and the usual per-voxel finish, as an insert does.
+ * Exact (bit for bit an insert of the transformed points) when every product and sum above is exact: an axis rotation, a
+ * translation by whole cells, power-of-two resolutions and points on a binary lattice.  Otherwise mean and covariance
+ * differ from an insert of the transformed points by rounding, and a voxel whose points straddle destination cells goes
+ * to the cell of its mean where an insert would have split it.  Voxels below min_points contribute like any other.
+ * src is read-only: its voxels, epoch, generation and stamps stay as they were.  src and dst may differ in resolution,
+ * search radius and flags.  Voxel ids follow the rule of an insert: a merge is ONE batch, new voxels are appended in
+ * ascending destination cell; dst's epoch advances by one and the touched voxels are stamped with it; n_points grows by
+ * src's.  R is not checked for orthonormality.  An empty src is a no-op that leaves the epoch alone.
+ * *n_touched (optional) = destination voxels touched.  Rejected before anything runs or is written, *n_touched included:
+ *   NOS_ERR_INVALID_ARGUMENT  dst, src, R or t NULL, dst == src, different contexts, a non-finite entry of R or t (or
+ *                             finite entries so large that a source voxel's moments overflow);
+ *   NOS_ERR_HIP               either store was left undefined by an earlier failure;
+ *   NOS_ERR_UNSUPPORTED       a destination cell outside +-2^20 per axis, or source voxels landing in one cell with more
+ *                             than 2^32 - 1 points together: the message names the source voxel id, dst is bit for bit as before. */
+int nos_voxel_map_merge(nos_voxel_map* dst, const nos_voxel_map* src, const double R[9], const double t[3], size_t* n_touched);
 int nos_voxel_map_destroy(nos_voxel_map* map);
 
 /* ---- the hot path -------------------------------------------------------------
@@ -716,6 +742,14 @@ int nos_debug_lm_step(nos_ctx* ctx, int dof, const double* sums, const double se
  * flags: 0 or NOS_MAP_PROPER_SQRT_INFORMATION.  An invalid voxel: sqrt_information identity, *valid = 0 (and mean 0 below min_points). */
 int nos_debug_voxel_finish(uint32_t count, const double sums[9], const int64_t cell[3], double voxel_resolution,
                            const double params[3], int flags, double mean[3], double sqrt_information[9], unsigned char* valid);
+
+/* Test hook: the moment transform of nos_voxel_map_merge computed ON THE HOST by the function its kernel calls (no GPU
+ * call, no context).  count >= 1 and sums[9] about the corner of `cell` in a grid of edge src_resolution (as
+ * nos_debug_voxel_finish takes them) -> cell_out, the destination cell in a grid of edge dst_resolution, and sums_out[9]
+ * about that cell's corner.  NOS_ERR_UNSUPPORTED when the destination cell is not representable in 64 bits. */
+int nos_debug_voxel_moments(uint32_t count, const double sums[9], const int64_t cell[3], double src_resolution,
+                            const double R[9], const double t[3], double dst_resolution,
+                            int64_t cell_out[3], double sums_out[9]);
 
 /* ---- pose-graph optimisation (BASELINE.json configs[4]) --------
  * The reference's PoseGraphOptimizerAnalytic::Solve is an empty loop

@@ -810,6 +810,7 @@ class VoxelMap:
         self._h = None
         h = ctypes.c_void_p()
         flags = int(bool(proper_sqrt_information)) if flags is None else int(flags)
+        self.voxel_resolution, self.search_radius_sq, self._flags = float(voxel_resolution), float(search_radius_sq), flags
         check(self._lib.nos_voxel_map_create(ctx.handle, ctypes.c_double(voxel_resolution), ctypes.c_double(search_radius_sq),
                                              flags, int(capacity), ctypes.byref(h)), "nos_voxel_map_create")
         self._h = h
@@ -830,6 +831,31 @@ class VoxelMap:
         check(self._lib.nos_voxel_map_insert_scan(self._h, scan._h, _dp(R), _dp(t), ctypes.byref(n)),
               "nos_voxel_map_insert_scan")
         return int(n.value)
+
+    def merge(self, other, R=None, t=None):
+        """Every voxel of another VoxelMap moved by R p + t (default: the identity) and added to the voxels of this one
+        (nos_voxel_map_merge) → number of voxels of this store the merge touched.  Only `other`'s counts and sums are read:
+        the cost follows its voxels, not its points, and it may differ in resolution, search radius and flags.  A source
+        voxel goes, whole, to the cell its transformed mean falls into.  `other` is not modified."""
+        R = _dvec(np.eye(3) if R is None else R, 9)
+        t = _dvec(np.zeros(3) if t is None else t, 3)
+        n = ctypes.c_size_t()
+        check(self._lib.nos_voxel_map_merge(self._h, other._h, _dp(R), _dp(t), ctypes.byref(n)), "nos_voxel_map_merge")
+        return int(n.value)
+
+    def coarsened(self, factor, search_radius_sq=None):
+        """→ a new VoxelMap at voxel_resolution · factor filled by merge(self): one level of a multi-resolution map, built
+        from this store's voxels without the points.  search_radius_sq defaults to this store's · factor²; the flags are
+        this store's.  The new store is closed before an exception leaves."""
+        factor = float(factor)
+        radius = self.search_radius_sq * factor * factor if search_radius_sq is None else search_radius_sq
+        out = VoxelMap(self._ctx, self.voxel_resolution * factor, radius, flags=self._flags)
+        try:
+            out.merge(self)
+        except Exception:
+            out.close()
+            raise
+        return out
 
     def snapshot(self):
         """→ NdtMap of the store as it is now; it stays valid after later inserts and after close()."""

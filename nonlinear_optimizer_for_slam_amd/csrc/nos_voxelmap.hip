@@ -6,6 +6,7 @@
 
 #include "voxelmap_kernels.hpp"
 #include "voxelmatch_kernels.hpp"
+#include "voxelmerge_kernels.hpp"
 
 using namespace nosd;
 
@@ -119,6 +120,49 @@ int store_reserve(nos_voxel_map* vm, size_t need) {
                      block_bytes, nv, capacity);
 }
 
+// The back half of an insert and of a merge, ONE copy: U runs (keys ascending and unique, their counts, their nine sums
+// about the corner of the key's cell) go into the store — room for them, lookup, rank of the misses, voxel_merge_kernel
+// (count += n, acc += seg, the finish, stamp = epoch + 1), the closing wait and the bookkeeping.  Nothing of the store is
+// written before the merge kernel; `buf` is the caller's arena, `points` what the runs hold together.
+int store_merge_runs(nos_voxel_map* vm, DeviceBuffers& buf, const uint64_t* run_key, const uint32_t* run_count,
+                     const double* seg_acc, uint32_t U, unsigned long long points, const char* what, size_t* n_touched) {
+  hipStream_t st = vm->ctx->slots[0].stream;
+  unsigned int h_info[nos::kInfoWords] = {};
+  uint32_t *run_slot = nullptr, *miss = nullptr, *rank = nullptr;
+  int rc = store_reserve(vm, size_t(vm->n_voxels) + U);  // load factor <= 1/2 whatever the number of new voxels
+  if (rc != NOS_OK) return rc;
+  PrimTmp t_rank;
+  const auto rank_misses = [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, miss, rank, 0u, size_t(U), rocprim::plus<uint32_t>(), st); };
+  hipError_t e = buf.alloc(&run_slot, U);
+  if (e == hipSuccess) e = buf.alloc(&miss, U);
+  if (e == hipSuccess) e = buf.alloc(&rank, U);
+  if (e == hipSuccess) e = prim_plan(buf, rank_misses, t_rank);
+  if (e != hipSuccess) return hip_fail(e, what);
+  const nos::MapBuildParams prm{5, 0.01, 0.01, (vm->flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0, vm->voxel_resolution};
+  const dim3 ugrid(unsigned((size_t(U) + 255) / 256));
+  hipLaunchKernelGGL(nos::voxel_lookup_kernel, ugrid, dim3(256), 0, st, vm->view, run_key, U, run_slot, miss, vm->d_info);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = prim_run(rank_misses, t_rank);
+  if (e != hipSuccess) return hip_fail(e, what);  // still nothing written
+  hipLaunchKernelGGL(nos::voxel_merge_kernel, ugrid, dim3(256), 0, st, vm->view, run_key, run_count, seg_acc, run_slot, rank, U, prm,
+                     uint32_t(vm->epoch + 1), vm->d_info);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(h_info, vm->d_info, 5 * sizeof(unsigned int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the wait at the end
+  if (e != hipSuccess || h_info[nos::kInfoProbeError] != 0) {
+    vm->broken = true;
+    if (e != hipSuccess) return hip_fail(e, what);
+    return fail(NOS_ERR_HIP, "%s failed: a table probe found no free entry", what);
+  }
+  vm->n_voxels += h_info[nos::kInfoNew];
+  vm->view.n_voxels = vm->n_voxels;
+  vm->n_valid = size_t(int(h_info[nos::kInfoValid]));
+  vm->n_points += points;
+  ++vm->epoch;  // what the merge stamped the touched slots with
+  if (n_touched) *n_touched = U;
+  return NOS_OK;
+}
+
 // One insert.  host_xyz != nullptr: [n][3] in the map frame; otherwise d_planes = 3 planes of n doubles in a local frame,
 // warped by `pose` on the device.
 int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const double* d_planes, const nos::PosePod& pose,
@@ -134,7 +178,6 @@ int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const doub
   DeviceBuffers buf(&slot);  // arena: every temporary comes from the slot's buffer pool — no hipMalloc / hipFree per insert
   double *rec = nullptr, *staged = nullptr, *seg_acc = nullptr;
   KeyGroups<uint64_t> g;  // the batch grouped by voxel: a run = the points of one voxel, in point order
-  uint32_t *run_slot = nullptr, *miss = nullptr, *rank = nullptr;
   hipError_t e = hipSetDevice(slot.device);
   buf.reserve(n * (7 * sizeof(double) + 3 * sizeof(uint64_t) + 4 * sizeof(uint32_t)) + (size_t(16) << 20));
   if (e == hipSuccess) e = buf.alloc(&rec, n * 4);
@@ -169,44 +212,67 @@ int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const doub
   if (h_info[nos::kInfoFarPoint] != 0)
     return fail(NOS_ERR_UNSUPPORTED, "point %u lies outside the addressable grid (+-2^20 cells per axis)",
                 h_info[nos::kInfoFarPoint] - 1u);
-  int rc = store_reserve(vm, size_t(vm->n_voxels) + U);  // load factor <= 1/2 whatever the number of new voxels
-  if (rc != NOS_OK) return rc;
+  // step 3: the build's sums kernel on the batch; step 4 (store_merge_runs): lookup, rank of the misses, merge + finish
   buf.reserve(size_t(U) * (9 * sizeof(double) + 3 * sizeof(uint32_t)) + (size_t(1) << 20));
-  PrimTmp t_rank;
-  const auto rank_misses = [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, miss, rank, 0u, size_t(U), rocprim::plus<uint32_t>(), st); };
   e = buf.alloc(&seg_acc, size_t(U) * 9);
-  if (e == hipSuccess) e = buf.alloc(&run_slot, U);
-  if (e == hipSuccess) e = buf.alloc(&miss, U);
-  if (e == hipSuccess) e = buf.alloc(&rank, U);
-  if (e == hipSuccess) e = prim_plan(buf, rank_misses, t_rank);
   if (e == hipSuccess) e = g.queue_offsets(U);
   if (e != hipSuccess) return hip_fail(e, "voxel store insert (segments)");
-  // step 3: the build's sums kernel on the batch; step 4: lookup, rank of the misses, merge + finish
-  const nos::MapBuildParams prm{5, 0.01, 0.01, (vm->flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0, vm->voxel_resolution};
   e = launch_voxel_sums(rec, g.idx_sorted, g.offsets, g.counts, U, 1.0 / vm->voxel_resolution, vm->voxel_resolution, seg_acc, st);
   if (e != hipSuccess) return hip_fail(e, "voxel store insert (sums)");
-  const dim3 ugrid(unsigned((size_t(U) + 255) / 256));
-  hipLaunchKernelGGL(nos::voxel_lookup_kernel, ugrid, dim3(256), 0, st, vm->view, g.uniq, U, run_slot, miss, vm->d_info);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = prim_run(rank_misses, t_rank);
-  if (e != hipSuccess) return hip_fail(e, "voxel store insert (lookup)");  // still nothing written
-  hipLaunchKernelGGL(nos::voxel_merge_kernel, ugrid, dim3(256), 0, st, vm->view, g.uniq, g.counts, seg_acc, run_slot, rank, U, prm,
-                     uint32_t(vm->epoch + 1), vm->d_info);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(h_info, vm->d_info, 5 * sizeof(unsigned int), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the wait at the end
-  if (e != hipSuccess || h_info[nos::kInfoProbeError] != 0) {
-    vm->broken = true;
-    if (e != hipSuccess) return hip_fail(e, "voxel store insert (merge)");
-    return fail(NOS_ERR_HIP, "voxel store insert failed: a table probe found no free entry");
+  return store_merge_runs(vm, buf, g.uniq, g.counts, seg_acc, U, n, "voxel store insert", n_touched);
+}
+
+// One merge of `src` into `dst` under `pose`: the source's slots become moment records about destination
+// cells, grouped by destination cell and added up per cell; the wait in the middle reads the run count and the flags, and
+// nothing of the destination is written before it.  The source is only read.
+int store_merge(nos_voxel_map* dst, const nos_voxel_map* src, const nos::PosePod& pose, size_t* n_touched) {
+  if (dst->broken || src->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+  const size_t n = src->n_voxels;
+  if (n == 0) {
+    if (n_touched) *n_touched = 0;
+    return NOS_OK;
   }
-  vm->n_voxels += h_info[nos::kInfoNew];
-  vm->view.n_voxels = vm->n_voxels;
-  vm->n_valid = size_t(int(h_info[nos::kInfoValid]));
-  vm->n_points += n;
-  ++vm->epoch;  // what the merge stamped the touched slots with
-  if (n_touched) *n_touched = U;
-  return NOS_OK;
+  DeviceSlot& slot = dst->ctx->slots[0];
+  hipStream_t st = slot.stream;
+  DeviceBuffers buf(&slot);  // arena: every temporary comes from the slot's buffer pool
+  double *mom = nullptr, *seg_acc = nullptr;
+  uint32_t *mom_count = nullptr, *seg_count = nullptr;
+  KeyGroups<uint64_t> g;  // the source's slots grouped by destination cell: a run = the voxels that land in one cell, in slot order
+  hipError_t e = hipSetDevice(slot.device);
+  buf.reserve(n * (18 * sizeof(double) + 3 * sizeof(uint64_t) + 9 * sizeof(uint32_t)) + (size_t(16) << 20));
+  if (e == hipSuccess) e = buf.alloc(&mom, n * 9);
+  if (e == hipSuccess) e = buf.alloc(&mom_count, n);
+  if (e == hipSuccess) e = buf.alloc(&seg_acc, n * 9);
+  if (e == hipSuccess) e = buf.alloc(&seg_count, n);
+  if (e == hipSuccess) e = g.arrays(buf, st, n);
+  if (e == hipSuccess) e = g.temporaries(buf, 63);  // all planning ahead of the first kernel
+  unsigned int h_info[nos::kInfoWords] = {};
+  uint32_t U = 0;
+  const dim3 grid(unsigned((n + 255) / 256));
+  if (e == hipSuccess) e = hipMemsetAsync(dst->d_info, 0, 4 * sizeof(unsigned int), st);  // bad, far, probe error, new
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(nos::voxel_moments_kernel, grid, dim3(256), 0, st, src->view, src->voxel_resolution, pose,
+                       dst->voxel_resolution, 1.0 / dst->voxel_resolution, mom, mom_count, g.keys, g.idx, dst->d_info);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = g.queue(&U);
+  if (e == hipSuccess) e = g.queue_offsets(uint32_t(n));  // over the most runs there can be: their number is still on its way
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(nos::voxel_moment_sums_kernel, grid, dim3(256), 0, st, mom, mom_count, g.idx_sorted, g.offsets,
+                       g.counts, g.n_runs, seg_acc, seg_count, dst->d_info);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h_info, dst->d_info, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the one wait in the middle: run count and flags
+  if (e != hipSuccess) return hip_fail(e, "voxel store merge (sums)");
+  // nothing of the destination has been written so far: a rejected merge leaves it as it was
+  if (h_info[nos::kInfoBadPoint] != 0)
+    return fail(NOS_ERR_INVALID_ARGUMENT, "source voxel %u has non-finite moments under this pose", h_info[nos::kInfoBadPoint] - 1u);
+  if (h_info[nos::kInfoFarPoint] != 0)
+    return fail(NOS_ERR_UNSUPPORTED,
+                "source voxel %u lands outside the addressable grid (+-2^20 cells per axis) or takes its destination voxel past "
+                "2^32 - 1 points", h_info[nos::kInfoFarPoint] - 1u);
+  return store_merge_runs(dst, buf, g.uniq, seg_count, seg_acc, U, src->n_points, "voxel store merge", n_touched);
 }
 
 // One prune: keep flags and totals, scan, ONE wait; when something goes, the survivors move to a fresh
@@ -413,6 +479,38 @@ int nos_voxel_map_insert_scan(nos_voxel_map* vm, nos_scan* scan, const double R[
   if (!vm || !scan || !R || !t) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
   if (vm->ctx != scan->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map and scan belong to different contexts");
   return store_insert(vm, scan->n, nullptr, scan->d_planes, make_pose(R, t), n_touched);
+}
+
+int nos_voxel_map_merge(nos_voxel_map* dst, const nos_voxel_map* src, const double R[9], const double t[3], size_t* n_touched) {
+  if (!dst || !src || !R || !t) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (dst == src) return fail(NOS_ERR_INVALID_ARGUMENT, "a voxel map cannot be merged into itself");
+  nosd::CtxGuard guard_(dst->ctx);  // one solve / accumulate / create at a time per context
+  if (dst->ctx != src->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "the two voxel maps belong to different contexts");
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(R[k])) return fail(NOS_ERR_INVALID_ARGUMENT, "R has a non-finite entry");
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(t[k])) return fail(NOS_ERR_INVALID_ARGUMENT, "t has a non-finite entry");
+  return store_merge(dst, src, make_pose(R, t), n_touched);
+}
+
+// Test hook: the moment transform on the HOST — voxel_moments as the kernel compiles it, no GPU call.
+int nos_debug_voxel_moments(uint32_t count, const double sums[9], const int64_t cell[3], double src_resolution,
+                            const double R[9], const double t[3], double dst_resolution, int64_t cell_out[3],
+                            double sums_out[9]) {
+  if (!sums || !cell || !R || !t || !cell_out || !sums_out) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (count == 0) return fail(NOS_ERR_INVALID_ARGUMENT, "a voxel holds at least one point");
+  if (!(src_resolution > 0.0) || !std::isfinite(src_resolution) || !(dst_resolution > 0.0) || !std::isfinite(dst_resolution))
+    return fail(NOS_ERR_INVALID_ARGUMENT, "bad voxel resolution");
+  double acc[9], Rm[9], tv[3], cf[3], out[9];
+  for (int k = 0; k < 9; ++k) acc[k] = sums[k], Rm[k] = R[k];
+  for (int k = 0; k < 3; ++k) tv[k] = t[k];
+  const int64_t c[3] = {cell[0], cell[1], cell[2]};
+  nos::voxel_moments(count, acc, c, src_resolution, Rm, tv, dst_resolution, 1.0 / dst_resolution, cf, out);
+  for (int k = 0; k < 3; ++k)
+    if (!(cf[k] >= -9.0e18 && cf[k] <= 9.0e18)) return fail(NOS_ERR_UNSUPPORTED, "the destination cell is not representable");
+  for (int k = 0; k < 3; ++k) cell_out[k] = int64_t(cf[k]);
+  for (int k = 0; k < 9; ++k) sums_out[k] = out[k];
+  return NOS_OK;
 }
 
 int nos_voxel_map_info(const nos_voxel_map* vm, size_t* n_voxels, size_t* n_valid, unsigned long long* n_points) {

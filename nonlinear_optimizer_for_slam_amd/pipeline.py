@@ -257,3 +257,27 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
         poses.append(Pose(pose.R, pose.t))
         all_rounds.append(rounds)
     return poses, all_rounds
+
+
+def compose_map(ctx, submaps, poses, voxel_resolution=None, search_radius_sq=None, proper_sqrt_information=True, capacity=0):
+    """The global map from submaps at their current pose estimates — e.g. rebuilt after PoseGraph.optimize has corrected
+    the trajectory, without the raw scans: every api.VoxelMap of `submaps` is merged under its pose (VoxelMap.merge, map
+    point = R p + t), in list order, into a fresh VoxelMap.  poses: one Pose (or (R, t) pair) per submap.  voxel_resolution
+    and search_radius_sq default to the first submap's.  → the new VoxelMap, the caller's to close; on an error it is
+    closed before the exception leaves.  The submaps are not modified."""
+    submaps, poses = list(submaps), list(poses)
+    if len(submaps) != len(poses):
+        raise ValueError("%d submaps but %d poses" % (len(submaps), len(poses)))
+    if not submaps and (voxel_resolution is None or search_radius_sq is None):
+        raise ValueError("without submaps, voxel_resolution and search_radius_sq have to be given")
+    res = submaps[0].voxel_resolution if voxel_resolution is None else voxel_resolution
+    radius = submaps[0].search_radius_sq if search_radius_sq is None else search_radius_sq
+    out = VoxelMap(ctx, res, radius, proper_sqrt_information=proper_sqrt_information, capacity=capacity)
+    try:
+        for sub, pose in zip(submaps, poses):
+            R, t = (pose.R, pose.t) if hasattr(pose, "R") else pose
+            out.merge(sub, R, t)
+    except Exception:
+        out.close()
+        raise
+    return out
