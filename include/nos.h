@@ -783,6 +783,10 @@ int nos_pgo_get_state(nos_pose_graph* pg, double* poses, double* switches);
 int nos_pgo_get_vector(nos_pose_graph* pg, int which, double* out);
 /* y = (J^T J with its diagonal scaled by 1 + lambda) x for host vectors.  Diagnostics. */
 int nos_pgo_matvec(nos_pose_graph* pg, double lambda, const double* x, double* y);
+/* z = M^-1 r for a host vector (tests): the preconditioner nos_pgo_solve would use at this lambda (context options
+ * pgo_precond, pgo_agg, pgo_coarse_probe honoured).  Vector order of nos_pgo_matvec; must follow nos_pgo_linearize.
+ * Switch rows: r_s / (h_s (1 + lambda)) where a switch is free, r_s / (1 + lambda) otherwise.  Diagnostics. */
+int nos_pgo_precondition(nos_pose_graph* pg, double lambda, const double* r, double* z);
 /* What the sweeps have to touch (bench.py's byte models): info[0] poses, [1] constraints, [2] entries of the block-local
  * product (one per constraint and block it touches; 0 = the owner-computes product is in use), [3] poses per block,
  * [4] blocks, [5] halo poses over all blocks, [6] aggregates of the coarse level, [7] PCR levels (6, 7: 0 before the

@@ -35,7 +35,7 @@ C_ABI_SYMBOLS = (
     "nos_voxel_map_create", "nos_voxel_map_insert", "nos_voxel_map_insert_scan", "nos_voxel_map_info", "nos_voxel_map_snapshot",
     "nos_voxel_map_stats", "nos_voxel_map_match", "nos_voxel_map_match_indexed", "nos_voxel_map_prune", "nos_voxel_map_memory", "nos_voxel_map_merge", "nos_voxel_map_destroy", "nos_dataset_drop_last_matches", "nos_pgo_create", "nos_pgo_destroy", "nos_pgo_num_unknowns",
     "nos_pgo_linearize", "nos_pgo_solve", "nos_pgo_retract", "nos_pgo_get_state", "nos_pgo_get_vector",
-    "nos_pgo_matvec", "nos_pgo_time_sweep", "nos_pgo_layout_info", "nos_debug_lm_step", "nos_debug_voxel_finish", "nos_debug_voxel_moments", "nos_dataset_destroy", "nos_dataset_size", "nos_dataset_dtype", "nos_dataset_stream_bytes",
+    "nos_pgo_matvec", "nos_pgo_precondition", "nos_pgo_time_sweep", "nos_pgo_layout_info", "nos_debug_lm_step", "nos_debug_voxel_finish", "nos_debug_voxel_moments", "nos_dataset_destroy", "nos_dataset_size", "nos_dataset_dtype", "nos_dataset_stream_bytes",
     "nos_dataset_set_simd_class",
     "nos_ndt6_accumulate", "nos_ndt3_accumulate", "nos_reproj_accumulate",
     "nos_ndt6_accumulate_async", "nos_ndt3_accumulate_async", "nos_reproj_accumulate_async",
@@ -211,6 +211,8 @@ def _declare(lib):
     lib.nos_pgo_get_state.argtypes = [vp, dp, dp]
     lib.nos_pgo_get_vector.argtypes = [vp, i, dp]
     lib.nos_pgo_matvec.argtypes = [vp, ctypes.c_double, dp, dp]
+    if hasattr(lib, "nos_pgo_precondition"):  # absent from older builds loaded through NOS_HIP_LIB
+        lib.nos_pgo_precondition.argtypes = [vp, ctypes.c_double, dp, dp]
     if hasattr(lib, "nos_pgo_layout_info"):
         lib.nos_pgo_layout_info.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]
     if hasattr(lib, "nos_debug_lm_step"):

@@ -49,6 +49,16 @@ namespace {
 
 constexpr uint32_t kPgoDotBlocks = 1024;
 
+// LDS of the block-local product (pgo_matvec_block_kernel<128, 256>): 14 doubles per own and halo pose, 6 per slot.
+// halo_cap / slot_cap are the capacities the kernel is launched with: the largest halo rounded up to 8, the largest slot
+// count but at least 256 (the tail's sum re-uses the slots: >= 1024 doubles).
+constexpr size_t kPgoLdsCap = size_t(160) * 1024;  // LDS of one CU: no workgroup gets more, whatever the runtime reports
+constexpr uint32_t pgo_halo_cap(uint32_t largest_halo) { return (largest_halo + 7u) & ~7u; }
+constexpr uint32_t pgo_slot_cap(uint32_t largest_slots) { return largest_slots > 256u ? largest_slots : 256u; }
+constexpr size_t pgo_product_lds(uint32_t halo_cap, uint32_t slot_cap) {
+  return ((size_t(128) + halo_cap) * 14 + size_t(slot_cap) * 6) * sizeof(double);
+}
+
 int pgo_read_scalars(nos_pose_graph* pg, int count, double* out) {
   DeviceSlot& slot = pg->ctx->slots[0];
   NOS_HIP_CHECK(hipMemcpyAsync(pg->h_scalars, pg->d_scalars, sizeof(double) * count, hipMemcpyDeviceToHost, slot.stream));
@@ -69,6 +79,10 @@ int pgo_dot(nos_pose_graph* pg, const double* a, const double* b, double* out) {
 
 int pgo_launch_product(nos_pose_graph* pg, double lambda, const double* x, double* y, const double* z = nullptr,
                        double* x_new = nullptr);
+const void* pgo_product_kernel(bool switch_rows) {
+  return switch_rows ? reinterpret_cast<const void*>(nos::pgo_matvec_block_kernel<128, 256, true>)
+                     : reinterpret_cast<const void*>(nos::pgo_matvec_block_kernel<128, 256, false>);
+}
 
 // y = A x on the device and x.y to the host (host-read CG scalars, option pgo_host_scalars): the same product kernel and the
 // same in-launch sum as the device-resident form, the total read back from the scalar block.
@@ -86,7 +100,7 @@ int pgo_launch_product(nos_pose_graph* pg, double lambda, const double* x, doubl
   const int switch_rows = pg->n_free_switches > 0 ? 1 : 0;
   if (pg->block_poses != 0) {
     constexpr int kP = 128, kT = 256;
-    const size_t lds = ((size_t(kP) + pg->bview.halo_cap) * 14 + size_t(pg->bview.slot_cap) * 6) * sizeof(double);
+    const size_t lds = pgo_product_lds(pg->bview.halo_cap, pg->bview.slot_cap);
     auto* kernel = switch_rows ? nos::pgo_matvec_block_kernel<kP, kT, true> : nos::pgo_matvec_block_kernel<kP, kT, false>;
     if (lds > size_t(48) * 1024) {
       const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
@@ -260,6 +274,45 @@ int pgo_coarse_apply(nos_pose_graph* pg, const double* r, const double** xc) {
   return pgo_pcr_rhs(pg, xc);
 }
 
+// The preconditioner of one solve at one lambda: what nos_pgo_solve and nos_pgo_precondition share.
+struct PgoPrecond {
+  uint32_t agg = 0;           // poses per aggregate of the coarse level
+  bool two_level = false;     // coarse correction on top of block-Jacobi
+  uint32_t active_edges = 0;  // switch rows that take part (0: no free switch, the rows stay identically zero)
+  uint32_t pblocks = 0;       // workgroups of pgo_apply_precond_kernel = rows of its partials
+};
+
+// Block-Jacobi inverses and, from a few aggregates on, the coarse operator and its PCR factors.  The probing form of the
+// coarse set-up uses d_p / d_ap as scratch: call before the CG vectors (or a test's r) are put in place.
+int pgo_precond_setup(nos_pose_graph* pg, double lambda, PgoPrecond* pc) {
+  DeviceSlot& slot = pg->ctx->slots[0];
+  pc->active_edges = pg->n_free_switches > 0 ? pg->n_edges : 0;
+  pc->pblocks = (pg->n_poses + pc->active_edges + 255) / 256;
+  hipLaunchKernelGGL(nos::pgo_precond_kernel, dim3((pg->n_poses + 255) / 256), dim3(256), 0, slot.stream, pg->d_hdiag,
+                     lambda, pg->n_poses, pg->d_minv);
+  // two-level preconditioner: rigid-motion coarse space over aggregates of consecutive poses (pgo_coarse_kernels.hpp);
+  // worth its set-up (18 products) from a few aggregates on
+  pc->agg = uint32_t(std::max(2, pg->ctx->settings.pgo_agg));
+  pc->two_level = pg->ctx->settings.pgo_precond != 0 && pg->n_poses >= 4 * pc->agg;
+  if (pc->two_level) return pgo_coarse_setup(pg, lambda, pc->agg);
+  return NOS_OK;
+}
+
+// d_z = M^-1 d_r, with the block partials of r.z and r.r in d_partials (host-read form: no in-launch tail).
+int pgo_precond_apply(nos_pose_graph* pg, double lambda, const PgoPrecond& pc) {
+  DeviceSlot& slot = pg->ctx->slots[0];
+  const size_t N6 = size_t(6) * pg->n_poses;
+  const double* xc = nullptr;
+  if (pc.two_level) {
+    const int rca = pgo_coarse_apply(pg, pg->d_r, &xc);
+    if (rca != NOS_OK) return rca;
+  }
+  hipLaunchKernelGGL(nos::pgo_apply_precond_kernel, dim3(pc.pblocks), dim3(256), 0, slot.stream, pg->d_minv, pg->d_hs, lambda,
+                     pg->n_poses, pc.active_edges, pg->d_r, pg->d_r + N6, pg->d_z, pg->d_z + N6, pg->d_partials, pg->d_pose,
+                     pg->d_fixed, xc, pc.agg);
+  return NOS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -331,8 +384,11 @@ int nos_pgo_create(nos_ctx* ctx, size_t n_poses, const double* poses, size_t n_e
   // each with the adjacency slots (positions relative to the block's first adjacency entry) of its ends inside the block and
   // with its two poses as indices LOCAL to the block: < kBlockPoses = own pose, else kBlockPoses + position in the block's
   // halo list (the other blocks' poses its constraints refer to, ascending).
-  constexpr uint32_t kBlockPoses = 128, kSlotLimit = 2304, kHaloLimit = 512;  // LDS: (128 + 512) x 112 B + 2304 x 48 B = 182 KB
-                                                                               // is the refusal line; a trajectory graph needs ≈ 70 KB
+  // kSlotLimit / kHaloLimit are PACKING limits (16-bit slot and local-index fields of an entry), not the LDS budget: at
+  // both limits the product would ask for (128 + 512) x 112 B + 2304 x 48 B = 182 272 B, more than a CU has (160 KiB).
+  // What a workgroup may have is asked of the device below (pgo_product_lds against the budget); a trajectory graph
+  // needs ≈ 70 KB.
+  constexpr uint32_t kBlockPoses = 128, kSlotLimit = 2304, kHaloLimit = 512;
   const uint32_t n_blocks = (N + kBlockPoses - 1) / kBlockPoses;
   std::vector<uint32_t> bent_off(size_t(n_blocks) + 1, 0), bhalo_off(size_t(n_blocks) + 1, 0);
   struct Piece {  // what one host thread produced for its contiguous range of blocks [first_block, …)
@@ -426,6 +482,16 @@ int nos_pgo_create(nos_ctx* ctx, size_t n_poses, const double* poses, size_t n_e
         bent_off[b + 1] += bent_off[b];
         bhalo_off[b + 1] += bhalo_off[b];
       }
+      // the product keeps a block's poses, halo and slots in LDS: a graph that needs more than a workgroup may have goes
+      // to the owner-computes kernels like one beyond the packing limits
+      int lds_max = 0;
+      if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->slots[0].device) != hipSuccess)
+        lds_max = 64 * 1024;
+      const size_t budget = std::min<size_t>(size_t(std::max(lds_max, 0)), kPgoLdsCap);
+      hipFuncAttributes fa{};  // the kernel's own static LDS (the tail's flag) counts against the same budget
+      const size_t fixed_lds =
+          hipFuncGetAttributes(&fa, pgo_product_kernel(n_free > 0)) == hipSuccess ? fa.sharedSizeBytes : size_t(64);
+      blocks_ok = pgo_product_lds(pgo_halo_cap(halo_cap), pgo_slot_cap(slot_cap)) + fixed_lds <= budget;
     }
   }
   nos_pose_graph* pg = new (std::nothrow) nos_pose_graph();
@@ -515,8 +581,8 @@ int nos_pgo_create(nos_ctx* ctx, size_t n_poses, const double* poses, size_t n_e
   pg->bview.halo = pg->d_bhalo;
   pg->bview.halo_off = pg->d_bhalo_off;
   pg->bview.n_blocks = pg->n_blocks;
-  pg->bview.halo_cap = (halo_cap + 7u) & ~7u;
-  pg->bview.slot_cap = std::max<uint32_t>(slot_cap, 256u);  // the tail's sum re-uses the slots: >= 1024 doubles
+  pg->bview.halo_cap = pgo_halo_cap(halo_cap);
+  pg->bview.slot_cap = pgo_slot_cap(slot_cap);
   *out_pg = pg;
   return NOS_OK;
 }
@@ -559,31 +625,14 @@ int nos_pgo_solve(nos_pose_graph* pg, double lambda, int max_iterations, double 
   NOS_HIP_CHECK(hipSetDevice(slot.device));
   // without free switches the switch rows of every CG vector stay identically zero: leave them out
   const size_t N6 = size_t(6) * pg->n_poses;
-  const uint32_t active_edges = pg->n_free_switches > 0 ? pg->n_edges : 0;
+  PgoPrecond pc;
+  const int rcs = pgo_precond_setup(pg, lambda, &pc);
+  if (rcs != NOS_OK) return rcs;
+  const uint32_t active_edges = pc.active_edges, pblocks = pc.pblocks, agg = pc.agg;
+  const bool two_level = pc.two_level;
   const size_t n = N6 + active_edges;
   const unsigned vblocks = unsigned((n + 255) / 256);
-  const uint32_t pblocks = (pg->n_poses + active_edges + 255) / 256;
-  hipLaunchKernelGGL(nos::pgo_precond_kernel, dim3((pg->n_poses + 255) / 256), dim3(256), 0, slot.stream, pg->d_hdiag,
-                     lambda, pg->n_poses, pg->d_minv);
-  // two-level preconditioner: rigid-motion coarse space over aggregates of consecutive poses (pgo_coarse_kernels.hpp);
-  // worth its set-up (18 products) from a few aggregates on
-  const uint32_t agg = uint32_t(std::max(2, pg->ctx->settings.pgo_agg));
-  const bool two_level = pg->ctx->settings.pgo_precond != 0 && pg->n_poses >= 4 * agg;
-  if (two_level) {
-    const int rcs = pgo_coarse_setup(pg, lambda, agg);
-    if (rcs != NOS_OK) return rcs;
-  }
-  auto apply_precond = [&]() -> int {
-    const double* xc = nullptr;
-    if (two_level) {
-      const int rca = pgo_coarse_apply(pg, pg->d_r, &xc);
-      if (rca != NOS_OK) return rca;
-    }
-    hipLaunchKernelGGL(nos::pgo_apply_precond_kernel, dim3(pblocks), dim3(256), 0, slot.stream, pg->d_minv, pg->d_hs, lambda,
-                       pg->n_poses, active_edges, pg->d_r, pg->d_r + N6, pg->d_z, pg->d_z + N6, pg->d_partials, pg->d_pose,
-                       pg->d_fixed, xc, agg);
-    return NOS_OK;
-  };
+  auto apply_precond = [&]() -> int { return pgo_precond_apply(pg, lambda, pc); };
   // x = 0, r = -g
   NOS_HIP_CHECK(hipMemsetAsync(pg->d_x, 0, n * sizeof(double), slot.stream));
   NOS_HIP_CHECK(hipMemsetAsync(pg->d_r, 0, n * sizeof(double), slot.stream));
@@ -818,6 +867,33 @@ int nos_pgo_matvec(nos_pose_graph* pg, double lambda, const double* x, double* y
   for (size_t i = 0; i < N; ++i)
     for (int k = 0; k < 6; ++k) y[size_t(k) * N + i] = rec[6 * i + k];
   for (size_t e = 0; e < pg->n_edges; ++e) y[6 * N + e] = (pg->n_free_switches > 0) ? rec[6 * N + e] : (1.0 + lambda) * x[6 * N + e];
+  return NOS_OK;
+}
+
+// z = M^-1 r for a host vector (tests): the preconditioner nos_pgo_solve would use at this lambda.
+int nos_pgo_precondition(nos_pose_graph* pg, double lambda, const double* r, double* z) {
+  nosd::CtxGuard guard_(pg ? pg->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!pg || !r || !z) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  DeviceSlot& slot = pg->ctx->slots[0];
+  NOS_HIP_CHECK(hipSetDevice(slot.device));
+  PgoPrecond pc;
+  int rc = pgo_precond_setup(pg, lambda, &pc);  // before r goes up: the probing form uses d_p / d_ap as scratch
+  if (rc != NOS_OK) return rc;
+  const size_t N = pg->n_poses, n = pg->n_unknowns;
+  std::vector<double> rec(n);
+  for (size_t i = 0; i < N; ++i)
+    for (int k = 0; k < 6; ++k) rec[6 * i + k] = r[size_t(k) * N + i];
+  for (size_t e = 0; e < pg->n_edges; ++e) rec[6 * N + e] = r[6 * N + e];
+  NOS_HIP_CHECK(hipMemcpyAsync(pg->d_r, rec.data(), n * sizeof(double), hipMemcpyHostToDevice, slot.stream));
+  rc = pgo_precond_apply(pg, lambda, pc);
+  if (rc != NOS_OK) return rc;
+  NOS_HIP_CHECK(hipGetLastError());
+  NOS_HIP_CHECK(hipMemcpyAsync(rec.data(), pg->d_z, n * sizeof(double), hipMemcpyDeviceToHost, slot.stream));
+  NOS_HIP_CHECK(hipStreamSynchronize(slot.stream));
+  for (size_t i = 0; i < N; ++i)
+    for (int k = 0; k < 6; ++k) z[size_t(k) * N + i] = rec[6 * i + k];
+  for (size_t e = 0; e < pg->n_edges; ++e)
+    z[6 * N + e] = pc.active_edges > 0 ? rec[6 * N + e] : r[6 * N + e] / (1.0 + lambda);
   return NOS_OK;
 }
 

@@ -61,59 +61,43 @@ __device__ __forceinline__ void m6_mulvec_add(const double (&A)[36], const doubl
     y[r] = v;
   }
 }
-// Inverse of a symmetric positive definite 6x6 (Cholesky; pivots floored so that an empty aggregate cannot poison the
-// recurrence).  Only the upper triangle of A is read.
+// Inverse of a symmetric positive definite 6x6: Gauss-Jordan elimination in place, no pivoting (none is needed for an SPD
+// block), pivots floored so that an empty aggregate cannot poison the recurrence; the result is made exactly symmetric.
+// Only the upper triangle of A is read.  Not L^-T L^-1 from a Cholesky factor: the blocks of the upper reduction levels
+// are Schur complements of long stretches of the chain and badly conditioned, and the product of the two triangular
+// inverses lost 50 times the accuracy of an elimination there (4 200-pose chain held at one end, lambda = 0: the
+// preconditioner 2.2e-8 from the exact answer against 4.6e-10 with this form; tests/test_pgo_preconditioner.py).
 __device__ __forceinline__ void m6_spd_inverse(const double (&A)[36], double (&Ai)[36]) {
-  double L[6][6], Li[6][6];
 #pragma unroll
   for (int r = 0; r < 6; ++r)
 #pragma unroll
-    for (int c = 0; c < 6; ++c) {
-      L[r][c] = 0.0;
-      Li[r][c] = 0.0;
-    }
+    for (int c = 0; c < 6; ++c) Ai[6 * r + c] = r <= c ? A[6 * r + c] : A[6 * c + r];
 #pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double d = A[6 * j + j];
-#pragma unroll
-    for (int m = 0; m < 6; ++m)
-      if (m < j) d -= L[j][m] * L[j][m];
+  for (int k = 0; k < 6; ++k) {
+    double d = Ai[7 * k];
     d = d > 1e-300 ? d : 1e-300;
-    const double lj = sqrt(d);
-    L[j][j] = lj;
+    const double p = 1.0 / d;
+    Ai[7 * k] = 1.0;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) Ai[6 * k + c] *= p;
 #pragma unroll
     for (int r = 0; r < 6; ++r)
-      if (r > j) {
-        double v = A[6 * j + r];  // upper triangle: A(j, r) = A(r, j)
+      if (r != k) {
+        const double f = Ai[6 * r + k];
+        Ai[6 * r + k] = 0.0;
 #pragma unroll
-        for (int m = 0; m < 6; ++m)
-          if (m < j) v -= L[r][m] * L[j][m];
-        L[r][j] = v / lj;
-      }
-  }
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    Li[c][c] = 1.0 / L[c][c];
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-      if (r > c) {
-        double v = 0.0;
-#pragma unroll
-        for (int m = 0; m < 6; ++m)
-          if (m >= c && m < r) v -= L[r][m] * Li[m][c];
-        Li[r][c] = v / L[r][r];
+        for (int c = 0; c < 6; ++c) Ai[6 * r + c] = fma(-f, Ai[6 * k + c], Ai[6 * r + c]);
       }
   }
 #pragma unroll
   for (int r = 0; r < 6; ++r)
 #pragma unroll
-    for (int c = 0; c < 6; ++c) {
-      double v = 0.0;
-#pragma unroll
-      for (int m = 0; m < 6; ++m)
-        if (m >= r && m >= c) v += Li[m][r] * Li[m][c];
-      Ai[6 * r + c] = v;
-    }
+    for (int c = 0; c < 6; ++c)
+      if (c > r) {
+        const double v = 0.5 * (Ai[6 * r + c] + Ai[6 * c + r]);
+        Ai[6 * r + c] = v;
+        Ai[6 * c + r] = v;
+      }
 }
 
 // B_i of the header comment for pose i of aggregate I (c = position of the aggregate's first pose).

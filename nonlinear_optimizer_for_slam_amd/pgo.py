@@ -74,6 +74,14 @@ class PoseGraph:
         check(self._lib.nos_pgo_matvec(self._h, ctypes.c_double(lam), _dp(x), _dp(y)), "nos_pgo_matvec")
         return y
 
+    def precondition(self, lam, r):
+        """z = M^-1 r (nos_pgo_precondition): the preconditioner solve() would use at this lambda, for a host vector in the
+        order of matvec().  Follows linearize(); honours the context options pgo_precond, pgo_agg and pgo_coarse_probe."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        z = np.zeros_like(r)
+        check(self._lib.nos_pgo_precondition(self._h, ctypes.c_double(lam), _dp(r), _dp(z)), "nos_pgo_precondition")
+        return z
+
     def layout_info(self):
         """What the sweeps touch (nos_pgo_layout_info): poses, constraints, entries / block size / blocks / halo poses of
         the block-local product (0 when the owner-computes product runs), aggregates and PCR levels of the coarse level."""

@@ -288,3 +288,189 @@ def random_graph(n, extra_edges_per_pose=3, seed=0, noise_t=0.05, noise_r=0.02, 
     fixed = np.zeros(n, dtype=np.uint8)
     fixed[0] = 1
     return {"true": true, "init": init, "ref": ref, "qry": qry, "meas": meas, "fixed": fixed}
+
+
+def with_edges(d, pairs, seed=1, meas_noise_t=0.01, meas_noise_r=0.005):
+    """The graph dict `d` (random_graph) with the constraints `pairs` = [(ref, qry), ...] appended: measurements are the
+    consistent relative poses of d["true"] plus seeded noise, as in random_graph.  → new dict."""
+    rng = np.random.default_rng(seed)
+    true = d["true"]
+    meas = np.zeros((len(pairs), 7))
+    for e, (a, b) in enumerate(pairs):
+        t = qrot(true[a, 3:]).T @ (true[b, :3] - true[a, :3]) + rng.normal(scale=meas_noise_t, size=3)
+        qm = qmul(qmul(qconj(true[a, 3:]), true[b, 3:]), qexp(rng.normal(scale=meas_noise_r, size=3)))
+        meas[e, :3] = t
+        meas[e, 3:] = qm / np.linalg.norm(qm)
+    out = dict(d)
+    out["ref"] = np.concatenate([d["ref"], np.array([a for a, _ in pairs], dtype=np.int32)]).astype(np.int32)
+    out["qry"] = np.concatenate([d["qry"], np.array([b for _, b in pairs], dtype=np.int32)]).astype(np.int32)
+    out["meas"] = np.concatenate([d["meas"], meas]) if len(pairs) else d["meas"].copy()
+    out["fixed"] = d["fixed"].copy()
+    return out
+
+
+# ---------------------------------------------------------------- the two-level preconditioner, explicitly
+#
+# M^-1 r = blockdiag(H_ii damped)^-1 r + P A_c^-1 P^T r,  A_c = P^T H' P  (csrc/pgo_coarse_kernels.hpp states the
+# operator; this is a restatement from that statement with explicit sparse matrices and a direct solve).
+
+def pcr_spans(n_agg, span_levels=4, threads=128):
+    """How the library cuts the ceil(log2 n_agg) levels of the cyclic reduction into launches:
+    → [(first level, one past the last level, halo)], halo = 0 for the final in-workgroup span.  A span with a halo
+    gives every workgroup `threads - 2 halo` rows of one residue class (the chunk length)."""
+    levels = 0
+    while (1 << levels) < n_agg:
+        levels += 1
+    spans, l = [], 0
+    while True:
+        rows = (n_agg + (1 << l) - 1) >> l
+        if rows <= threads:
+            spans.append((l, levels, 0))
+            return spans
+        k = min(span_levels, levels - l)
+        spans.append((l, l + k, (1 << k) - 1))
+        l += k
+
+
+def tridiagonal_blocks(A_c):
+    """Block-tridiagonal sparse A_c [6C, 6C] → (L, D, U) as [C, 6, 6] arrays: A_c(J, J-1), A_c(J, J), A_c(J, J+1)."""
+    C = A_c.shape[0] // 6
+    B = sp.bsr_matrix(A_c, blocksize=(6, 6))
+    B.sort_indices()
+    L, D, U = (np.zeros((C, 6, 6)) for _ in range(3))
+    rows = np.repeat(np.arange(C), np.diff(B.indptr))
+    off = B.indices - rows
+    if np.any(np.abs(off) > 1):
+        raise ValueError("A_c is not block tridiagonal")
+    L[rows[off == -1]] = B.data[off == -1]
+    D[rows[off == 0]] = B.data[off == 0]
+    U[rows[off == 1]] = B.data[off == 1]
+    return L, D, U
+
+
+def pcr_factors(A_c):
+    """The elimination factors of parallel cyclic reduction on block-tridiagonal A_c, level by level in float64:
+        alpha = -L_J D_{J-d}^-1,  gamma = -U_J D_{J+d}^-1,  d = 2^level,
+        L'_J = alpha L_{J-d},  D'_J = D_J + alpha U_{J-d} + gamma L_{J+d},  U'_J = gamma U_{J+d}
+    → ([(alpha, gamma) per level], inverse of the decoupled diagonal blocks), all [C, 6, 6]."""
+    L, D, U = tridiagonal_blocks(A_c)
+    C = D.shape[0]
+    levels, d = [], 1
+    while d < C:
+        Dinv = np.linalg.inv(D)
+        alpha, gamma = np.zeros_like(D), np.zeros_like(D)
+        alpha[d:] = -L[d:] @ Dinv[:-d]
+        gamma[:-d] = -U[:-d] @ Dinv[d:]
+        Ln, Dn, Un = np.zeros_like(D), D.copy(), np.zeros_like(D)
+        Ln[d:] = alpha[d:] @ L[:-d]
+        Dn[d:] += alpha[d:] @ U[:-d]
+        Dn[:-d] += gamma[:-d] @ L[d:]
+        Un[:-d] = gamma[:-d] @ U[d:]
+        levels.append((alpha, gamma))
+        L, D, U = Ln, Dn, Un
+        d *= 2
+    return levels, np.linalg.inv(D)
+
+
+def pcr_twin(A_c, b, skip=None, factors=None):
+    """x = A_c^-1 b by parallel cyclic reduction: per level b'_J = b_J + alpha b_{J-d} + gamma b_{J+d} with the factors
+    of pcr_factors (computed here unless given), then the block solves x_J = D_J^-1 b_J.
+    skip = (level, row, side): the neighbour term of that row at that level (side 0: J - d, 1: J + d) is left out of the
+    right-hand side — what a lost halo row or a dropped term in the library would do."""
+    levels, Dinv = pcr_factors(A_c) if factors is None else factors
+    x = np.array(b, dtype=np.float64).reshape(-1, 6).copy()
+    for level, (alpha, gamma) in enumerate(levels):
+        d = 1 << level
+        left, right = np.zeros_like(x), np.zeros_like(x)
+        left[d:] = np.einsum("jab,jb->ja", alpha[d:], x[:-d])
+        right[:-d] = np.einsum("jab,jb->ja", gamma[:-d], x[d:])
+        if skip is not None and skip[0] == level:
+            (left if skip[2] == 0 else right)[skip[1]] = 0.0
+        x = x + left + right
+    return np.einsum("jab,jb->ja", Dinv, x).reshape(-1)
+
+
+class TwoLevel:
+    """See two_level()."""
+
+    def __init__(self, graph, H, lam, agg):
+        n, m = graph.n, graph.m
+        self.n, self.m, self.lam, self.agg = n, m, lam, agg
+        C = self.n_agg = (n + agg - 1) // agg
+        # pose-major order inside: unknown 6 i + k  <->  plane order k n + i
+        self.perm = (np.arange(6)[None, :] * n + np.arange(n)[:, None]).reshape(-1)
+        Hpp = sp.csr_matrix(H)[:6 * n][:, :6 * n][self.perm][:, self.perm]
+        Hd = (Hpp + lam * sp.diags(Hpp.diagonal())).tocsr()
+        B = sp.bsr_matrix(Hd, blocksize=(6, 6))
+        B.sort_indices()
+        rows = np.repeat(np.arange(n), np.diff(B.indptr))
+        on_diag = B.indices == rows
+        blocks = np.zeros((n, 6, 6))
+        blocks[rows[on_diag]] = B.data[on_diag]
+        fixed = np.asarray(graph.fixed, dtype=bool)
+        blocks[fixed] = np.eye(6)
+        self.bj = np.linalg.inv(blocks)
+        # H': couplings of constraints whose ends lie more than one aggregate apart removed (their diagonal blocks stay)
+        keep = np.abs(rows // agg - B.indices // agg) <= 1
+        kept_rows, kept_cols = rows[keep], B.indices[keep]
+        indptr = np.concatenate([[0], np.cumsum(np.bincount(kept_rows, minlength=n))])
+        self.Hprime = sp.bsr_matrix((B.data[keep], kept_cols, indptr), shape=(6 * n, 6 * n)).tocsr()
+        # P: B_i = [I, -[p_i - c_I]x; 0, R_i^T], zero for fixed poses, c_I the position of the aggregate's first pose
+        pr, pc, pv = [], [], []
+        for i in range(n):
+            if fixed[i]:
+                continue
+            I = i // agg
+            Bi = np.zeros((6, 6))
+            Bi[:3, :3] = np.eye(3)
+            Bi[:3, 3:] = -hat(graph.poses[i, :3] - graph.poses[I * agg, :3])
+            Bi[3:, 3:] = qrot(graph.poses[i, 3:]).T
+            rr, cc = np.nonzero(Bi)
+            pr.append(6 * i + rr)
+            pc.append(6 * I + cc)
+            pv.append(Bi[rr, cc])
+        cat = (lambda a: np.concatenate(a)) if pr else (lambda a: np.zeros(0))
+        self.P = sp.coo_matrix((cat(pv), (cat(pr).astype(np.int64), cat(pc).astype(np.int64))), shape=(6 * n, 6 * C)).tocsr()
+        A = (self.P.T @ self.Hprime @ self.P).tocsr()
+        empty = np.ones(C, dtype=bool)
+        empty[np.arange(n)[~fixed] // agg] = False
+        self.A_c = (A + sp.diags(np.repeat(empty.astype(np.float64), 6))).tocsc()
+        self._lu = spla.splu(self.A_c)
+        hs = sp.csr_matrix(H).diagonal()[6 * n:]
+        self.switch_scale = 1.0 / (hs * (1.0 + lam)) if m else np.zeros(0)
+
+    def _split(self, r):
+        r = np.asarray(r, dtype=np.float64)
+        return r[:6 * self.n][self.perm], r[6 * self.n:]
+
+    def _join(self, zp, rs):
+        z = np.zeros(6 * self.n + self.m)
+        z[self.perm] = zp
+        z[6 * self.n:] = rs * self.switch_scale
+        return z
+
+    def restrict(self, r):
+        return self.P.T @ self._split(r)[0]
+
+    def apply_block_jacobi(self, r):
+        rp, rs = self._split(r)
+        return self._join(np.einsum("iab,ib->ia", self.bj, rp.reshape(-1, 6)).reshape(-1), rs)
+
+    def apply(self, r, coarse_solve=None):
+        """M^-1 r; coarse_solve(A_c, b) replaces the sparse LU solve of the coarse system (pcr_twin)."""
+        rp, rs = self._split(r)
+        b = self.P.T @ rp
+        xc = self._lu.solve(b) if coarse_solve is None else coarse_solve(self.A_c, b)
+        zp = np.einsum("iab,ib->ia", self.bj, rp.reshape(-1, 6)).reshape(-1) + self.P @ xc
+        return self._join(zp, rs)
+
+
+def two_level(graph, H, lam, agg):
+    """The two-level preconditioner of the pose-graph PCG from the explicit H of graph.linearize():
+      * block-Jacobi: inverse of each pose's 6x6 diagonal block with its diagonal scaled by 1 + lam (fixed: identity);
+      * P: B_i = [I, -[p_i - c_I]x; 0, R_i^T] per free pose of aggregate I = i // agg;
+      * H' = pose-pose part of H + lam diag(H) without the couplings that span more than neighbouring aggregates;
+      * A_c = P^T H' P, identity block for an aggregate without a free pose;
+      * apply(r) = M_bj^-1 r + P splu(A_c).solve(P^T r);  switch rows r_s / (h_s (1 + lam)).
+    Vectors are in the order of Graph.linearize()."""
+    return TwoLevel(graph, H, lam, agg)

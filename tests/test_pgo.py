@@ -350,3 +350,82 @@ def test_coarse_operator_assembled_directly_equals_the_probed_one(ctx):
         it_bj, _, _ = g.solve(1e-3, 4000, 1e-11)
     assert res[0][0] < it_bj                                        # and it is still a preconditioner worth having
     g.close()
+
+
+# ------------------------------------------------------------------------------------------ small solver edges
+
+@pytest.mark.gpu
+def test_zero_gradient_gives_a_zero_step_and_an_untouched_graph(ctx):
+    """Exactly consistent measurements at noiseless poses (identity rotations, positions and offsets that are exact in
+    binary, so every residual is 0.0 and not merely tiny): the right-hand side of the solve is zero.  solve returns at once
+    with (0, 0.0, 0.0), the step is all zeros, nothing is NaN and the retraction leaves every pose bit for bit."""
+    from nonlinear_optimizer_for_slam_amd import pgo
+    n = 300
+    poses = np.zeros((n, 7))
+    poses[:, 0] = 0.5 * np.arange(n)
+    poses[:, 1] = 0.25 * (np.arange(n) % 7)
+    poses[:, 2] = -0.125 * (np.arange(n) % 3)
+    poses[:, 3] = 1.0
+    pairs = [(i, i + 1) for i in range(n - 1)] + [(i, i + 3) for i in range(0, n - 3, 2)]
+    ref = np.array([a for a, _ in pairs], dtype=np.int32)
+    qry = np.array([b for _, b in pairs], dtype=np.int32)
+    meas = np.zeros((len(pairs), 7))
+    meas[:, :3] = poses[qry, :3] - poses[ref, :3]
+    meas[:, 3] = 1.0
+    fixed = np.zeros(n, dtype=np.uint8)
+    fixed[0] = 1
+    g = pgo.PoseGraph(ctx, poses, ref, qry, meas, None, None, fixed)
+    cost, gnorm = g.linearize()
+    assert cost == 0.0 and gnorm == 0.0
+    assert not np.any(g.vector("gradient"))
+    assert g.solve(1e-3, 100, 1e-10) == (0, 0.0, 0.0)
+    step = g.vector("step")
+    assert step.shape == (6 * n + len(pairs),) and not np.any(step)      # all zeros: none of them NaN either
+    g.retract()
+    after, sw = g.state()
+    assert np.array_equal(after, poses) and np.all(sw == 1.0)
+    g.close()
+
+
+@pytest.mark.gpu
+def test_iteration_caps_that_are_no_multiple_of_the_check_interval(ctx):
+    """The device-resident PCG runs in batches of min(8, remaining): caps of 5 and 13 give exactly 5 and 13 iterations, and
+    the step after 13 is the one the per-iteration (host scalar) form has after 13."""
+    d = op.random_graph(400, 3, seed=9)
+    cpu, gpu = _graph_pair(ctx, d)
+    gpu.linearize()
+    it5, _, _ = gpu.solve(1e-4, 5, 0.0)
+    x5 = gpu.vector("step").copy()
+    it13, _, _ = gpu.solve(1e-4, 13, 0.0)
+    x13 = gpu.vector("step").copy()
+    with ctx.options(pgo_host_scalars=1):
+        it13_host, _, _ = gpu.solve(1e-4, 13, 0.0)
+        x13_host = gpu.vector("step").copy()
+        it5_host, _, _ = gpu.solve(1e-4, 5, 0.0)
+        x5_host = gpu.vector("step").copy()
+    gpu.close()
+    assert (it5, it13, it5_host, it13_host) == (5, 13, 5, 13)
+    np.testing.assert_allclose(x13, x13_host, rtol=0, atol=1e-12 * np.max(np.abs(x13_host)))
+    np.testing.assert_allclose(x5, x5_host, rtol=0, atol=1e-12 * np.max(np.abs(x5_host)))
+    assert np.max(np.abs(x13 - x5)) > 1e-6 * np.max(np.abs(x13))          # and the 8 further iterations did something
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [7, 200])
+def test_graph_without_constraints(ctx, n):
+    """n_edges = 0 (200 poses: enough for the coarse level to be set up on it): cost 0, zero step, owner-computes form."""
+    from nonlinear_optimizer_for_slam_amd import pgo
+    d = op.random_graph(n, 0, seed=3)
+    none = np.zeros(0, dtype=np.int32)
+    g = pgo.PoseGraph(ctx, d["init"], none, none, np.zeros((0, 7)), None, None, d["fixed"])
+    assert g.layout_info()["block_poses"] == 0 and g.n_unknowns == 6 * n
+    cost, gnorm = g.linearize()
+    assert cost == 0.0 and gnorm == 0.0
+    assert g.solve(1e-3, 50, 1e-10) == (0, 0.0, 0.0)
+    step = g.vector("step")
+    assert step.shape == (6 * n,) and not np.any(step)
+    g.retract()
+    after = g.state()[0]
+    assert np.array_equal(after[:, :3], d["init"][:, :3])
+    np.testing.assert_allclose(after[:, 3:], d["init"][:, 3:], rtol=0, atol=4e-16)   # renormalised: an ulp at the most
+    g.close()
