@@ -498,6 +498,27 @@ int nos_voxel_map_memory(const nos_voxel_map* map, size_t* capacity, size_t* byt
  *   NOS_ERR_UNSUPPORTED       a destination cell outside +-2^20 per axis, or source voxels landing in one cell with more
  *                             than 2^32 - 1 points together: the message names the source voxel id, dst is bit for bit as before. */
 int nos_voxel_map_merge(nos_voxel_map* dst, const nos_voxel_map* src, const double R[9], const double t[3], size_t* n_touched);
+/* One store matched against another: distribution-to-distribution NDT (Stoyanov et al. 2012).  Every valid
+ * voxel of `source` is warped by q = R mean_s + t (the matcher's warp) and matched to its (up to) max_neighbors nearest
+ * valid voxel means of `target` — the search of nos_voxel_map_match for the point mean_s: same radius test, guard band
+ * with its caveat, tie-break by slot and limit of 9 cells per axis, all of them the TARGET's.  Each match becomes one
+ * ordinary flat NDT correspondence: p = mean_s (source frame), mu = mean_j, and a sqrt-information S with
+ *   S^T S = A = (Sigma_j + R Sigma_s R^T)^-1,   Sigma_x = (S_x^T S_x)^-1 of the store's sqrt_information S_x
+ * (so the eigenvalue floor of the voxel finish is in it, and NOS_MAP_PROPER_SQRT_INFORMATION does not matter).  A is
+ * evaluated at the pose of the call and is a constant of the dataset: a solve holds it fixed as it holds the
+ * correspondences fixed; the next match re-evaluates both.  S is the inverse of the Cholesky factor of the combined
+ * covariance (lower triangular).  R is not checked for orthonormality.
+ * The dataset has 2 * n_voxels(source) slots: source voxel v owns slots 2v (nearest) and 2v + 1 (second nearest).  All-zero
+ * records, not counted in *n_matches: an invalid source voxel, a missing neighbour, slot 2v + 1 when max_neighbors = 1, a
+ * pair whose combined covariance is not finite or not positive definite.  Every accumulate and solve entry point takes it.
+ * Both stores are read only (target == source is allowed) and may differ in resolution, radius and flags; one kernel plus
+ * the dataset's padding, one wait; the work follows the source's voxels.  An empty source gives an empty dataset.
+ * Rejected before anything runs, *out_ds unwritten: NOS_ERR_INVALID_ARGUMENT for a NULL argument (n_matches may be NULL),
+ * stores of different contexts, an unknown dtype; NOS_ERR_UNSUPPORTED for max_neighbors outside 1-2, a multi-device
+ * context, a search ball of the target that spans more than 9 cells per axis; NOS_ERR_HIP for a store (either) an earlier
+ * failure left undefined. */
+int nos_voxel_map_match_map(nos_voxel_map* target, nos_voxel_map* source, const double R[9], const double t[3],
+                            int max_neighbors, int dtype, nos_dataset** out_ds, size_t* n_matches);
 int nos_voxel_map_destroy(nos_voxel_map* map);
 
 /* ---- the hot path -------------------------------------------------------------
@@ -750,6 +771,13 @@ int nos_debug_voxel_finish(uint32_t count, const double sums[9], const int64_t c
 int nos_debug_voxel_moments(uint32_t count, const double sums[9], const int64_t cell[3], double src_resolution,
                             const double R[9], const double t[3], double dst_resolution,
                             int64_t cell_out[3], double sums_out[9]);
+
+/* Test hook: the combined information of nos_voxel_map_match_map computed ON THE HOST by the function its kernel calls (no
+ * GPU call, no context).  S_target, S_source: row-major sqrt-informations; R row-major.  S_out: lower triangular with
+ * S_out^T S_out = ((S_target^T S_target)^-1 + R (S_source^T S_source)^-1 R^T)^-1 and *ok = 1, or all zero and *ok = 0 when
+ * an input is not finite or singular or the combined covariance is not finite or not positive definite (NOS_OK either way). */
+int nos_debug_voxel_pair_information(const double S_target[9], const double S_source[9], const double R[9],
+                                     double S_out[9], unsigned char* ok);
 
 /* ---- pose-graph optimisation (BASELINE.json configs[4]) --------
  * The reference's PoseGraphOptimizerAnalytic::Solve is an empty loop

@@ -33,9 +33,9 @@ C_ABI_SYMBOLS = (
     "nos_scan_destroy", "nos_scan_size", "nos_scan_sort_by_cell", "nos_scan_order", "nos_scan_filter", "nos_scan_points", "nos_ndt_match", "nos_ndt_indexed_dataset_create", "nos_ndt_match_indexed", "nos_indexed_dataset_info", "nos_indexed_dataset_download", "nos_ndt_map_build", "nos_map_stats_size",
     "nos_map_stats_get", "nos_map_stats_get_eigen", "nos_map_stats_destroy",
     "nos_voxel_map_create", "nos_voxel_map_insert", "nos_voxel_map_insert_scan", "nos_voxel_map_info", "nos_voxel_map_snapshot",
-    "nos_voxel_map_stats", "nos_voxel_map_match", "nos_voxel_map_match_indexed", "nos_voxel_map_prune", "nos_voxel_map_memory", "nos_voxel_map_merge", "nos_voxel_map_destroy", "nos_dataset_drop_last_matches", "nos_pgo_create", "nos_pgo_destroy", "nos_pgo_num_unknowns",
+    "nos_voxel_map_stats", "nos_voxel_map_match", "nos_voxel_map_match_indexed", "nos_voxel_map_prune", "nos_voxel_map_memory", "nos_voxel_map_merge", "nos_voxel_map_match_map", "nos_voxel_map_destroy", "nos_dataset_drop_last_matches", "nos_pgo_create", "nos_pgo_destroy", "nos_pgo_num_unknowns",
     "nos_pgo_linearize", "nos_pgo_solve", "nos_pgo_retract", "nos_pgo_get_state", "nos_pgo_get_vector",
-    "nos_pgo_matvec", "nos_pgo_precondition", "nos_pgo_time_sweep", "nos_pgo_layout_info", "nos_debug_lm_step", "nos_debug_voxel_finish", "nos_debug_voxel_moments", "nos_dataset_destroy", "nos_dataset_size", "nos_dataset_dtype", "nos_dataset_stream_bytes",
+    "nos_pgo_matvec", "nos_pgo_precondition", "nos_pgo_time_sweep", "nos_pgo_layout_info", "nos_debug_lm_step", "nos_debug_voxel_finish", "nos_debug_voxel_moments", "nos_debug_voxel_pair_information", "nos_dataset_destroy", "nos_dataset_size", "nos_dataset_dtype", "nos_dataset_stream_bytes",
     "nos_dataset_set_simd_class",
     "nos_ndt6_accumulate", "nos_ndt3_accumulate", "nos_reproj_accumulate",
     "nos_ndt6_accumulate_async", "nos_ndt3_accumulate_async", "nos_reproj_accumulate_async",
@@ -192,6 +192,8 @@ def _declare(lib):
             lib.nos_voxel_map_memory.argtypes = [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ull_p, ull_p]
         if hasattr(lib, "nos_voxel_map_merge"):  # one store merged into another under a pose: absent from builds older still
             lib.nos_voxel_map_merge.argtypes = [vp, vp, dp, dp, ctypes.POINTER(sz)]
+        if hasattr(lib, "nos_voxel_map_match_map"):  # one store matched against another: absent from builds older still
+            lib.nos_voxel_map_match_map.argtypes = [vp, vp, dp, dp, i, i, c_void_pp, ctypes.POINTER(sz)]
         if hasattr(lib, "nos_voxel_map_match"):  # matching against the live store: absent from builds older still
             lib.nos_voxel_map_match.argtypes = [vp, vp, dp, dp, i, i, c_void_pp, ctypes.POINTER(sz)]
         if hasattr(lib, "nos_voxel_map_match_indexed"):  # the voxel-indexed form of it: absent from builds older still
@@ -223,6 +225,8 @@ def _declare(lib):
     if hasattr(lib, "nos_debug_voxel_moments"):  # absent from older builds loaded through NOS_HIP_LIB
         i64p = ctypes.POINTER(ctypes.c_int64)
         lib.nos_debug_voxel_moments.argtypes = [ctypes.c_uint32, dp, i64p, ctypes.c_double, dp, dp, ctypes.c_double, i64p, dp]
+    if hasattr(lib, "nos_debug_voxel_pair_information"):  # absent from older builds loaded through NOS_HIP_LIB
+        lib.nos_debug_voxel_pair_information.argtypes = [dp, dp, dp, dp, ctypes.POINTER(ctypes.c_ubyte)]
     if hasattr(lib, "nos_pgo_time_sweep"):  # absent from older builds loaded through NOS_HIP_LIB
         lib.nos_pgo_time_sweep.argtypes = [vp, i, ctypes.c_double, i, dp]
     lib.nos_dataset_destroy.argtypes = [vp]

@@ -896,6 +896,22 @@ class VoxelMap:
               "nos_voxel_map_match_indexed")
         return NdtIndexedDataset(self._ctx, h), int(n.value)
 
+    def match_map(self, source, R, t, max_neighbors=2, dtype="f64"):
+        """Another VoxelMap matched against this one, voxel against voxel (distribution-to-distribution NDT,
+        nos_voxel_map_match_map) → (NdtDataset with 2 slots per voxel of `source`, number of real matches).  Every valid
+        voxel mean of `source` is warped by R p + t and searched on this store exactly as match() searches a point; a
+        match is an ordinary record p = source mean, mu = this store's mean, and a sqrt-information S with
+        SᵀS = (Σ_this + R Σ_source Rᵀ)⁻¹, evaluated at this pose and fixed in the dataset.  Slots 2v and 2v + 1 belong to
+        source voxel v; an invalid voxel and a missing neighbour are all-zero records.  Neither store is modified;
+        source may be this store, and may differ in resolution, search radius and flags."""
+        R = _dvec(R, 9)
+        t = _dvec(t, 3)
+        h = ctypes.c_void_p()
+        n = ctypes.c_size_t()
+        check(self._lib.nos_voxel_map_match_map(self._h, source._h, _dp(R), _dp(t), max_neighbors, _DTYPES[dtype],
+                                                ctypes.byref(h), ctypes.byref(n)), "nos_voxel_map_match_map")
+        return NdtDataset(self._ctx, h), int(n.value)
+
     def score(self, scan, R, t, loss, max_neighbors=2):
         """score_batch for one pose → (matches, matched_points, cost)."""
         row = score_batch(self, [scan], _dvec(R, 9), _dvec(t, 3), loss, max_neighbors)[0]

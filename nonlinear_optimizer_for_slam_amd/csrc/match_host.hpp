@@ -1,6 +1,8 @@
 // match_host.hpp — host side of a match, shared by nos_ndt_match (nos_match.hip), nos_ndt_match_indexed (nos_indexed.hip),
-// nos_voxel_map_match and nos_voxel_map_match_indexed (nos_voxelmap.hip); DESIGN.md §18.  The routes differ in their
-// SOURCE only, as the two batched registrations differ in their Launcher (register_host.hpp).  A source has view,
+// nos_voxel_map_match, nos_voxel_map_match_indexed and nos_voxel_map_match_map (nos_voxelmap.hip); DESIGN.md §18.  The
+// last runs over a second store's voxels where the others run over a scan's points (Items, below).  Otherwise the routes
+// differ in their SOURCE only, as the two batched registrations differ in their Launcher (register_host.hpp).  A source
+// has view,
 // d_count, d_error (NULL for a snapshot: its search cannot fail), launch (starts a kernel of its view), kWhat (for
 // messages) and three constants, which keep differences between the routes that nothing requires:
 //   kTallyLaunches, kRecordLastKernel   only the store routes report to the bracket profiler / set the slot's last_kernel
@@ -51,20 +53,42 @@ inline int check_match_call(const nos_ctx* map_ctx, const nos_scan* scan, const 
   return NOS_OK;
 }
 
+// What a match runs over, one thread per item.  Items have n(), kForm (what a message of the flat match calls the route)
+// and lead(f): f(the kernel's arguments between the view and the item count).  A scan's points are the items of every
+// match but the map-to-map one, whose items are a second store's voxels (nos_voxelmap.hip's StoreVoxels).
+struct ScanPoints {
+  const nos_scan* scan;
+  static constexpr const char* kForm = "";
+  size_t n() const { return scan->n; }
+  template <typename F>
+  void lead(F f) const {
+    const double *px = scan->d_planes, *py = px + scan->n, *pz = py + scan->n;
+    f(px, py, pz);
+  }
+};
+
 // What every match begins with, queued on the slot's stream: counter and probe-error word cleared, then `kernel`, one
-// thread per scan point, on (view, the scan's planes, n, pose, max_neighbors, tail…, counter[, error word]).
-template <typename Src, typename Kernel, typename... Tail>
-hipError_t start_match(const Src& src, DeviceSlot& slot, Kernel kernel, const nos_scan* scan, const nos::PosePod& pose,
-                       int max_neighbors, Tail... tail) {
-  const size_t n = scan->n;
+// thread per item, on (view, the items' arguments, n, pose, max_neighbors, tail…, counter[, error word]).
+template <typename Src, typename Kernel, typename Items, typename... Tail>
+hipError_t start_match_over(const Src& src, DeviceSlot& slot, Kernel kernel, const Items& items, const nos::PosePod& pose,
+                            int max_neighbors, Tail... tail) {
+  const size_t n = items.n();
   hipError_t e = hipMemsetAsync(src.d_count, 0, sizeof(unsigned long long), slot.stream);
   if (e == hipSuccess && src.d_error) e = hipMemsetAsync(src.d_error, 0, sizeof(unsigned int), slot.stream);
   if (e != hipSuccess || n == 0) return e;
-  const double *px = scan->d_planes, *py = px + n, *pz = py + n;
-  src.launch(kernel, dim3(unsigned((n + 255) / 256)), slot.stream, px, py, pz, uint64_t(n), pose, max_neighbors, tail...);
+  items.lead([&](auto... lead) {
+    src.launch(kernel, dim3(unsigned((n + 255) / 256)), slot.stream, lead..., uint64_t(n), pose, max_neighbors, tail...);
+  });
   if (Src::kRecordLastKernel) slot.last_kernel = reinterpret_cast<const void*>(kernel);
   if (Src::kTallyLaunches && slot.prof_on && slot.prof_every == 0) ++slot.prof_launches;  // SELF-REPORTED (bracket profiler)
   return hipGetLastError();
+}
+
+// start_match_over a scan's points: (view, the scan's planes, n, pose, max_neighbors, tail…, counter[, error word]).
+template <typename Src, typename Kernel, typename... Tail>
+hipError_t start_match(const Src& src, DeviceSlot& slot, Kernel kernel, const nos_scan* scan, const nos::PosePod& pose,
+                       int max_neighbors, Tail... tail) {
+  return start_match_over(src, slot, kernel, ScanPoints{scan}, pose, max_neighbors, tail...);
 }
 
 // After start_match (e: what queuing gave): both words to the host, the call's one wait for the matcher → the match's status.
@@ -82,32 +106,39 @@ int read_match_words(const Src& src, hipError_t e, hipStream_t st, const char* f
   return NOS_OK;
 }
 
-// The flat match: a dataset of two slots per scan point (out_ds goes to dataset_new), the view's match kernel by element
+// The flat match: a dataset of two slots per item (out_ds goes to dataset_new), the view's match kernel by element
 // type (k64, k32), the dataset's padding, the count.  One wait.  Call after check_match_call and whatever else the route
 // rejects.
-template <typename Src, typename K64, typename K32>
-int run_match(const Src& src, K64 k64, K32 k32, nos_ctx* ctx, const nos_scan* scan, const nos::PosePod& pose, int max_neighbors,
-              int dtype, nos_dataset** out_ds, size_t* n_matches) {
+template <typename Src, typename K64, typename K32, typename Items>
+int run_match_over(const Src& src, K64 k64, K32 k32, nos_ctx* ctx, const Items& items, const nos::PosePod& pose,
+                   int max_neighbors, int dtype, nos_dataset** out_ds, size_t* n_matches) {
   nos_dataset* ds = nullptr;
-  int rc = dataset_new(ctx, kKindNdt, 2 * scan->n, dtype, out_ds, &ds);
+  int rc = dataset_new(ctx, kKindNdt, 2 * items.n(), dtype, out_ds, &ds);
   if (rc != NOS_OK) return rc;
   Shard& sh = ds->shards[0];
   DeviceSlot& slot = ctx->slots[0];
   hipError_t e = hipSetDevice(slot.device);
   if (e == hipSuccess)
-    e = dtype == NOS_F64 ? start_match(src, slot, k64, scan, pose, max_neighbors, sh.layout, static_cast<double*>(sh.data))
-                         : start_match(src, slot, k32, scan, pose, max_neighbors, sh.layout, static_cast<float*>(sh.data));
+    e = dtype == NOS_F64 ? start_match_over(src, slot, k64, items, pose, max_neighbors, sh.layout, static_cast<double*>(sh.data))
+                         : start_match_over(src, slot, k32, items, pose, max_neighbors, sh.layout, static_cast<float*>(sh.data));
   if (e == hipSuccess) {
     rc = zero_pad(dtype, nos::kNdtStored, sh.layout, sh.data, slot.stream);  // the dataset's padding: a launch when there is some
     if (Src::kTallyLaunches && slot.prof_on && slot.prof_every == 0 && sh.layout.n_padded > sh.layout.n) ++slot.prof_launches;
   }
-  if (rc == NOS_OK) rc = read_match_words(src, e, slot.stream, "", n_matches);
+  if (rc == NOS_OK) rc = read_match_words(src, e, slot.stream, Items::kForm, n_matches);
   if (rc != NOS_OK) {
     nos_dataset_destroy(ds);
     return rc;
   }
   *out_ds = ds;
   return NOS_OK;
+}
+
+// run_match_over a scan's points: two slots per scan point.
+template <typename Src, typename K64, typename K32>
+int run_match(const Src& src, K64 k64, K32 k32, nos_ctx* ctx, const nos_scan* scan, const nos::PosePod& pose, int max_neighbors,
+              int dtype, nos_dataset** out_ds, size_t* n_matches) {
+  return run_match_over(src, k64, k32, ctx, ScanPoints{scan}, pose, max_neighbors, dtype, out_ds, n_matches);
 }
 
 // The first half of an indexed match: the two id planes *d_idx = [2][n] from the call's arena `buf`, the view's index

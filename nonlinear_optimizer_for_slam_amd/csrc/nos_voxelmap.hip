@@ -7,6 +7,7 @@
 #include "voxelmap_kernels.hpp"
 #include "voxelmatch_kernels.hpp"
 #include "voxelmerge_kernels.hpp"
+#include "voxeld2d_kernels.hpp"
 
 using namespace nosd;
 
@@ -418,6 +419,25 @@ hipError_t compact_ids(size_t capacity, DeviceSlot& slot, DeviceBuffers& buf, in
   return e;
 }
 
+// The items of the map-to-map match (match_host.hpp's run_match_over): a store's voxels where every other match has a
+// scan's points — one lane per slot of `source`, two dataset slots each; nothing of the store is written.  rot: the
+// pose's rotation once more, for the kernel's algebra (voxeld2d_kernels.hpp).
+struct StoreVoxels {
+  const nos_voxel_map* source;
+  nos::RotPod rot;
+  static constexpr const char* kForm = "map-to-map ";
+  StoreVoxels(const nos_voxel_map* s, const nos::PosePod& pose) : source(s) {
+    for (int k = 0; k < 9; ++k) rot.R[k] = pose.R[k];
+  }
+  size_t n() const { return source->n_voxels; }
+  template <typename F>
+  void lead(F f) const {
+    const nos::VoxelStoreView& sv = source->view;
+    f(static_cast<const unsigned char*>(sv.valid), static_cast<const double*>(sv.mean), static_cast<const double*>(sv.sqrt_info),
+      rot);
+  }
+};
+
 int voxel_map_register(int dof, nos_voxel_map* vm, nos_scan* const* scans, int32_t n_problems, double* R, double* t,
                        const nos_loss* loss, const nos_register_options* ropt, const nos_lm_options* options,
                        nos_register_report* reports) {
@@ -581,6 +601,37 @@ int nos_voxel_map_match(nos_voxel_map* vm, nos_scan* scan, const double R[9], co
                  make_pose(R, t), max_neighbors, dtype, &ds, n_matches);
   if (rc == NOS_OK) *out_ds = ds;
   return rc;
+}
+
+int nos_voxel_map_match_map(nos_voxel_map* target, nos_voxel_map* source, const double R[9], const double t[3], int max_neighbors,
+                            int dtype, nos_dataset** out_ds, size_t* n_matches) {
+  nosd::CtxGuard guard_(target ? target->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  // nos_voxel_map_match's rejections in its order, with the source store where it has the scan
+  if (!target || !source || !R || !t || !out_ds) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (target->ctx != source->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "the two voxel maps belong to different contexts");
+  if (dtype != NOS_F64 && dtype != NOS_F32) return fail(NOS_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
+  if (max_neighbors < 1 || max_neighbors > 2) return fail(NOS_ERR_UNSUPPORTED, "max_neighbors must be 1 or 2");
+  if (target->ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "matching against a voxel store needs a single-device context");
+  int rc = check_live_store(live_store(target));
+  if (rc != NOS_OK) return rc;
+  if (source->broken) return fail(NOS_ERR_HIP, "the source voxel store was left undefined by an earlier failure");
+  nos_dataset* ds = nullptr;  // *out_ds is written on success only
+  const nos::PosePod pose = make_pose(R, t);
+  rc = run_match_over(StoreSource{live_store(target)}, nos::voxel_match_map_kernel<double>, nos::voxel_match_map_kernel<float>,
+                      target->ctx, StoreVoxels(source, pose), pose, max_neighbors, dtype, &ds, n_matches);
+  if (rc == NOS_OK) *out_ds = ds;
+  return rc;
+}
+
+// Test hook: the combined information on the HOST — voxel_pair_information as the kernel compiles it, no GPU call.
+int nos_debug_voxel_pair_information(const double S_target[9], const double S_source[9], const double R[9], double S_out[9],
+                                     unsigned char* ok) {
+  if (!S_target || !S_source || !R || !S_out || !ok) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  double St[9], Ss[9], Rm[9], out[9];
+  for (int k = 0; k < 9; ++k) St[k] = S_target[k], Ss[k] = S_source[k], Rm[k] = R[k];
+  *ok = nos::voxel_pair_information(St, Ss, Rm, out);
+  for (int k = 0; k < 9; ++k) S_out[k] = out[k];
+  return NOS_OK;
 }
 
 int nos_voxel_map_match_indexed(nos_voxel_map* vm, nos_scan* scan, const double R[9], const double t[3], int max_neighbors,

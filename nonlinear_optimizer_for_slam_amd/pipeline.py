@@ -93,6 +93,88 @@ def scan_to_map(ctx, ndt_map, scan, initial_pose=None, loss=("exponential", 1.0,
     return pose, rounds, outer
 
 
+def map_to_map(ctx, target, source, initial_pose=None, loss=("exponential", 1.0, 1.0), options=None,
+               max_outer_iterations=10, max_neighbors=2, dtype="f64", levels=None, on_solve=None):
+    """The pose of one api.VoxelMap in the frame of another, from their voxels alone (distribution-to-distribution NDT,
+    DESIGN.md §23): scan_to_map's outer loop with target.match_map(source, ...) as the matcher — up to
+    max_outer_iterations rounds of {match_map at the current pose, 6-DoF SolveDataset}, the same stopping test, the same
+    `rounds` dicts, RuntimeError when a round's solve fails.  A round's information matrices are those of its match and
+    stay fixed during its solve; the next round re-evaluates them with the correspondences.  Neither store is modified.
+    levels: None, or factors such as (4, 2, 1) — coarse to fine: for a factor f != 1 target.coarsened(f) is registered
+    against the source coarsened ON THE SAME GRID: the source's voxels merged, under the previous level's pose, into a
+    fresh store with the coarse target's resolution and radius (VoxelMap.merge, the source's flags), so both coarse maps
+    cut space along the same planes and summarise the same pieces of it when the pose is right.  (source.coarsened(f)
+    cuts along the source's own axes, which the pose turns and shifts against the target's; two partitions half a cell
+    apart give means that differ by up to half a coarse cell at the true pose.)  That level solves for the correction on
+    top of its start pose and the two are composed.  Both temporaries are closed, also before an exception leaves;
+    factor 1 uses the stores themselves and has to be the last one (ValueError otherwise: a coarse level's normal
+    equations describe its correction, not the pose returned).  Every level runs up to max_outer_iterations rounds;
+    `rounds` is the concatenation, each dict with a "level" key, and outer_iter is the last level's.
+    → (Pose, rounds, outer_iter, info).  info["sums"]: NdtDataset.accumulate6 (21 H | 6 g | cost, under `loss`) of ONE
+    MORE match_map of the stores themselves at the returned pose — so correspondences, information matrices and
+    linearisation point all belong to that pose; its 6 x 6 block is what a caller turns into the information of a
+    pose-graph edge.  info["matches"]: that match's count."""
+    pose = Pose() if initial_pose is None else Pose(initial_pose.R, initial_pose.t)
+    options = options or Options()
+    solver = MahalanobisDistanceMinimizerHip(device_ids=ctx.device_ids, dtype=dtype)
+    solver.SetLossFunction(loss)
+    rounds, outer, info = [], 0, {}
+    factors = (1,) if levels is None else tuple(levels)
+    if not factors:
+        raise ValueError("levels needs at least one factor")
+    if factors[-1] != 1:
+        raise ValueError("the last factor of levels has to be 1: info[\"sums\"] and the returned pose belong to the stores "
+                         "themselves, a coarse level only prepares the start of the next (got %r)" % (factors,))
+    for li, factor in enumerate(factors):
+        made = []
+        base = None
+        try:
+            if factor == 1:
+                tgt, src = target, source
+            else:
+                tgt = target.coarsened(factor)
+                made.append(tgt)
+                src = VoxelMap(ctx, tgt.voxel_resolution, tgt.search_radius_sq, flags=source._flags)
+                made.append(src)
+                base = pose
+                src.merge(source, base.R, base.t)
+                pose = Pose()  # the correction on top of `base`: src is already in the target's frame as base has it
+            last = Pose(pose.R, pose.t)
+            for outer in range(max_outer_iterations):
+                dataset, n_matches = tgt.match_map(src, pose.R, pose.t, max_neighbors, dtype)
+                try:
+                    if not solver.SolveDataset(options, dataset, pose):
+                        raise RuntimeError("SolveDataset failed (status %d)" % solver.report.status)
+                finally:
+                    dataset.close()
+                row = {"matches": n_matches, "used": n_matches, "iterations": solver.report.iterations,
+                       "printed_cost": solver.report.printed_cost}
+                if levels is not None:
+                    row["level"] = factor
+                rounds.append(row)
+                if on_solve is not None:
+                    on_solve(outer, solver.report, n_matches)
+                dR = pose.R.T @ last.R
+                dt = pose.R.T @ (last.t - pose.t)
+                if np.linalg.norm(dt) < 1e-5 and _quat_vec_norm(dR) < 1e-5:
+                    break
+                last = Pose(pose.R, pose.t)
+            else:
+                outer = max_outer_iterations
+            if li == len(factors) - 1:
+                dataset, n_matches = tgt.match_map(src, pose.R, pose.t, max_neighbors, dtype)
+                try:
+                    info = {"sums": dataset.accumulate6(pose.R, pose.t, loss), "matches": n_matches}
+                finally:
+                    dataset.close()
+            if base is not None:
+                pose = Pose(pose.R @ base.R, pose.R @ base.t + pose.t)
+        finally:
+            for vm in made:
+                vm.close()
+    return pose, rounds, outer, info
+
+
 def scan_to_map_batch(ctx, ndt_map, scans, initial_poses=None, loss=("exponential", 1.0, 1.0), options=None,
                       max_outer_iterations=10, dof=6, dtype="f64", keep_multiple=None):
     """scan_to_map for many scans against one map in ONE launch (api.register6_batch / register3_batch): the outer loop
