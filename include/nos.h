@@ -265,6 +265,35 @@ int nos_scan_order(const nos_scan* scan, uint32_t* order_out);
 int nos_scan_filter(nos_scan* scan, double voxel_size, nos_scan** out_scan);
 /* points_xyz_out: [nos_scan_size][3], the points in stored order (diagnostics, tests, callers that need them back) */
 int nos_scan_points(const nos_scan* scan, double* points_xyz_out);
+/* Motion compensation ("deskewing") on the device: a NEW, independent scan whose points are re-expressed in the sensor
+ * frame at one reference instant, under a constant-twist model of the sensor's motion during the sweep.
+ * Rule: the sensor pose at time s is T(s) = T(s_ref) Exp((s - s_ref) xi), the twist xi = (v, w) in the body frame and per
+ * unit of the time stamps.  A point p measured at time s in the sensor's own frame becomes
+ *   tau = s - s_ref,   phi = tau w,   u = tau v,   theta = |phi|
+ *   p' = Exp(tau xi) p = R(phi) p + V(phi) u
+ *   R(phi) p = p + a (phi x p) + b (phi x (phi x p))
+ *   V(phi) u = u + b (phi x u) + c (phi x (phi x u))
+ *   a = sin(theta) / theta,  b = (1 - cos(theta)) / theta^2,  c = (theta - sin(theta)) / theta^3   (1, 1/2, 1/6 at theta = 0)
+ * — the SE(3) exponential, not the split SO(3) x R^3 interpolation.  twist[6] is translation first, rotation second
+ * (v, then w): the parameter order of the 6-DoF solver and of the reference's pose_optimizer update.
+ *   times    host array indexed by a point's ORIGINAL index — what nos_scan_order reports: the stored position for a scan
+ *            that was never sorted nor filtered, otherwise order[j].  A cell-sorted or a filtered scan is therefore
+ *            deskewed with the time stamps of the array it came from.  Only entries a stored point refers to are examined.
+ *   output   same n, same stored order; nos_scan_order(out) is a copy of the input's (absent if the input has none).  The
+ *            input scan is unchanged.  An empty scan deskews to an empty scan.
+ *   exact    tau == 0 leaves a point's coordinates equal (==) to the input's, and so does xi == 0 (a -0.0 may come back as
+ *            +0.0).  The bits of a point's result are a function of (p, s, s_ref, xi) alone: the same from run to run,
+ *            whatever the stored position or the launch geometry — deskewing a sorted or filtered scan gives the rows
+ *            [order] of the deskew of the source.  Large theta is legal (the math library reduces the argument).
+ *            Point coordinates are not validated: IEEE arithmetic carries non-finite ones through.
+ * Single-device contexts only.  A rejected call writes nothing, *out_scan included, and leaves nothing allocated:
+ *   NOS_ERR_INVALID_ARGUMENT  scan, out_scan or twist is NULL; times is NULL while the scan has points; reference_time or
+ *                             a twist component is not finite; a stored point's original index is >= n_times; a stored
+ *                             point's time stamp is not finite (the error text names the stored position for these two)
+ *   NOS_ERR_UNSUPPORTED       the context has more than one device; the scan has >= 2^32 - 1 points
+ *   NOS_ERR_OUT_OF_MEMORY     the time stamps (8 B per entry of times) or the new scan do not fit */
+int nos_scan_deskew(nos_scan* scan, const double* times, size_t n_times, double reference_time,
+                    const double twist[6], nos_scan** out_scan);
 int nos_ndt_match(nos_ndt_map* map, nos_scan* scan, const double R[9], const double t[3],
                   int max_neighbors, int dtype, nos_dataset** out_ds, size_t* n_matches);
 /* Tail drop of the reference's solver classes for a matcher-written dataset.  The scalar 3-DoF class uses only the

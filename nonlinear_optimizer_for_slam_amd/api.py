@@ -1029,6 +1029,26 @@ class Scan:
         self._ctx._adopt(out)
         return out
 
+    def deskewed(self, times, twist, reference_time=1.0):
+        """→ a new Scan, motion-compensated under a constant twist (nos_scan_deskew, on the device): the point measured at
+        times[i] becomes Exp((times[i] - reference_time) * twist) p, its coordinates in the sensor frame at reference_time.
+        times: one time stamp per point of the array this scan was made from (indexed like `order`, so a sorted or filtered
+        scan takes the source array's stamps); twist: [6] = (v, w), body frame, per unit of `times` (pipeline.pose_twist
+        gives one from two poses).  Same length, same stored order, same `order`.  This scan is unchanged."""
+        times = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        twist = np.ascontiguousarray(twist, dtype=np.float64).reshape(-1)
+        if twist.size != 6:
+            raise ValueError("twist must have 6 components (v, w)")
+        h = ctypes.c_void_p()
+        check(self._lib.nos_scan_deskew(self._h, _dp(times), times.size, ctypes.c_double(reference_time), _dp(twist),
+                                        ctypes.byref(h)), "nos_scan_deskew")
+        out = Scan.__new__(Scan)
+        out._ctx = self._ctx
+        out._lib = self._lib
+        out._h = h
+        self._ctx._adopt(out)
+        return out
+
     def points(self):
         """→ the points [n,3] in stored order (nos_scan_points; diagnostics and tests)."""
         out = np.zeros((len(self), 3), dtype=np.float64)

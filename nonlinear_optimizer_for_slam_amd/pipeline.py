@@ -6,6 +6,8 @@ nonlinear_optimizer/mahalanobis_distance_minimizer/tests/simple_optimization_tes
 up to 10 rounds of {MatchPointCloud at the current pose, Solve()}, stopping when the pose changed by
 less than 1e-5 in translation and in the quaternion vector part.
 """
+import math
+
 import numpy as np
 
 from .api import NdtMap, Scan, VoxelMap, register3_batch, register6_batch, score_batch
@@ -17,6 +19,75 @@ def _quat_vec_norm(R):
     c = (np.trace(R) - 1.0) / 2.0
     c = min(1.0, max(-1.0, c))
     return float(np.sqrt(max(0.0, (1.0 - c) / 2.0)))
+
+
+_SERIES_THETA = 0.25  # below it (theta - sin theta) / theta^3 and its kin come from their series (kDeskewSeriesTheta)
+
+
+def _hat(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def twist_pose(twist):
+    """twist [6] = (v, w), translation first → Pose = Exp(twist), the SE(3) exponential (the rule of nos_scan_deskew,
+    DESIGN.md §24): R = I + a [w]x + b [w]x², t = (I + b [w]x + c [w]x²) v with a = sin θ / θ, b = (1 − cos θ) / θ²,
+    c = (θ − sin θ) / θ³ at θ = |w|.  1 − cos θ is 2 sin²(θ/2), c comes from its series below θ = 0.25, and θ < 1e-8 (θ = 0,
+    θ² underflowing) gives the limits 1, 1/2, 1/6."""
+    twist = np.asarray(twist, dtype=np.float64).reshape(6)
+    v, w = twist[:3], twist[3:]
+    theta = math.hypot(w[0], w[1], w[2])  # scaled: 1e-170 stays 1e-170
+    q = theta * theta
+    if theta < 1e-8:  # the limits are exact to the last digit here (1 − θ²/6, …), and θ² may underflow
+        a, b, c = 1.0, 0.5, 1.0 / 6.0
+    else:
+        a = np.sin(theta) / theta
+        b = 2.0 * np.sin(0.5 * theta) ** 2 / q
+        if theta < _SERIES_THETA:
+            c = 1 / 6 + q * (-1 / 120 + q * (1 / 5040 + q * (-1 / 362880 + q * (1 / 39916800 - q / 6227020800))))
+        else:
+            c = (theta - np.sin(theta)) / (q * theta)
+    W = _hat(w)
+    W2 = W @ W
+    return Pose(np.eye(3) + a * W + b * W2, v + b * (W @ v) + c * (W2 @ v))
+
+
+def pose_twist(pose_a, pose_b):
+    """→ twist [6] = Log(T_a⁻¹ T_b), translation first: the constant body-frame twist that carries pose_a to pose_b in
+    one unit of time (twist_pose's inverse).  Rotation angles up to π − 1e-6; at π itself the axis' sign is not defined
+    and the result is one of the two logarithms, with no promise which.
+    The angle is atan2(|vec|, (tr − 1) / 2) with vec the antisymmetric part of R, so it is as accurate near 0 as near π/2;
+    beyond 3π/4 the axis comes from the symmetric part, where vec loses its digits.  The translation is V⁻¹ t,
+    V⁻¹ = I − ½ [w]x + d [w]x², d = (1 − (θ/2) cot(θ/2)) / θ², from its series below θ = 0.25."""
+    if np.array_equal(pose_a.R, pose_b.R) and np.array_equal(pose_a.t, pose_b.t):
+        return np.zeros(6)  # exactly, whatever the rounding of Rᵀ R
+    R = pose_a.R.T @ pose_b.R
+    t = pose_a.R.T @ (pose_b.t - pose_a.t)
+    vec = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])  # sin θ · axis
+    s = math.hypot(vec[0], vec[1], vec[2])
+    cth = 0.5 * (np.trace(R) - 1.0)
+    theta = float(np.arctan2(s, cth))
+    if s == 0.0:
+        w = vec.copy()  # θ = 0 (θ = π exactly is not supported)
+    elif cth > -0.7:
+        w = vec * (theta / s)
+    else:  # R + Rᵀ = 2 cos θ I + 2 (1 − cos θ) k kᵀ: the largest k_i from the diagonal, the others from its row
+        S = 0.5 * (R + R.T)
+        i = int(np.argmax(np.diag(S)))
+        ki = np.sqrt(max(0.0, (S[i, i] - cth) / (1.0 - cth)))
+        axis = S[i] / ((1.0 - cth) * ki)
+        axis[i] = ki
+        if vec[i] < 0.0:
+            axis = -axis
+        w = axis * (theta / np.sqrt(axis @ axis))
+    q = theta * theta
+    if theta < _SERIES_THETA:
+        d = 1 / 12 + q * (1 / 720 + q * (1 / 30240 + q * (1 / 1209600 + q * (1 / 47900160 + q * (
+            691 / 1307674368000 + q * (1 / 74724249600 + q * (3617 / 10670622842880000)))))))
+    else:
+        half = 0.5 * theta
+        d = (1.0 - half * np.cos(half) / np.sin(half)) / q
+    W = _hat(w)
+    return np.concatenate([t - 0.5 * (W @ t) + d * (W @ (W @ t)), w])
 
 
 def scan_to_map(ctx, ndt_map, scan, initial_pose=None, loss=("exponential", 1.0, 1.0), options=None,
@@ -266,7 +337,8 @@ _ONE_LAUNCH_KWARGS = ("loss", "options", "max_outer_iterations", "dof", "dtype",
 
 
 def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, max_voxel_age=None, filter_voxel_size=None,
-             insert_filtered=False, live_match=None, one_launch=False, live_indexed=False, **scan_to_map_kwargs):
+             insert_filtered=False, live_match=None, one_launch=False, live_indexed=False, sweep_times=None, sweep_reference=1.0,
+             **scan_to_map_kwargs):
     """Scan-to-map odometry over a growing map (api.VoxelMap): for each scan, snapshot the store → scan_to_map from the
     previous scan's pose → insert the scan at the pose found (VoxelMap.insert_scan, warped on the device).  The harness's
     sequence UpdateNdtMap → OptimizePose → UpdateNdtMap (MDM/tests/simple_optimization_test.cc:236-281, 474-503) with the
@@ -290,6 +362,13 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
     live_indexed=True: every round matches through VoxelMap.match_indexed (scan_to_map's live_indexed: the voxel-indexed
     layout with a compact table, no snapshot).  Implies live_match; an explicit live_match=False raises ValueError.  Same
     poses and rounds, bit for bit, as odometry(indexed=True) on the snapshot route.  Not a keyword of one_launch=True.
+    sweep_times: a sequence of one time array per scan (indexed like the scan's `order`): every frame is first motion-
+    compensated on the device (Scan.deskewed) and the deskewed scan takes the raw scan's place for the
+    filter, the registration and the insert; it is closed after the frame, also when an exception leaves.  Convention:
+    times are in units of one sweep period; a frame's pose is the sensor pose at its reference instant, the time
+    sweep_reference of its own array (1.0: the end of the sweep); consecutive reference instants are 1.0 apart.  Frame k
+    is deskewed with the constant-velocity twist pose_twist(poses[k-2], poses[k-1]), frames 0 and 1 with zero.  The
+    start pose of a frame's registration stays the previous pose.  None: nothing is deskewed.
     → (list of Poses, list of per-scan round lists)."""
     if live_indexed:
         if live_match is not None and not live_match:
@@ -313,9 +392,15 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
     pose = Pose() if initial_pose is None else Pose(initial_pose.R, initial_pose.t)
     windowed = window_half_extent is not None or max_voxel_age is not None
     poses, all_rounds = [], []
-    for scan in scans:
-        registered = scan if filter_voxel_size is None else scan.filtered(filter_voxel_size)
+    for k, scan in enumerate(scans):
+        raw = scan
+        if sweep_times is not None:  # constant velocity: the last frame-to-frame motion goes on through this sweep
+            twist = pose_twist(poses[k - 2], poses[k - 1]) if k >= 2 else np.zeros(6)
+            scan = raw.deskewed(sweep_times[k], twist, sweep_reference)
+        registered = scan
         try:
+            if filter_voxel_size is not None:
+                registered = scan.filtered(filter_voxel_size)
             ndt_map = voxel_map if live_match else voxel_map.snapshot()
             try:
                 if one_launch:
@@ -332,6 +417,8 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
         finally:
             if registered is not scan:
                 registered.close()
+            if scan is not raw:
+                scan.close()
         if windowed:
             box = window_half_extent is not None
             voxel_map.prune(center=pose.t if box else None, half_extent=window_half_extent if box else None,
