@@ -257,11 +257,26 @@ __device__ __forceinline__ bool lm_solve_lane(const LdsDouble* tot, double lambd
   return nos_host::DampedStep<N>(out, lambda, step);
 }
 
+// |v| < tol with `n2` = |v|^2 already summed: squared norm against squared tolerance while both are normal doubles.  Where
+// one is not (it underflowed, overflowed or is NaN — or |v| is exactly 0) the comparison of squares says nothing:
+// nos_host::NormBelowScaled, the host loop's own rare arm (a square root, no division).
+template <int N, typename V>
+__device__ __forceinline__ bool lm_norm_below(double n2, double tol, const V& src) {
+  if (!(tol > 0.0)) return false;  // the test is switched off
+  const double t2 = tol * tol;
+  if (nos_host::SquareInRange(n2) && nos_host::SquareInRange(t2)) return n2 < t2;
+  double v[N];
+#pragma unroll
+  for (int r = 0; r < N; ++r) v[r] = src[r];
+  return nos_host::NormBelowScaled<N>(v, n2, tol);
+}
+
 // Second half: pose update, the two convergence tests (after the update, as in the reference), λ schedule — the rest of
 // nos_host::LmAdvance6 / LmAdvance3 with the transcendental part written for a lone GPU lane, where every fp64 instruction
 // costs 8 cycles whatever it computes: the exponential map's two factors are even in θ and are summed as power series for
 // θ < 1/8 (no square root, no argument reduction, no division; sincos beyond), normalisation by reciprocal square root (seed
-// + two Newton steps), the tests on squared norms.  Within an ulp or two of the host loop's libm calls per operation.
+// + two Newton steps), the tests on squared norms (the host's scaled form where a square leaves the normal range).  Measured
+// against 60 digits beside the host step and a plain numpy statement: DESIGN.md §5, tests/test_lm_step_xprec.py.
 template <int NOUT, int N>
 __device__ __forceinline__ void lm_finish_lane(const LdsDouble* tot, LdsLmDevice* lmd, const double (&step)[N], bool solved) {
   NOS_PROBE(unsigned long long tick_ = clock64();)
@@ -336,7 +351,7 @@ __device__ __forceinline__ void lm_finish_lane(const LdsDouble* tot, LdsLmDevice
     lmd->st.R[2] = dd * c + e * sn;
     lmd->st.R[3] = e * c - dd * sn;
   }
-  if ((ptol > 0.0 && s2 < ptol * ptol) || (gtol > 0.0 && g2 < gtol * gtol)) {  // |step| < ptol || |g| < gtol
+  if (lm_norm_below<N>(s2, ptol, step) || lm_norm_below<N>(g2, gtol, tot + N * (N + 1) / 2)) {  // |step| < ptol || |g| < gtol
     lmd->st.done = 1;
   } else {
     if (float_schedule) {

@@ -200,11 +200,32 @@ NOS_HD inline bool DampedStep(const double* out, double lambda, double* step) {
   return SolveLdlt<N>(H, mg, step);
 }
 
+// Is a sum of squares (or the square of a tolerance) a normal double: neither zero, subnormal, infinite nor NaN?
+NOS_HD inline bool SquareInRange(double s) { return s >= DBL_MIN && s <= DBL_MAX; }
+
+// |v| < tol where the sum of squares `s` of v, or the square of tol, is no normal double.  A normal s is compared through
+// its root.  One that underflowed (|v| below 1.5e-154) or overflowed (|v| above 1.3e154) is summed again over v times
+// 2^+600 or 2^-600, which puts every double's square back into range, against tol times the same power of two: an exact
+// product, unless it overflows (then every such v is below) or underflows (none is) — which is the answer.  A NaN
+// anywhere compares false and an infinite component is below no tolerance, as in the plain form.
 template <int N>
-NOS_HD inline double Norm(const double* v) {
+NOS_HD inline bool NormBelowScaled(const double* v, double s, double tol) {
+  if (SquareInRange(s)) return sqrt(s) < tol;
+  if (s != s) return false;
+  const double up = 4.149515568880993e180;  // 2^600
+  const double k = s < DBL_MIN ? up : 1.0 / up;
+  double s2 = 0.0;
+  for (int i = 0; i < N; ++i) s2 += (v[i] * k) * (v[i] * k);
+  return sqrt(s2) < tol * k;
+}
+
+// The convergence test |v| < tol of the loop: the reference's `v.norm() < tol` wherever the sum of squares is a normal
+// double, the scaled form where it is not (there the plain form would compare 0 or infinity with tol).
+template <int N>
+NOS_HD inline bool NormBelow(const double* v, double tol) {
   double s = 0.0;
   for (int i = 0; i < N; ++i) s += v[i] * v[i];
-  return sqrt(s);
+  return NormBelowScaled<N>(v, s, tol);
 }
 
 struct LmSettings {
@@ -305,7 +326,7 @@ NOS_HD inline void LmAdvance6(const LmSettings& s, const double out[28], LmState
   st->t[2] += step[2];
   RightMultiplyNormalize(&st->q, ExpQuat(step + 3));
   QuatToMatrix(st->q, st->R);
-  if (Norm<6>(step) < s.parameter_tolerance || Norm<6>(out + 21) < s.gradient_tolerance) {
+  if (NormBelow<6>(step, s.parameter_tolerance) || NormBelow<6>(out + 21, s.gradient_tolerance)) {
     st->done = 1;
     return;
   }
@@ -336,7 +357,7 @@ NOS_HD inline void LmAdvance3(const LmSettings& s, const double out[10], LmState
   st->R[1] = b * c - a * sn;
   st->R[2] = d * c + e * sn;
   st->R[3] = e * c - d * sn;
-  if (Norm<3>(step) < s.parameter_tolerance || Norm<3>(out + 6) < s.gradient_tolerance) {
+  if (NormBelow<3>(step, s.parameter_tolerance) || NormBelow<3>(out + 6, s.gradient_tolerance)) {
     st->done = 1;
     return;
   }
