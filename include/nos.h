@@ -496,6 +496,58 @@ typedef struct nos_voxel_prune {
   unsigned long long max_age;    /* in inserts */
 } nos_voxel_prune;
 int nos_voxel_map_prune(nos_voxel_map* map, const nos_voxel_prune* what, size_t* n_removed);
+/* Line-of-sight carving, the third prune rule: a ray that ends beyond a voxel has passed through it, so
+ * that voxel is free space.  Every point p of `scan` (its local frame) is a ray from the sensor origin; the rays are walked
+ * through the grid on the device and the voxels that enough rays cross and (almost) none end in are removed as a prune
+ * removes them.  Rule (exact; every operation is an IEEE double operation, fused only where it says so):
+ *   Ray.  o = R origin + t and e = R p + t, both with the multiply-adds of nos_voxel_map_insert_scan's warp (per row
+ *     fma(R2, z, fma(R0, x, R1 * y)) + t).  d = e - o per component, len = sqrt((dx dx + dy dy) + dz dz), not fused.
+ *     The ray is SKIPPED (counted in *n_skipped, counts nothing) iff e has a non-finite component, or !(len > min_range),
+ *     or !(len > end_margin), or one of the cells floor(o inv_res), floor(b inv_res), floor(e inv_res) lies outside the
+ *     addressable +-2^20 per axis (b below; inv_res = 1.0 / voxel_resolution, the factor an insert multiplies by).
+ *     s = (len - end_margin) / len when len <= max_range, else s = max_range / len (a longer ray is walked up to
+ *     max_range, not dropped).  Walked segment: a = o, b_k = o_k + s d_k (product rounded, then the sum).
+ *   Walk.  ca = floor(a inv_res), cb = floor(b inv_res) per axis.  Axis k makes n_k = |cb_k - ca_k| steps of
+ *     sign(cb_k - ca_k).  Its j-th crossing (j = 1 ... n_k) lies at g = double(ca_k + j) res going up and at
+ *     double(ca_k - j + 1) res going down, with parameter tau = (g - a_k) / (b_k - a_k): computed from j, never
+ *     accumulated (product, two differences, quotient: each rounded once).  An axis with n_k = 0 has no crossing and
+ *     nothing is divided for it.  Starting in ca, the walk repeatedly takes the pending crossing with the smallest tau —
+ *     equal tau go to x before y before z — and steps that axis.  It visits exactly 1 + n_x + n_y + n_z cells, the first
+ *     and the last included, always ends in cb, and visits no cell twice.  Every visited cell the store holds gets
+ *     crossings[voxel] += 1.
+ *   Hits.  The cell floor(e inv_res) of every ray that is not skipped, if the store holds it, gets hits[voxel] += 1.
+ *   Removal.  A voxel goes iff crossings >= min_crossings and hits < min_hits.  The survivors keep their relative order
+ *     and are renumbered by rank; the table, n_points, n_valid, generation and the capacity rule behave exactly as
+ *     nos_voxel_map_prune with the same keep flags.  epoch and the stamps are untouched (a carve is not an insert).  With
+ *     nothing to remove, or with dry_run, nothing of the store is written and generation stays as it was.
+ * The counts are integers added by integer atomics: they do not depend on the order of the points or of the lanes.
+ * *n_removed (optional): voxels removed; with dry_run, the voxels that would go.  *n_skipped (optional): rays skipped.
+ * crossings_out, hits_out (optional): host arrays of n_voxels entries each, n_voxels as nos_voxel_map_info reports it
+ * BEFORE the call, in voxel-id order — what a caller needs to accumulate evidence over several scans by a policy of
+ * their own.  An empty scan or an empty store is a no-op (zero counts).
+ * Rejected, the store and every output unwritten; every NOS_ERR_INVALID_ARGUMENT check comes before any device is touched:
+ *   NOS_ERR_INVALID_ARGUMENT  map, scan, R, t or what NULL; struct_size < sizeof(nos_voxel_carve); a non-finite entry of
+ *                             R, t or origin; end_margin or min_range negative or not finite; max_range not finite or
+ *                             not above 0; min_crossings == 0 or min_hits == 0; a scan of another context;
+ *   NOS_ERR_UNSUPPORTED       a multi-device context; 3 (ceil(max_range / voxel_resolution) + 1) > NOS_CARVE_MAX_CELLS,
+ *                             the bound on a ray's trip count; a scan of 2^32 - 1 points or more;
+ *   NOS_ERR_HIP               a store left undefined by an earlier failure.
+ * A failure half-way leaves the store exactly as it was.  Work: one table probe per visited cell and one integer atomic
+ * per visited cell the store holds, plus a prune's; one host wait when nothing goes or with dry_run, two otherwise. */
+#define NOS_CARVE_MAX_CELLS 4096
+typedef struct nos_voxel_carve {
+  size_t struct_size;        /* sizeof(nos_voxel_carve), for later growth */
+  double origin[3];          /* sensor origin in the SCAN's frame (usually 0, 0, 0) */
+  double end_margin;         /* metres cut off the ray before its endpoint, >= 0 */
+  double min_range;          /* rays no longer than this are skipped, >= 0 */
+  double max_range;          /* longer rays are walked up to this length; finite, > 0 */
+  uint32_t min_crossings;    /* >= 1 */
+  uint32_t min_hits;         /* >= 1: a voxel with this many endpoints of THIS scan in its cell is protected */
+  int dry_run;               /* 1: count only, remove nothing */
+} nos_voxel_carve;
+int nos_voxel_map_carve(nos_voxel_map* map, nos_scan* scan, const double R[9], const double t[3],
+                        const nos_voxel_carve* what, size_t* n_removed, size_t* n_skipped,
+                        uint32_t* crossings_out, uint32_t* hits_out);
 /* Any output pointer may be NULL.  capacity: slots the arrays have room for; bytes: device memory the store holds;
  * epoch: see NOS_PRUNE_AGE; generation: times the store's device block was replaced (growth, a prune that removed
  * something). */

@@ -801,7 +801,8 @@ class VoxelMap:
 
     Voxel ids (the order of stats(), the matcher's tie-break) follow the sequence of batches: batch of first appearance,
     then ascending cell.  proper_sqrt_information as in NdtMap.build; capacity (voxels) only avoids early growth.
-    prune() removes voxels by a box and / or by age (a sliding window) and renumbers the survivors by their rank."""
+    prune() removes voxels by a box and / or by age (a sliding window) and renumbers the survivors by their rank;
+    carve() removes, the same way, the voxels a scan's rays pass through (line of sight)."""
 
     def __init__(self, ctx, voxel_resolution=1.0, search_radius_sq=1.0, proper_sqrt_information=True, capacity=0,
                  flags=None):
@@ -952,6 +953,44 @@ class VoxelMap:
         n = ctypes.c_size_t()
         check(self._lib.nos_voxel_map_prune(self._h, ctypes.byref(rule), ctypes.byref(n)), "nos_voxel_map_prune")
         return int(n.value)
+
+    def carve(self, scan, R, t, min_crossings=2, min_hits=1, end_margin=None, min_range=0.0, max_range=None, origin=(0, 0, 0),
+              dry_run=False, counts=False):
+        """Line-of-sight carving (nos_voxel_map_carve) → (number of voxels removed, info).  Every point of
+        the api.Scan is a ray from the sensor `origin` (scan frame), warped by R p + t and walked cell by cell through the
+        grid: a voxel that at least min_crossings rays pass through and in whose cell fewer than min_hits rays of this
+        scan end is free space and goes, as prune() removes voxels (survivors keep their order, renumbered by rank).
+        end_margin (default 1.5 · voxel_resolution): metres cut off each ray before its endpoint, so that the surface a
+        ray ends on is not carved by it.  Rays no longer than min_range are skipped; rays longer than max_range (default
+        1024 · voxel_resolution) are walked up to max_range.  dry_run=True removes nothing and returns the number of voxels
+        that would go.  info: {"skipped": rays skipped} and, with counts=True, "crossings" and "hits" — uint32 arrays in
+        voxel-id order as it was BEFORE the call, for callers who accumulate evidence over several scans themselves."""
+        R = _dvec(R, 9)
+        t = _dvec(t, 3)
+        o = _dvec(origin, 3)
+        what = _lib.NosVoxelCarve()
+        what.struct_size = ctypes.sizeof(_lib.NosVoxelCarve)
+        for k in range(3):
+            what.origin[k] = o[k]
+        what.end_margin = 1.5 * self.voxel_resolution if end_margin is None else float(end_margin)
+        what.min_range = float(min_range)
+        what.max_range = 1024.0 * self.voxel_resolution if max_range is None else float(max_range)
+        if int(min_crossings) < 0 or int(min_hits) < 0:
+            raise ValueError("min_crossings and min_hits must be >= 1")
+        what.min_crossings, what.min_hits, what.dry_run = int(min_crossings), int(min_hits), int(bool(dry_run))
+        removed, skipped = ctypes.c_size_t(), ctypes.c_size_t()
+        crossings = hits = None
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        if counts:
+            n = len(self)
+            crossings, hits = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        check(self._lib.nos_voxel_map_carve(self._h, scan._h, _dp(R), _dp(t), ctypes.byref(what), ctypes.byref(removed),
+                                            ctypes.byref(skipped), crossings.ctypes.data_as(u32p) if counts else None,
+                                            hits.ctypes.data_as(u32p) if counts else None), "nos_voxel_map_carve")
+        info = {"skipped": int(skipped.value)}
+        if counts:
+            info["crossings"], info["hits"] = crossings, hits
+        return int(removed.value), info
 
     def memory(self):
         """→ dict: capacity (slots), bytes (device memory held), epoch (successful non-empty inserts so far), generation

@@ -1,5 +1,6 @@
 // nos_voxelmap.hip — incremental NDT voxel store: a device-resident map that grows scan by scan; a batch
-// is grouped by voxel through group_host.hpp (§19), matched against through match_host.hpp (§18).
+// is grouped by voxel through group_host.hpp (§19), matched against through match_host.hpp (§18); it forgets by box and age
+// (prune, §13) and by line of sight (carve, §25).
 #define NOS_WITH_VOXEL_INDEX_KERNELS  // voxelmatch_kernels.hpp: this unit compiles (and launches) the two index kernels
 #include "group_host.hpp"
 #include "match_host.hpp"
@@ -8,6 +9,7 @@
 #include "voxelmatch_kernels.hpp"
 #include "voxelmerge_kernels.hpp"
 #include "voxeld2d_kernels.hpp"
+#include "voxelcarve_kernels.hpp"
 
 using namespace nosd;
 
@@ -276,78 +278,170 @@ int store_merge(nos_voxel_map* dst, const nos_voxel_map* src, const nos::PosePod
   return store_merge_runs(dst, buf, g.uniq, seg_count, seg_acc, U, src->n_points, "voxel store merge", n_touched);
 }
 
-// One prune: keep flags and totals, scan, ONE wait; when something goes, the survivors move to a fresh
-// block in their old order and the table is rebuilt there.  A failure at any point leaves the store as it was.
+// The keep flags of a prune or of a carve and everything behind them, ONE copy.  plan: arena memory
+// for the flags and their ranks, the scan's plan, the totals zeroed — all ahead of the caller's keep kernel, which writes
+// keep[] and the totals.  wait: the exclusive scan of the flags, then the ONE wait, which brings `n_words` words of d_info
+// from `first_word` on (the totals among them) into h_info.  compact: nothing to remove → nothing written, nothing
+// allocated; else the survivors move to a fresh block in their old order and the table is rebuilt there, with the
+// closing wait.  A failure at any point leaves the store as it was.
+struct KeepPass {
+  nos_voxel_map* vm;
+  size_t V;
+  hipStream_t st;
+  dim3 grid;
+  uint32_t *keep = nullptr, *new_slot = nullptr;
+  PrimTmp t_slots;
+  // removed voxels, their points (two words), valid voxels kept: words kInfoRemoved … kInfoKeptValid
+  unsigned int totals[4] = {0, 0, 0, 0};
+  explicit KeepPass(nos_voxel_map* m)
+      : vm(m), V(m->n_voxels), st(m->ctx->slots[0].stream), grid(unsigned((size_t(m->n_voxels) + 255) / 256)) {}
+  hipError_t scan(void* t, size_t& b) const { return rocprim::exclusive_scan(t, b, keep, new_slot, 0u, V, rocprim::plus<uint32_t>(), st); }
+  hipError_t plan(DeviceBuffers& buf) {
+    const auto new_slots = [&](void* t, size_t& b) { return scan(t, b); };
+    hipError_t e = buf.alloc(&keep, V);
+    if (e == hipSuccess) e = buf.alloc(&new_slot, V);
+    if (e == hipSuccess) e = prim_plan(buf, new_slots, t_slots);
+    static_assert(nos::kInfoKeptValid == nos::kInfoRemoved + 3 && nos::kInfoRemovedPoints == nos::kInfoRemoved + 1, "info layout");
+    if (e == hipSuccess) e = hipMemsetAsync(vm->d_info + nos::kInfoRemoved, 0, sizeof totals, st);
+    return e;
+  }
+  int wait(unsigned int* h_info, int first_word, int n_words) {
+    const auto new_slots = [&](void* t, size_t& b) { return scan(t, b); };
+    hipError_t e = prim_run(new_slots, t_slots);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(h_info + first_word, vm->d_info + first_word, size_t(n_words) * sizeof(unsigned int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // the one wait: what goes?
+    if (e != hipSuccess) return hip_fail(e, "voxel store prune (keep)");
+    for (int k = 0; k < 4; ++k) totals[k] = h_info[nos::kInfoRemoved + k];
+    return NOS_OK;
+  }
+  int compact(size_t* n_removed) {
+    const size_t removed = totals[0];
+    if (removed == 0) {  // the common per-frame case: nothing written, nothing allocated
+      if (n_removed) *n_removed = 0;
+      return NOS_OK;
+    }
+    const unsigned long long removed_points = (unsigned long long)totals[1] | ((unsigned long long)totals[2] << 32);
+    const size_t kept = V - removed;
+    size_t capacity = vm->capacity;
+    if (kept <= vm->capacity / 4) {
+      capacity = 16;
+      while (capacity < 2 * kept) capacity *= 2;
+      capacity = std::max(capacity, vm->min_capacity);
+    }
+    void* block = nullptr;
+    size_t block_bytes = 0;
+    nos::VoxelStoreView nv{};
+    hipError_t e = store_alloc(capacity, st, &block, &block_bytes, &nv);
+    if (e != hipSuccess) return hip_fail(e, "voxel store prune (new block)");
+    nv.n_voxels = uint32_t(kept);
+    unsigned int err = 0;
+    e = hipMemsetAsync(vm->d_info + nos::kInfoProbeError, 0, sizeof(unsigned int), st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(nos::voxel_compact_kernel, grid, dim3(256), 0, st, vm->view, nv, keep, new_slot, vm->d_info);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&err, vm->d_info + nos::kInfoProbeError, sizeof err, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // the closing wait: the old block is freed by adopt_block
+    const char* what = "voxel store prune (compact)";
+    if (e == hipSuccess && err == 0) {
+      // the device-side valid counter follows (in stream order before any later merge)
+      e = hipMemcpyAsync(vm->d_info + nos::kInfoValid, vm->d_info + nos::kInfoKeptValid, sizeof(unsigned int),
+                         hipMemcpyDeviceToDevice, st);
+      what = "voxel store prune (counter)";
+    }
+    const int rc = adopt_block(vm, e, err, what, "voxel store prune failed: the new table overflowed", block, block_bytes, nv, capacity);
+    if (rc != NOS_OK) return rc;
+    vm->n_voxels = uint32_t(kept);
+    vm->n_valid = totals[3];
+    vm->n_points -= removed_points;
+    if (n_removed) *n_removed = removed;
+    return NOS_OK;
+  }
+};
+
+// One prune: keep flags and totals by box and / or age, then KeepPass.
 int store_prune(nos_voxel_map* vm, const nos::VoxelKeepRule& rule, size_t* n_removed) {
-  const size_t V = vm->n_voxels;
-  if (V == 0) {
+  if (vm->n_voxels == 0) {
     if (n_removed) *n_removed = 0;
     return NOS_OK;
   }
   DeviceSlot& slot = vm->ctx->slots[0];
-  hipStream_t st = slot.stream;
   DeviceBuffers buf(&slot);
-  uint32_t *keep = nullptr, *new_slot = nullptr;
-  PrimTmp t_slots;
-  const auto new_slots = [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, keep, new_slot, 0u, V, rocprim::plus<uint32_t>(), st); };
+  KeepPass pass(vm);
   hipError_t e = hipSetDevice(slot.device);
-  buf.reserve(V * 2 * sizeof(uint32_t) + (size_t(1) << 20));
-  if (e == hipSuccess) e = buf.alloc(&keep, V);
-  if (e == hipSuccess) e = buf.alloc(&new_slot, V);
-  if (e == hipSuccess) e = prim_plan(buf, new_slots, t_slots);
-  // removed voxels, their points (two words), valid voxels kept: words kInfoRemoved … kInfoKeptValid
-  unsigned int totals[4] = {0, 0, 0, 0};
-  static_assert(nos::kInfoKeptValid == nos::kInfoRemoved + 3 && nos::kInfoRemovedPoints == nos::kInfoRemoved + 1, "info layout");
-  if (e == hipSuccess) e = hipMemsetAsync(vm->d_info + nos::kInfoRemoved, 0, sizeof totals, st);
-  const dim3 grid(unsigned((V + 255) / 256));
+  buf.reserve(pass.V * 2 * sizeof(uint32_t) + (size_t(1) << 20));
+  if (e == hipSuccess) e = pass.plan(buf);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(nos::voxel_keep_kernel, grid, dim3(256), 0, st, vm->view, rule, keep, vm->d_info);
+    hipLaunchKernelGGL(nos::voxel_keep_kernel, pass.grid, dim3(256), 0, pass.st, vm->view, rule, pass.keep, vm->d_info);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = prim_run(new_slots, t_slots);
-  if (e == hipSuccess) e = hipMemcpyAsync(totals, vm->d_info + nos::kInfoRemoved, sizeof totals, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the one wait: what goes?
   if (e != hipSuccess) return hip_fail(e, "voxel store prune (keep)");
-  const size_t removed = totals[0];
-  if (removed == 0) {  // the common per-frame case: nothing written, nothing allocated
+  unsigned int h_info[nos::kInfoWords] = {};
+  const int rc = pass.wait(h_info, nos::kInfoRemoved, 4);
+  return rc != NOS_OK ? rc : pass.compact(n_removed);
+}
+
+// One carve: the rays of `scan` under `pose` are walked through the grid (crossings and hits per slot,
+// zeroed per call), the keep flags follow from the two counters, then KeepPass.  Waits: the one that reads totals, flags
+// and the skipped count (it also brings the counters when the caller asked for them); the closing one of the compaction
+// when something goes.  The outputs are written once nothing can fail any more.
+int store_carve(nos_voxel_map* vm, const nos_scan* scan, const nos::PosePod& pose, const nos::VoxelCarveParams& prm,
+                uint32_t min_crossings, uint32_t min_hits, bool dry_run, size_t* n_removed, size_t* n_skipped,
+                uint32_t* crossings_out, uint32_t* hits_out) {
+  const size_t n = scan->n;
+  if (n >= 0xFFFFFFFFull) return fail(NOS_ERR_UNSUPPORTED, "too many points for one carve");
+  if (n == 0 || vm->n_voxels == 0) {  // nothing to walk, or nothing to find: every ray would count nothing
     if (n_removed) *n_removed = 0;
+    if (n_skipped) *n_skipped = 0;
+    if (crossings_out) std::memset(crossings_out, 0, size_t(vm->n_voxels) * sizeof(uint32_t));
+    if (hits_out) std::memset(hits_out, 0, size_t(vm->n_voxels) * sizeof(uint32_t));
     return NOS_OK;
   }
-  const unsigned long long removed_points = (unsigned long long)totals[1] | ((unsigned long long)totals[2] << 32);
-  const size_t kept = V - removed;
-  size_t capacity = vm->capacity;
-  if (kept <= vm->capacity / 4) {
-    capacity = 16;
-    while (capacity < 2 * kept) capacity *= 2;
-    capacity = std::max(capacity, vm->min_capacity);
-  }
-  void* block = nullptr;
-  size_t block_bytes = 0;
-  nos::VoxelStoreView nv{};
-  e = store_alloc(capacity, st, &block, &block_bytes, &nv);
-  if (e != hipSuccess) return hip_fail(e, "voxel store prune (new block)");
-  nv.n_voxels = uint32_t(kept);
-  unsigned int err = 0;
-  e = hipMemsetAsync(vm->d_info + nos::kInfoProbeError, 0, sizeof(unsigned int), st);
+  DeviceSlot& slot = vm->ctx->slots[0];
+  DeviceBuffers buf(&slot);
+  KeepPass pass(vm);
+  const size_t V = pass.V;
+  hipStream_t st = pass.st;
+  uint32_t* counters = nullptr;  // crossings [V], then hits [V]
+  std::vector<uint32_t> h_counters;
+  const bool want_counts = crossings_out || hits_out;
+  if (want_counts) h_counters.resize(2 * V);
+  hipError_t e = hipSetDevice(slot.device);
+  buf.reserve(V * 4 * sizeof(uint32_t) + (size_t(1) << 20));
+  if (e == hipSuccess) e = buf.alloc(&counters, 2 * V);
+  if (e == hipSuccess) e = pass.plan(buf);
+  if (e == hipSuccess) e = hipMemsetAsync(counters, 0, 2 * V * sizeof(uint32_t), st);
+  if (e == hipSuccess) e = hipMemsetAsync(vm->d_info + nos::kInfoProbeError, 0, sizeof(unsigned int), st);
+  if (e == hipSuccess) e = hipMemsetAsync(vm->d_info + nos::kInfoSkipped, 0, sizeof(unsigned int), st);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(nos::voxel_compact_kernel, grid, dim3(256), 0, st, vm->view, nv, keep, new_slot, vm->d_info);
+    hipLaunchKernelGGL(nos::voxel_carve_walk_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, vm->view, scan->d_planes,
+                       uint64_t(n), pose, prm, counters, counters + V, vm->d_info);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(&err, vm->d_info + nos::kInfoProbeError, sizeof err, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the closing wait: the old block is freed by adopt_block
-  const char* what = "voxel store prune (compact)";
-  if (e == hipSuccess && err == 0) {
-    // the device-side valid counter follows (in stream order before any later merge)
-    e = hipMemcpyAsync(vm->d_info + nos::kInfoValid, vm->d_info + nos::kInfoKeptValid, sizeof(unsigned int),
-                       hipMemcpyDeviceToDevice, st);
-    what = "voxel store prune (counter)";
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(nos::voxel_carve_keep_kernel, pass.grid, dim3(256), 0, st, vm->view, counters, counters + V, min_crossings,
+                       min_hits, pass.keep, vm->d_info);
+    e = hipGetLastError();
   }
-  const int rc = adopt_block(vm, e, err, what, "voxel store prune failed: the new table overflowed", block, block_bytes, nv, capacity);
+  if (e == hipSuccess && want_counts)
+    e = hipMemcpyAsync(h_counters.data(), counters, 2 * V * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+  if (e != hipSuccess) return hip_fail(e, "voxel store carve (walk)");
+  unsigned int h_info[nos::kInfoWords] = {};
+  static_assert(nos::kInfoProbeError < nos::kInfoRemoved && nos::kInfoSkipped == nos::kInfoKeptValid + 1, "info layout");
+  int rc = pass.wait(h_info, nos::kInfoProbeError, nos::kInfoSkipped - nos::kInfoProbeError + 1);
   if (rc != NOS_OK) return rc;
-  vm->n_voxels = uint32_t(kept);
-  vm->n_valid = totals[3];
-  vm->n_points -= removed_points;
-  if (n_removed) *n_removed = removed;
+  if (h_info[nos::kInfoProbeError] != 0)  // the store was only read: it is as it was
+    return fail(NOS_ERR_HIP, "voxel store carve failed: a table probe or a ray's walk ran past its bound");
+  if (dry_run) {  // what would go; nothing of the store is written
+    if (n_removed) *n_removed = h_info[nos::kInfoRemoved];
+  } else {
+    rc = pass.compact(n_removed);
+    if (rc != NOS_OK) return rc;
+  }
+  if (n_skipped) *n_skipped = h_info[nos::kInfoSkipped];
+  if (crossings_out) std::memcpy(crossings_out, h_counters.data(), V * sizeof(uint32_t));
+  if (hits_out) std::memcpy(hits_out, h_counters.data() + V, V * sizeof(uint32_t));
   return NOS_OK;
 }
 
@@ -568,6 +662,37 @@ int nos_voxel_map_prune(nos_voxel_map* vm, const nos_voxel_prune* what, size_t* 
   rule.epoch = uint32_t(vm->epoch);
   rule.max_age = what->max_age > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(what->max_age);
   return store_prune(vm, rule, n_removed);
+}
+
+int nos_voxel_map_carve(nos_voxel_map* vm, nos_scan* scan, const double R[9], const double t[3], const nos_voxel_carve* what,
+                        size_t* n_removed, size_t* n_skipped, uint32_t* crossings_out, uint32_t* hits_out) {
+  // the NULL, struct and value checks come before any device (and any handle's content) is touched
+  if (!vm || !scan || !R || !t || !what) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (what->struct_size < sizeof(nos_voxel_carve)) return fail(NOS_ERR_INVALID_ARGUMENT, "struct_size is smaller than nos_voxel_carve");
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(R[k])) return fail(NOS_ERR_INVALID_ARGUMENT, "R has a non-finite entry");
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(t[k]) || !std::isfinite(what->origin[k])) return fail(NOS_ERR_INVALID_ARGUMENT, "t or origin has a non-finite entry");
+  if (!std::isfinite(what->end_margin) || what->end_margin < 0.0 || !std::isfinite(what->min_range) || what->min_range < 0.0)
+    return fail(NOS_ERR_INVALID_ARGUMENT, "end_margin and min_range must be finite and >= 0");
+  if (!std::isfinite(what->max_range) || !(what->max_range > 0.0)) return fail(NOS_ERR_INVALID_ARGUMENT, "max_range must be finite and > 0");
+  if (what->min_crossings == 0 || what->min_hits == 0) return fail(NOS_ERR_INVALID_ARGUMENT, "min_crossings and min_hits must be >= 1");
+  if (vm->ctx != scan->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map and scan belong to different contexts");
+  nosd::CtxGuard guard_(vm->ctx);  // one solve / accumulate / create at a time per context
+  if (vm->ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "carving a voxel store needs a single-device context");
+  // a ray's trip count: at most ceil(max_range / res) + 1 steps per axis
+  if (3.0 * (std::ceil(what->max_range / vm->voxel_resolution) + 1.0) > double(NOS_CARVE_MAX_CELLS))
+    return fail(NOS_ERR_UNSUPPORTED, "max_range spans more than NOS_CARVE_MAX_CELLS cells: 3 (ceil(max_range / resolution) + 1) > %d",
+                NOS_CARVE_MAX_CELLS);
+  if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+  nos::VoxelCarveParams prm{};
+  for (int k = 0; k < 3; ++k) prm.origin[k] = what->origin[k];
+  prm.end_margin = what->end_margin, prm.min_range = what->min_range, prm.max_range = what->max_range;
+  prm.res = vm->voxel_resolution;
+  prm.inv_res = 1.0 / vm->voxel_resolution;  // what voxel_points_kernel is handed
+  prm.max_cells = NOS_CARVE_MAX_CELLS;
+  return store_carve(vm, scan, make_pose(R, t), prm, what->min_crossings, what->min_hits, what->dry_run != 0, n_removed, n_skipped,
+                     crossings_out, hits_out);
 }
 
 int nos_voxel_map_memory(const nos_voxel_map* vm, size_t* capacity, size_t* bytes, unsigned long long* epoch,

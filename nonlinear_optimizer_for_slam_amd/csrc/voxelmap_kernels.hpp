@@ -22,7 +22,7 @@
 // One prune = voxel_keep_kernel (a 0/1 flag per slot by box and / or age, and the totals of what goes) → exclusive scan
 // of the flags → voxel_compact_kernel (every kept slot moves to its rank among the kept ones in a FRESH block and enters
 // that block's empty table).  Out of place, because a parallel in-place stable compaction races: a lane's destination is
-// another lane's unread source.
+// another lane's unread source.  A carve (voxelcarve_kernels.hpp) writes its own keep flags and shares everything behind them.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -45,6 +45,8 @@ enum VoxelInfoWord {
   kInfoRemoved = 5,     // voxels the last keep pass marked for removal
   kInfoRemovedPoints = 6,  // their points: one 64-bit counter in words 6 and 7
   kInfoKeptValid = 8,   // valid voxels among those the last keep pass kept
+  kInfoSkipped = 9,     // rays the last carve skipped (voxelcarve_kernels.hpp); a carve also raises bit 1 of
+                        // kInfoProbeError when a ray's trip count ran past its bound
   kInfoMatches = 10,    // real matches of the last nos_voxel_map_match(_indexed): one 64-bit counter in words 10 and 11.  That call
                         // writes these two words and clears kInfoProbeError before its launch; "the store is not modified"
                         // holds for the info block by convention only: no call reads words 10-11, and every call that
@@ -218,6 +220,25 @@ struct VoxelKeepRule {
   int use_box, use_age;
 };
 
+// What every keep kernel ends with (every lane of the block calls it): the totals of what goes — voxels removed, their
+// points, valid voxels kept — summed over the wave and added by one integer atomic per wave each.
+__device__ __forceinline__ void voxel_keep_totals(unsigned int removed, unsigned long long removed_points, unsigned int kept_valid,
+                                                  unsigned int* __restrict__ info) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    removed += __shfl_xor(removed, o, kWave);
+    kept_valid += __shfl_xor(kept_valid, o, kWave);
+    removed_points += __shfl_xor(removed_points, o, kWave);
+  }
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    if (removed != 0) {
+      atomicAdd(&info[kInfoRemoved], removed);
+      atomicAdd(reinterpret_cast<unsigned long long*>(&info[kInfoRemovedPoints]), removed_points);
+    }
+    if (kept_valid != 0) atomicAdd(&info[kInfoKeptValid], kept_valid);
+  }
+}
+
 // Prune, step 1.  One lane per slot in use: keep[v] = 1 iff the voxel passes every test the rule asks for.  The totals
 // (voxels removed, their points, valid voxels kept) move by one integer atomic per wave each.  Nothing of the store is written.
 __global__ __launch_bounds__(256) void voxel_keep_kernel(VoxelStoreView s, VoxelKeepRule rule, uint32_t* __restrict__ keep,
@@ -242,19 +263,7 @@ __global__ __launch_bounds__(256) void voxel_keep_kernel(VoxelStoreView s, Voxel
       removed_points = s.count[v];
     }
   }
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) {
-    removed += __shfl_xor(removed, o, kWave);
-    kept_valid += __shfl_xor(kept_valid, o, kWave);
-    removed_points += __shfl_xor(removed_points, o, kWave);
-  }
-  if ((threadIdx.x & (kWave - 1)) == 0) {
-    if (removed != 0) {
-      atomicAdd(&info[kInfoRemoved], removed);
-      atomicAdd(reinterpret_cast<unsigned long long*>(&info[kInfoRemovedPoints]), removed_points);
-    }
-    if (kept_valid != 0) atomicAdd(&info[kInfoKeptValid], kept_valid);
-  }
+  voxel_keep_totals(removed, removed_points, kept_valid, info);
 }
 
 // Prune, step 2.  One lane per slot of the old block: a kept slot moves, with everything it holds, to

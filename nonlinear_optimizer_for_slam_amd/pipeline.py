@@ -338,7 +338,7 @@ _ONE_LAUNCH_KWARGS = ("loss", "options", "max_outer_iterations", "dof", "dtype",
 
 def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, max_voxel_age=None, filter_voxel_size=None,
              insert_filtered=False, live_match=None, one_launch=False, live_indexed=False, sweep_times=None, sweep_reference=1.0,
-             **scan_to_map_kwargs):
+             carve=None, **scan_to_map_kwargs):
     """Scan-to-map odometry over a growing map (api.VoxelMap): for each scan, snapshot the store → scan_to_map from the
     previous scan's pose → insert the scan at the pose found (VoxelMap.insert_scan, warped on the device).  The harness's
     sequence UpdateNdtMap → OptimizePose → UpdateNdtMap (MDM/tests/simple_optimization_test.cc:236-281, 474-503) with the
@@ -369,6 +369,13 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
     sweep_reference of its own array (1.0: the end of the sweep); consecutive reference instants are 1.0 apart.  Frame k
     is deskewed with the constant-velocity twist pose_twist(poses[k-2], poses[k-1]), frames 0 and 1 with zero.  The
     start pose of a frame's registration stays the previous pose.  None: nothing is deskewed.
+    carve: a dict of VoxelMap.carve keywords (may be empty) — every frame, after the registration and before the insert,
+    the store is carved along the rays of the scan about to be inserted, at the pose found (line of sight):
+    what stood in front of the sensor for a few frames (a car, a person, a door) goes once the sensor sees through it.
+    The inserted scan is the carving scan, so every cell the insert will touch is protected by its own hits.  Caveats.
+    Deskewed frames: the ray origin is the sensor at the frame's reference instant, while the true origins differ by the
+    motion within the sweep — end_margin has to cover that.  Grazing rays skim the cells of the surface they end on:
+    min_crossings and the hit protection are the guards.  None: nothing is carved, bit for bit.
     → (list of Poses, list of per-scan round lists)."""
     if live_indexed:
         if live_match is not None and not live_match:
@@ -413,7 +420,10 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
             finally:
                 if not live_match:
                     ndt_map.close()
-            voxel_map.insert_scan(registered if insert_filtered else scan, pose.R, pose.t)
+            inserted = registered if insert_filtered else scan
+            if carve is not None:
+                voxel_map.carve(inserted, pose.R, pose.t, **carve)
+            voxel_map.insert_scan(inserted, pose.R, pose.t)
         finally:
             if registered is not scan:
                 registered.close()
