@@ -294,6 +294,71 @@ int nos_scan_points(const nos_scan* scan, double* points_xyz_out);
  *   NOS_ERR_OUT_OF_MEMORY     the time stamps (8 B per entry of times) or the new scan do not fit */
 int nos_scan_deskew(nos_scan* scan, const double* times, size_t n_times, double reference_time,
                     const double twist[6], nos_scan** out_scan);
+/* Place recognition on the device: the Scan Context descriptor of a scan (Kim & Kim, IROS 2018) and a database of stored
+ * descriptors that is searched exhaustively — every stored place at every yaw — in one launch.
+ *
+ * Parameters.  n_rings 1 ... 64, n_sectors 1 ... 128, max_range finite and > 0, z_floor finite; anything else is
+ * NOS_ERR_INVALID_ARGUMENT before any device is touched.
+ *
+ * Descriptor of a scan: n_rings x n_sectors doubles, ring-major, desc[i * n_sectors + j].  Points are taken in the scan's
+ * own sensor frame (no pose; the stored order does not matter).  Operation by operation, in double:
+ *   used     a point (x, y, z) is used when x, y, z are all finite, z >= z_floor, and r = sqrt(x*x + y*y) < max_range
+ *            (x*x + y*y may be fused);
+ *   ring     i = min(int(floor(r * (n_rings / max_range))), n_rings - 1) — the quotient n_rings / max_range formed once;
+ *            a ring boundary belongs to the outer ring;
+ *   sector   a = atan2(y, x); if a < 0: a = a + 2 pi; j = int(floor(a * (n_sectors / (2 pi)))), and j = j - n_sectors when
+ *            that gives n_sectors (a rounded up to 2 pi).  A point with x == 0 && y == 0 goes to sector 0;
+ *   bin      max(z) over its points, then ONE subtraction per bin: value = max(z) - z_floor, so the value is one rounding
+ *            of a double the scan contains.  An empty bin holds 0.0;
+ *   n_used   the number of points that were used.
+ * The maximum is an integer maximum of an order-preserving key of z: the result is the same bits from run to run and
+ * for every order of the points.  An empty scan gives the all-zero descriptor and n_used = 0.
+ *
+ * Distance between a query q and a candidate c of the same parameters (R = n_rings, S = n_sectors):
+ *   norm     |a_j| = sqrt(sum_i a[i][j]^2), i ascending;
+ *   shift    for s = 0 ... S - 1:  d_s = (sum_j (1 - (sum_i q[i][j] * c[i][(j + s) mod S]) / (|q_j| * |c_(j+s)|))) / m
+ *            over the columns j, ascending, for which both |q_j| > 0 and |c_(j+s)| > 0; m is their number; i ascending;
+ *            d_s = 1.0 when m == 0;
+ *   result   d = min_s d_s and the smallest s that attains it.  d is not clamped (rounding can leave -1e-16).
+ *
+ * Sign of the yaw.  The descriptor q of a scan taken from a sensor yawed by +phi about z relative to the sensor of a
+ * stored scan c of the same place has q_j ~ c_(j+s) with s ~ phi * S / (2 pi): a point at azimuth a in the stored frame is
+ * at a - phi in the query's.  The rough pose of the query is therefore T_stored o Rz(2 pi s / S).
+ *
+ *   nos_scan_descriptor       the descriptor of a scan to the host, and n_used (may be NULL).
+ *   nos_place_db_create       an empty database of one parameter set; reserve: slots allocated up front (0: none).  The
+ *                             store grows by doubling with a device-to-device copy.
+ *   nos_place_db_add          appends a host descriptor (any doubles; ring-major); *index (may be NULL) = its position.
+ *   nos_place_db_add_scan     appends the descriptor of a scan without it visiting the host; n_used may be NULL.
+ *   nos_place_db_get          stored descriptor `index`, ring-major — the doubles that were added, bit for bit.
+ *   nos_place_db_search       n_queries host descriptors against entries first ... first + count - 1: distance_out and
+ *                             shift_out are [n_queries][count].  One launch, one host wait.  first + count > size is
+ *                             NOS_ERR_INVALID_ARGUMENT; count == 0 or n_queries == 0 succeeds and writes nothing.
+ *   nos_place_db_search_scan  the same for the descriptor of a scan, built and searched on the device: one host wait.
+ * A pair's distance and shift are a function of the two descriptors alone: the same bits whatever the number of queries,
+ * the window, the database's capacity, and whether the query came from the host or from a scan.
+ * Single-device contexts only (NOS_ERR_UNSUPPORTED); a scan of >= 2^32 - 1 points is NOS_ERR_UNSUPPORTED.  NULL arguments
+ * (n_used and index excepted) and a scan of another context than the database's are NOS_ERR_INVALID_ARGUMENT, rejected
+ * before any device is touched with nothing written.  nos_place_db_destroy(NULL) is NOS_OK; nos_place_db_size(NULL) is 0.
+ * The database must be destroyed before its context. */
+typedef struct nos_place_params {
+  int32_t n_rings;
+  int32_t n_sectors;
+  double max_range;
+  double z_floor;
+} nos_place_params;
+typedef struct nos_place_db nos_place_db;
+int nos_scan_descriptor(nos_scan* scan, const nos_place_params* params, double* desc_out, size_t* n_used);
+int nos_place_db_create(nos_ctx* ctx, const nos_place_params* params, size_t reserve, nos_place_db** out_db);
+int nos_place_db_destroy(nos_place_db* db);
+size_t nos_place_db_size(const nos_place_db* db);
+int nos_place_db_add(nos_place_db* db, const double* desc, size_t* index);
+int nos_place_db_add_scan(nos_place_db* db, nos_scan* scan, size_t* index, size_t* n_used);
+int nos_place_db_get(nos_place_db* db, size_t index, double* desc_out);
+int nos_place_db_search(nos_place_db* db, const double* queries, int32_t n_queries, size_t first, size_t count,
+                        double* distance_out /*[n_queries][count]*/, int32_t* shift_out /*[n_queries][count]*/);
+int nos_place_db_search_scan(nos_place_db* db, nos_scan* scan, size_t first, size_t count, double* distance_out,
+                             int32_t* shift_out, size_t* n_used);
 int nos_ndt_match(nos_ndt_map* map, nos_scan* scan, const double R[9], const double t[3],
                   int max_neighbors, int dtype, nos_dataset** out_ds, size_t* n_matches);
 /* Tail drop of the reference's solver classes for a matcher-written dataset.  The scalar 3-DoF class uses only the

@@ -30,7 +30,7 @@ C_ABI_SYMBOLS = (
     "nos_ndt_dataset_create_from_device", "nos_reproj_dataset_create_from_device",
     "nos_ndt_dataset_create_from_records", "nos_reproj_dataset_create_from_records",
     "nos_dataset_download", "nos_ndt_map_create", "nos_ndt_map_destroy", "nos_ndt_map_size", "nos_scan_create",
-    "nos_scan_destroy", "nos_scan_size", "nos_scan_sort_by_cell", "nos_scan_order", "nos_scan_filter", "nos_scan_points", "nos_scan_deskew", "nos_ndt_match", "nos_ndt_indexed_dataset_create", "nos_ndt_match_indexed", "nos_indexed_dataset_info", "nos_indexed_dataset_download", "nos_ndt_map_build", "nos_map_stats_size",
+    "nos_scan_destroy", "nos_scan_size", "nos_scan_sort_by_cell", "nos_scan_order", "nos_scan_filter", "nos_scan_points", "nos_scan_deskew", "nos_scan_descriptor", "nos_place_db_create", "nos_place_db_destroy", "nos_place_db_size", "nos_place_db_add", "nos_place_db_add_scan", "nos_place_db_get", "nos_place_db_search", "nos_place_db_search_scan", "nos_ndt_match", "nos_ndt_indexed_dataset_create", "nos_ndt_match_indexed", "nos_indexed_dataset_info", "nos_indexed_dataset_download", "nos_ndt_map_build", "nos_map_stats_size",
     "nos_map_stats_get", "nos_map_stats_get_eigen", "nos_map_stats_destroy",
     "nos_voxel_map_create", "nos_voxel_map_insert", "nos_voxel_map_insert_scan", "nos_voxel_map_info", "nos_voxel_map_snapshot",
     "nos_voxel_map_stats", "nos_voxel_map_match", "nos_voxel_map_match_indexed", "nos_voxel_map_prune", "nos_voxel_map_carve", "nos_voxel_map_memory", "nos_voxel_map_merge", "nos_voxel_map_match_map", "nos_voxel_map_destroy", "nos_dataset_drop_last_matches", "nos_pgo_create", "nos_pgo_destroy", "nos_pgo_num_unknowns",
@@ -102,6 +102,11 @@ class NosVoxelCarve(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_size_t), ("origin", ctypes.c_double * 3), ("end_margin", ctypes.c_double),
                 ("min_range", ctypes.c_double), ("max_range", ctypes.c_double), ("min_crossings", ctypes.c_uint32),
                 ("min_hits", ctypes.c_uint32), ("dry_run", ctypes.c_int)]
+
+
+class NosPlaceParams(ctypes.Structure):
+    _fields_ = [("n_rings", ctypes.c_int32), ("n_sectors", ctypes.c_int32), ("max_range", ctypes.c_double),
+                ("z_floor", ctypes.c_double)]
 
 
 class NosError(RuntimeError):
@@ -176,6 +181,18 @@ def _declare(lib):
     lib.nos_scan_filter.argtypes = [vp, ctypes.c_double, c_void_pp]
     lib.nos_scan_points.argtypes = [vp, dp]
     lib.nos_scan_deskew.argtypes = [vp, dp, sz, ctypes.c_double, dp, c_void_pp]
+    if hasattr(lib, "nos_scan_descriptor"):  # place recognition: absent from older builds loaded through NOS_HIP_LIB
+        pp, szp, i32p = ctypes.POINTER(NosPlaceParams), ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int32)
+        lib.nos_scan_descriptor.argtypes = [vp, pp, dp, szp]
+        lib.nos_place_db_create.argtypes = [vp, pp, sz, c_void_pp]
+        lib.nos_place_db_destroy.argtypes = [vp]
+        lib.nos_place_db_size.argtypes = [vp]
+        lib.nos_place_db_size.restype = sz
+        lib.nos_place_db_add.argtypes = [vp, dp, szp]
+        lib.nos_place_db_add_scan.argtypes = [vp, vp, szp, szp]
+        lib.nos_place_db_get.argtypes = [vp, sz, dp]
+        lib.nos_place_db_search.argtypes = [vp, dp, ctypes.c_int32, sz, sz, dp, i32p]
+        lib.nos_place_db_search_scan.argtypes = [vp, vp, sz, sz, dp, i32p, szp]
     lib.nos_ndt_match.argtypes = [vp, vp, dp, dp, i, i, c_void_pp, ctypes.POINTER(sz)]
     lib.nos_ndt_indexed_dataset_create.argtypes = [vp, sz, ctypes.POINTER(dp), i, ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)),
                                                    sz, dp, dp, i, i, c_void_pp]

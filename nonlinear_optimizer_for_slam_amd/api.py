@@ -1088,6 +1088,18 @@ class Scan:
         self._ctx._adopt(out)
         return out
 
+    def descriptor(self, n_rings=20, n_sectors=60, max_range=80.0, z_floor=-2.0):
+        """→ (desc [n_rings, n_sectors], n_used): the Scan Context descriptor of this scan in its own sensor frame
+        (nos_scan_descriptor, on the device; the rule: include/nos.h) — max(z) − z_floor per ring and sector
+        of the points with finite coordinates, z ≥ z_floor and horizontal range < max_range; n_used counts them."""
+        params = _lib.NosPlaceParams(int(n_rings), int(n_sectors), float(max_range), float(z_floor))
+        in_limits = 1 <= params.n_rings <= 64 and 1 <= params.n_sectors <= 128  # otherwise the call rejects and writes nothing
+        desc = np.zeros((params.n_rings, params.n_sectors) if in_limits else (1, 1), dtype=np.float64)
+        used = ctypes.c_size_t(0)
+        check(self._lib.nos_scan_descriptor(self._h, ctypes.byref(params), _dp(desc), ctypes.byref(used)),
+              "nos_scan_descriptor")
+        return desc, int(used.value)
+
     def points(self):
         """→ the points [n,3] in stored order (nos_scan_points; diagnostics and tests)."""
         out = np.zeros((len(self), 3), dtype=np.float64)
@@ -1110,6 +1122,89 @@ class Scan:
     def close(self):
         if self._h:
             self._lib.nos_scan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        # at interpreter shutdown the HIP runtime may already be gone: leave the handle to the OS
+        if sys is None or sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PlaceDatabase:
+    """Device-resident database of Scan Context descriptors of one parameter set (nos_place_db; the rule: include/nos.h,
+    DESIGN.md §27): add places as the trajectory grows, search every stored place at every yaw in one launch."""
+
+    def __init__(self, ctx, n_rings=20, n_sectors=60, max_range=80.0, z_floor=-2.0, reserve=0):
+        self._ctx = ctx
+        self._lib = ctx._lib
+        self._h = None
+        params = _lib.NosPlaceParams(int(n_rings), int(n_sectors), float(max_range), float(z_floor))
+        h = ctypes.c_void_p()
+        check(self._lib.nos_place_db_create(ctx.handle, ctypes.byref(params), int(reserve), ctypes.byref(h)),
+              "nos_place_db_create")
+        self._h = h
+        self.n_rings, self.n_sectors = params.n_rings, params.n_sectors
+        self.max_range, self.z_floor = params.max_range, params.z_floor
+        ctx._adopt(self)
+
+    def _host_descriptors(self, desc):
+        a = np.ascontiguousarray(desc, dtype=np.float64)
+        if a.ndim < 2 or a.shape[-2:] != (self.n_rings, self.n_sectors):
+            raise ValueError("expected descriptors of shape [..., %d, %d], got %r" % (self.n_rings, self.n_sectors, a.shape))
+        return a
+
+    def add(self, desc_or_scan):
+        """Append a place: a host descriptor [n_rings, n_sectors] (nos_place_db_add) or an api.Scan, whose descriptor is
+        built on the device and never leaves it (nos_place_db_add_scan).  → its index."""
+        index = ctypes.c_size_t(0)
+        if isinstance(desc_or_scan, Scan):
+            check(self._lib.nos_place_db_add_scan(self._h, desc_or_scan._h, ctypes.byref(index), None), "nos_place_db_add_scan")
+        else:
+            a = self._host_descriptors(desc_or_scan)
+            if a.ndim != 2:
+                raise ValueError("add takes one descriptor")
+            check(self._lib.nos_place_db_add(self._h, _dp(a), ctypes.byref(index)), "nos_place_db_add")
+        return int(index.value)
+
+    def __len__(self):
+        return int(self._lib.nos_place_db_size(self._h))
+
+    def get(self, index):
+        """→ stored descriptor `index`, [n_rings, n_sectors] (nos_place_db_get)."""
+        out = np.zeros((self.n_rings, self.n_sectors), dtype=np.float64)
+        check(self._lib.nos_place_db_get(self._h, int(index), _dp(out)), "nos_place_db_get")
+        return out
+
+    def search(self, queries_or_scan, first=0, count=None):
+        """Distance and best shift of every query against the stored places first … first + count − 1 (count=None: to the
+        end).  queries_or_scan: descriptors [Q, n_rings, n_sectors], one descriptor [n_rings, n_sectors], or an api.Scan
+        (its descriptor is built and searched on the device).  → (distance, shift), float64 / int32 of shape [Q, count], or
+        [count] for a single query.  The query sensor is yawed by about 2π · shift / n_sectors relative to the stored one."""
+        first = int(first)
+        count = max(len(self) - first, 0) if count is None else int(count)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        if isinstance(queries_or_scan, Scan):
+            dist = np.zeros(count, dtype=np.float64)
+            shift = np.zeros(count, dtype=np.int32)
+            check(self._lib.nos_place_db_search_scan(self._h, queries_or_scan._h, first, count, _dp(dist),
+                                                     shift.ctypes.data_as(i32p), None), "nos_place_db_search_scan")
+            return dist, shift
+        a = self._host_descriptors(queries_or_scan)
+        single = a.ndim == 2
+        q = a.reshape(-1, self.n_rings, self.n_sectors)
+        dist = np.zeros((q.shape[0], count), dtype=np.float64)
+        shift = np.zeros((q.shape[0], count), dtype=np.int32)
+        check(self._lib.nos_place_db_search(self._h, _dp(q), q.shape[0], first, count, _dp(dist), shift.ctypes.data_as(i32p)),
+              "nos_place_db_search")
+        return (dist[0], shift[0]) if single else (dist, shift)
+
+    def close(self):
+        if self._h:
+            self._lib.nos_place_db_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -333,12 +333,56 @@ def relocalize(ctx, ndt_map, scan, candidates, loss=("exponential", 1.0, 1.0), t
     return rows[best][0], info
 
 
+def loop_candidates(db, query, top_k=5, max_distance=None, exclude_last=0):
+    """Have I been here before, and roughly which way was I facing?  One exhaustive search of an api.PlaceDatabase
+    (every stored place at every yaw) → the best places as a list of (index, distance, yaw), sorted by
+    distance, then index; at most top_k of them (None: all), only those with distance <= max_distance when that is given.
+    query: an api.Scan (its descriptor never leaves the device) or one host descriptor [n_rings, n_sectors].
+    yaw = 2π · shift / n_sectors wrapped to (−π, π]: the yaw of the query's sensor relative to the stored scan's, so the
+    rough pose of the query is T_stored ∘ Rz(yaw) (candidate_poses).
+    exclude_last: the newest entries are left out (the search window is narrowed, they are not even read) — a place does
+    not match the frames just before it."""
+    count = max(len(db) - max(int(exclude_last), 0), 0)
+    if count == 0:
+        return []
+    distance, shift = db.search(query, 0, count)
+    distance, shift = np.asarray(distance).reshape(-1, count), np.asarray(shift).reshape(-1, count)
+    if distance.shape[0] != 1:
+        raise ValueError("loop_candidates takes one query")
+    distance, shift = distance[0], shift[0]
+    order = sorted(range(count), key=lambda i: (distance[i], i))
+    if max_distance is not None:
+        order = [i for i in order if distance[i] <= max_distance]
+    if top_k is not None:
+        order = order[:max(int(top_k), 0)]
+    out = []
+    for i in order:
+        yaw = 2.0 * math.pi * int(shift[i]) / db.n_sectors
+        if yaw > math.pi:
+            yaw -= 2.0 * math.pi
+        out.append((i, float(distance[i]), yaw))
+    return out
+
+
+def candidate_poses(candidates, stored_poses):
+    """loop_candidates' rows → the rough poses of the query as relocalize takes them: for (index, distance, yaw) the Pose
+    R = R_stored · Rz(yaw), t = t_stored, with (R_stored, t_stored) = stored_poses[index] (a Pose or an (R, t) pair)."""
+    out = []
+    for index, _, yaw in candidates:
+        stored = stored_poses[index]
+        R, t = (stored.R, stored.t) if hasattr(stored, "R") else stored
+        c, s = math.cos(yaw), math.sin(yaw)
+        Rz = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+        out.append(Pose(np.asarray(R, dtype=np.float64).reshape(3, 3) @ Rz, np.asarray(t, dtype=np.float64).reshape(3)))
+    return out
+
+
 _ONE_LAUNCH_KWARGS = ("loss", "options", "max_outer_iterations", "dof", "dtype", "keep_multiple")
 
 
 def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, max_voxel_age=None, filter_voxel_size=None,
              insert_filtered=False, live_match=None, one_launch=False, live_indexed=False, sweep_times=None, sweep_reference=1.0,
-             carve=None, **scan_to_map_kwargs):
+             carve=None, place_db=None, **scan_to_map_kwargs):
     """Scan-to-map odometry over a growing map (api.VoxelMap): for each scan, snapshot the store → scan_to_map from the
     previous scan's pose → insert the scan at the pose found (VoxelMap.insert_scan, warped on the device).  The harness's
     sequence UpdateNdtMap → OptimizePose → UpdateNdtMap (MDM/tests/simple_optimization_test.cc:236-281, 474-503) with the
@@ -376,6 +420,10 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
     Deskewed frames: the ray origin is the sensor at the frame's reference instant, while the true origins differ by the
     motion within the sweep — end_margin has to cover that.  Grazing rays skim the cells of the surface they end on:
     min_crossings and the hit protection are the guards.  None: nothing is carved, bit for bit.
+    place_db: an api.PlaceDatabase — the Scan Context descriptor of every frame that was registered is appended to it (on
+    the device), built from the scan the frame registers, after the deskew and before the filter, and added once the
+    registration has succeeded: an empty database's index of a frame is then its index in the returned poses, ready for
+    loop_candidates.  None: nothing is added, bit for bit.
     → (list of Poses, list of per-scan round lists)."""
     if live_indexed:
         if live_match is not None and not live_match:
@@ -424,6 +472,8 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
             if carve is not None:
                 voxel_map.carve(inserted, pose.R, pose.t, **carve)
             voxel_map.insert_scan(inserted, pose.R, pose.t)
+            if place_db is not None:
+                place_db.add(scan)
         finally:
             if registered is not scan:
                 registered.close()
