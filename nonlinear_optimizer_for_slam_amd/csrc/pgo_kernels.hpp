@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "assemble_kernels.hpp"
+#include "pgo_layout.hpp"  // packing constants of the block lists (kPgoNoSlot), shared with the host-side builder
 
 namespace nos {
 
@@ -339,7 +340,7 @@ __device__ __forceinline__ void pgo_sum_rows(const double* __restrict__ partials
 struct PgoTail {
   double* partials;      // [gridDim.x][width]
   unsigned int* ticket;  // one word per tail, zero between launches
-  double* scalars;       // the device-resident CG scalars (layout at pgo_cg_alpha_kernel)
+  double* scalars;       // the device-resident CG scalars (layout at pgo_cg_update_dev_kernel)
 };
 
 template <int WIDTH>
@@ -367,7 +368,7 @@ __device__ __forceinline__ bool pgo_tail_is_last(const PgoTail& T, unsigned int*
   return *flag != 0u;
 }
 
-// CG scalar updates (the bodies of pgo_cg_alpha_kernel / pgo_cg_beta_kernel, shared with the in-launch tails).
+// CG scalar updates, run by thread 0 of the workgroup that finishes an in-launch tail (scalar layout at pgo_cg_update_dev_kernel).
 __device__ __forceinline__ void pgo_cg_alpha(double* __restrict__ s) {
   const double pap = s[0];
   if (s[7] != 0.0 || !(pap > 0.0) || !(pap <= 1.79769313486231570e308)) {
@@ -495,18 +496,6 @@ __global__ __launch_bounds__(256) void pgo_matvec_pose_kernel(PgoView G, const d
   if (threadIdx.x == 0) dot_partials[blockIdx.x] = bs;
 }
 
-// Switch rows alone; block partials of xs.ys (appended after the pose blocks' partials by the caller).
-__global__ __launch_bounds__(256) void pgo_matvec_switch_kernel(PgoView G, const double* __restrict__ h_s, double lambda,
-                                                                const double* __restrict__ x,
-                                                                const double* __restrict__ xs,
-                                                                double* __restrict__ ys,
-                                                                double* __restrict__ dot_partials) {
-  const double xy = pgo_matvec_switch_row(G, h_s, lambda, x, xs, ys, blockIdx.x * 256 + threadIdx.x);
-  __shared__ double lds[4];
-  const double bs = pgo_block_sum256(xy, lds);
-  if (threadIdx.x == 0) dot_partials[blockIdx.x] = bs;
-}
-
 // The product of one PCG iteration in ONE launch: workgroups [0, pose_blocks) take the pose rows, the following ones the
 // switch rows (only launched when a switch is free), and the workgroup that finishes last adds the partials of p.Ap up
 // and computes the step length (pgo_cg_alpha) — what used to be product [+ switch product] + sum + alpha kernels.
@@ -565,7 +554,6 @@ struct PgoBlockView {
   uint32_t halo_cap;            // LDS room for halo poses per workgroup (>= halo poses of any block)
   uint32_t slot_cap;            // LDS contribution slots per workgroup (>= adjacency entries of any block)
 };
-constexpr uint32_t kPgoNoSlot = 0xFFFFu;
 
 // Persistent workgroups: the grid is sized to what is resident (LDS-limited), every workgroup walks pose blocks
 // blockIdx.x, + gridDim.x, … and publishes ONE partial of x.y and draws ONE ticket at its end.  Per block:
@@ -1059,14 +1047,6 @@ __global__ __launch_bounds__(256) void pgo_cg_direction_kernel(size_t n, double 
 // Device-resident CG scalars (no host round trip inside a PCG iteration).  s[0], s[1] receive the sums of the partials
 // kernels as before; s[3] = |r|^2 of the latest iterate, s[4] = r·z of the current direction, s[5] = alpha, s[6] = beta,
 // s[7] = 1 after a breakdown (p·Ap <= 0 or not finite: the iterate is kept from then on).
-__global__ void pgo_cg_alpha_kernel(double* __restrict__ s) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  pgo_cg_alpha(s);
-}
-__global__ void pgo_cg_beta_kernel(double* __restrict__ s) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  pgo_cg_beta(s);
-}
 __global__ __launch_bounds__(256) void pgo_cg_update_dev_kernel(size_t n, const double* __restrict__ s,
                                                                 const double* __restrict__ p, const double* __restrict__ q,
                                                                 double* __restrict__ x, double* __restrict__ r) {

@@ -156,6 +156,63 @@ def test_large_block_local_product_equals_owner_computes_product(ctx, with_switc
     np.testing.assert_allclose(y[1], y[0], rtol=0, atol=1e-13 * np.max(np.abs(y[0])))
 
 
+@functools.lru_cache(maxsize=None)
+def _trajectory(n, seed):
+    """→ (graph dict, oracle graph, H), built once."""
+    d = op.random_graph(n, 3, seed=seed)
+    cpu = op.Graph(d["init"], d["ref"], d["qry"], d["meas"], None, None, d["fixed"])
+    return d, cpu, cpu.linearize()[0]
+
+
+def _assert_product(gpu, d, cpu, H, rng, lam=1e-3):
+    x = _masked(rng, d, None)
+    want = cpu.damped(H, lam) @ x
+    np.testing.assert_allclose(gpu.matvec(lam, x), want, rtol=0, atol=1e-11 * np.max(np.abs(want)))
+
+
+@pytest.mark.gpu
+def test_two_graphs_alive_at_once_each_with_its_own_lds(ctx):
+    """The LDS a launch of the block-local product may have is an attribute of the KERNEL, set before every launch that
+    needs more than 48 KiB: two graphs that need different amounts take turns without disturbing each other."""
+    from nonlinear_optimizer_for_slam_amd import pgo
+    large, _, _, cpu_l, H_l = _graph("large_but_inside", False)[:5]
+    small, cpu_s, H_s = _trajectory(BLOCK * 9 + 37, 12)
+    lds_l = _lds_bytes(_recount(768, large["ref"], large["qry"]))[2]
+    lds_s = _lds_bytes(_recount(BLOCK * 9 + 37, small["ref"], small["qry"]))[2]
+    assert lds_l == 122112 and lds_l > 48 * 1024 and lds_s > 48 * 1024 and lds_l != lds_s
+    rng = np.random.default_rng(5)
+    g_l = pgo.PoseGraph(ctx, large["init"], large["ref"], large["qry"], large["meas"], None, None, large["fixed"])
+    assert g_l.layout_info()["block_poses"] == BLOCK
+    g_l.linearize()
+    _assert_product(g_l, large, cpu_l, H_l, rng)
+    g_s = pgo.PoseGraph(ctx, small["init"], small["ref"], small["qry"], small["meas"], None, None, small["fixed"])
+    assert g_s.layout_info()["block_poses"] == BLOCK
+    g_s.linearize()
+    _assert_product(g_s, small, cpu_s, H_s, rng)
+    _assert_product(g_l, large, cpu_l, H_l, rng)
+    _assert_product(g_s, small, cpu_s, H_s, rng)
+    g_l.close()
+    g_s.close()
+
+
+@pytest.mark.gpu
+def test_create_and_destroy_with_both_product_forms(ctx):
+    """Every buffer of a graph is freed through the list it was recorded in, once: 50 graphs with the block lists, 50
+    without, then one more that still computes the right product."""
+    from nonlinear_optimizer_for_slam_amd import pgo
+    d, cpu, H = _trajectory(300, 4)
+    for block in (1, 0):
+        for _ in range(50):
+            with ctx.options(pgo_block=block):
+                g = pgo.PoseGraph(ctx, d["init"], d["ref"], d["qry"], d["meas"], None, None, d["fixed"])
+            assert g.layout_info()["block_poses"] == (BLOCK if block else 0)
+            g.close()
+    g = pgo.PoseGraph(ctx, d["init"], d["ref"], d["qry"], d["meas"], None, None, d["fixed"])
+    g.linearize()
+    _assert_product(g, d, cpu, H, np.random.default_rng(6))
+    g.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["large_but_inside", "trajectory"])
 def test_layout_info_against_a_recount(ctx, name):

@@ -11,6 +11,13 @@ print("generator: %.2f s, %d poses, %d constraints" % (t1 - t0, n, d["ref"].size
 ctx = Context((0,))
 t0 = time.perf_counter(); g = pgo.PoseGraph(ctx, d["init"], d["ref"], d["qry"], d["meas"], None, None, d["fixed"]); t1 = time.perf_counter()
 print("nos_pgo_create (SoA + adjacency + upload): %.1f ms" % (1e3 * (t1 - t0)), flush=True)
+if "create" in sys.argv[2:]:  # python tools/measure_pgo.py N create: the wall time of nos_pgo_create alone, three more times
+    for rep in range(3):
+        g.close()
+        t0 = time.perf_counter(); g = pgo.PoseGraph(ctx, d["init"], d["ref"], d["qry"], d["meas"], None, None, d["fixed"]); t1 = time.perf_counter()
+        print("nos_pgo_create again: %.1f ms (layout %s)" % (1e3 * (t1 - t0), g.layout_info()), flush=True)
+    g.close()
+    sys.exit(0)
 for rep in range(3):
     t0 = time.perf_counter(); c, gn = g.linearize(); dt = time.perf_counter() - t0
     print("linearize: %.3f ms  cost %.6g |g| %.4g  (%.1f M constraint evaluations/s)" % (1e3 * dt, c, gn, 2 * d["ref"].size / dt / 1e6), flush=True)
