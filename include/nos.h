@@ -210,7 +210,9 @@ int nos_dataset_download(nos_dataset* ds, double* const planes[]);
  * Replaces MatchPointCloud of the reference's test harness
  * (MDM/tests/simple_optimization_test.cc:296-342): FLANN KDTreeSingleIndex over the valid
  * voxel means + radiusSearch(radius = 1.0 on L2_Simple, i.e. squared distance, max_neighbors
- * = 2) becomes a uniform-grid lookup on the GPU.  nos_ndt_match writes {local point, mean,
+ * = 2) becomes a uniform-grid lookup on the GPU: cell edge sqrt(search_radius_sq) (1 + 2^-30), 27
+ * cells per point — the slack makes the search complete under rounding at a cell face, so every
+ * valid mean with squared distance < search_radius_sq is a candidate.  nos_ndt_match writes {local point, mean,
  * sqrt-information} for the (up to) two nearest voxels of every scan point straight into a
  * device dataset: slot 2*i + k holds the k-th nearest voxel of point i, an absent neighbour is
  * an all-zero record (contributes nothing).  The dataset is then used with nos_ndt6_accumulate /

@@ -6,8 +6,9 @@
 // voxel means within the search radius (FLANN radiusSearch on L2_Simple, i.e. SQUARED distance
 // < radius, max_neighbors = 2, sorted); each match becomes one correspondence
 // {local point, mean, sqrt-information}.  The k-d tree is replaced by a uniform grid with cell
-// edge = sqrt(radius): all candidates of a point lie in its 27-cell neighbourhood.  The voxel
-// records are stored in cell order so one cell's candidates are contiguous.
+// edge = sqrt(radius) (1 + 2^-30): all candidates of a point lie in its 27-cell neighbourhood — the
+// slack covers the rounding of x * inv_cell, see map_create_device.  The voxel records are stored
+// in cell order so one cell's candidates are contiguous.
 //
 // Output goes straight into the tiled-SoA dataset the assemble kernels read: two slots per point
 // (slot 2i + k = k-th nearest), an absent neighbour is an all-zero record, which contributes
@@ -39,7 +40,7 @@ struct MapView {
   const uint32_t* cell_start;
   const uint32_t* cell_count;
   uint32_t table_mask;       // table size - 1 (power of two)
-  double inv_cell;           // 1 / cell edge
+  double inv_cell;           // 1 / cell edge; the edge is sqrt(radius_sq) (1 + 2^-30), set by map_create_device alone
   double radius_sq;
   // Dense form of the same grid (set when the map's bounding box is small enough, which it is for every
   // scene the reference handles): cells in lexicographic (x, y, z) order — the order the voxel records are

@@ -127,7 +127,15 @@ __global__ __launch_bounds__(256) void map_cell_tables_kernel(const uint64_t* __
 // nos_ndt_map_create's uploaded copies, the build's (nos_mapbuild.hip) and the store's own (nos_voxelmap.hip).
 int nosd::map_create_device(nos_ctx* ctx, size_t n_voxels, const double* d_means, const double* d_S, const unsigned char* d_valid,
                             double search_radius_sq, nos_ndt_map** out_map) {
-  const double inv_cell = 1.0 / std::sqrt(search_radius_sq);
+  // The cell edge is sqrt(radius_sq) widened by kCellEdgeSlack = 2^-30, not sqrt(radius_sq) itself: the 27-cell search of
+  // find_two_nearest is complete only if a pair that passes `dist < radius_sq` lies in cells at most one apart, and with
+  // cell = floor(fl(x inv_cell)) an edge of exactly the radius loses that to rounding (a query an ulp below a face and a
+  // mean an ulp above the next one are less than the radius apart and two cells apart).  With the slack: a passing pair
+  // has |q - m| <= sqrt(radius_sq) (1 + 2^-50) per axis, so the exact quotients differ by less than 1 - 2^-31; a cell
+  // coordinate is below 2^21 in magnitude (kCellLimit), so each product rounds by at most 2^-33 (the rounding of inv_cell
+  // itself scales both alike); the rounded products differ by less than 1, and their floors by at most 1.  
+  constexpr double kCellEdgeSlack = 1.0 / double(1 << 30);
+  const double inv_cell = 1.0 / (std::sqrt(search_radius_sq) * (1.0 + kCellEdgeSlack));
   DeviceSlot& slot = ctx->slots[0];
   hipStream_t st = slot.stream;
   const uint32_t V = uint32_t(n_voxels);

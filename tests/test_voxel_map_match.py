@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle_scene as scene
-from tests import helpers
+from tests import helpers, matcher_edge_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -140,10 +140,7 @@ def test_a_live_match_equals_the_snapshot_route_through_the_life_of_a_store(ctx,
 
 # ------------------------------------------------------------------------------ 2. exact inputs
 
-def _voxel_points(mu, spread):
-    """eight points mu + (+-sx, +-sy, +-sz): count 8, every sum exact, mean = mu exactly"""
-    s = np.array([[a, b, c] for a in (-1, 1) for b in (-1, 1) for c in (-1, 1)], dtype=np.float64)
-    return np.asarray(mu, dtype=np.float64) + s * np.asarray(spread, dtype=np.float64)
+_voxel_points = matcher_edge_inputs.voxel_points  # shared with test_matcher_edges_gpu.py: the exact 8-point voxel
 
 
 def _brute(means, valid, q, stable):
