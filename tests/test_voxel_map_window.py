@@ -14,151 +14,22 @@ import pytest
 
 from oracle import oracle_scene as scene
 from tests import helpers
+from tests.voxel_store_model import (KEYS, Model, _assert_is_model, _box_bounds, _box_keep, _cells_of, _pack, _pow2_at_least,
+                                      _same_bits)
 
 pytestmark = pytest.mark.gpu
 
 LOSS = ("exponential", 1.0, 1.0)
-KEYS = ("cells", "counts", "valid", "means", "sqrt_infos")
-LIM = 1 << 20
-
-
-def _same_bits(a, b, keys=KEYS):
-    for key in keys:
-        assert np.array_equal(a[key], b[key]), key
 
 
 def _take(stats, mask):
     return {k: stats[k][mask] for k in KEYS}
 
 
-def _pack(cells):
-    c = cells.astype(np.int64) + LIM
-    return (c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2]
-
-
-def _cells_of(points, res):
-    return np.floor(points * (1.0 / res)).astype(np.int64)  # the store's own factor: one multiply, then floor
-
-
-def _box_bounds(center, half, res):
-    """The documented rule: floor((c -+ h) * inv_res) in double, clamped to the addressable cells."""
-    inv_res = 1.0 / res
-    center, half = np.asarray(center, dtype=np.float64), np.broadcast_to(np.asarray(half, dtype=np.float64), (3,))
-    lo = np.clip(np.floor((center - half) * inv_res), -LIM, LIM).astype(np.int64)
-    hi = np.clip(np.floor((center + half) * inv_res), -LIM - 1, LIM - 1).astype(np.int64)
-    return lo, hi
-
-
-def _box_keep(cells, center, half, res):
-    lo, hi = _box_bounds(center, half, res)
-    return np.all((cells >= lo) & (cells <= hi), axis=1)
-
-
 def _exact(rng, lo, hi, n):
     pts = rng.integers(np.asarray(lo) * 1024, np.asarray(hi) * 1024, size=(n, 3)).astype(np.float64) / 1024.0
     assert np.max(np.abs(pts)) <= 64 and np.array_equal(pts * 1024, np.round(pts * 1024))
     return pts
-
-
-class Model:
-    """cell → (count, nine sums, stamp), in slot order; every point ever inserted is kept with its insert's epoch, and a
-    point belongs to a live voxel iff its cell is live and it arrived at or after that voxel's birth."""
-
-    def __init__(self, res):
-        self.res, self.epoch = res, 0
-        self.slot = {}  # packed key → slot
-        self.cells = np.zeros((0, 3), dtype=np.int64)
-        self.counts = np.zeros(0, dtype=np.int64)
-        self.sums = np.zeros((0, 9))
-        self.stamp = np.zeros(0, dtype=np.int64)
-        self.birth = np.zeros(0, dtype=np.int64)
-        self.history = []  # (epoch, points, packed keys)
-
-    def insert(self, pts):
-        if pts.shape[0] == 0:
-            return 0
-        self.epoch += 1
-        cells = _cells_of(pts, self.res)
-        keys = _pack(cells)
-        self.history.append((self.epoch, pts, keys))
-        order = np.argsort(keys, kind="stable")
-        uniq, first, n = np.unique(keys[order], return_index=True, return_counts=True)
-        p = pts[order]
-        terms = np.stack([p[:, 0], p[:, 1], p[:, 2], p[:, 0] * p[:, 0], p[:, 0] * p[:, 1], p[:, 0] * p[:, 2],
-                          p[:, 1] * p[:, 1], p[:, 1] * p[:, 2], p[:, 2] * p[:, 2]], axis=1)
-        seg = np.add.reduceat(terms, first, axis=0)
-        new = np.array([u for u in range(uniq.size) if int(uniq[u]) not in self.slot], dtype=np.int64)  # ascending cell
-        V = self.cells.shape[0]
-        for r, u in enumerate(new):
-            self.slot[int(uniq[u])] = V + r
-        self.cells = np.concatenate([self.cells, cells[order][first][new]])
-        self.counts = np.concatenate([self.counts, np.zeros(len(new), dtype=np.int64)])
-        self.sums = np.concatenate([self.sums, np.zeros((len(new), 9))])
-        self.stamp = np.concatenate([self.stamp, np.zeros(len(new), dtype=np.int64)])
-        self.birth = np.concatenate([self.birth, np.full(len(new), self.epoch, dtype=np.int64)])
-        slots = np.array([self.slot[int(k)] for k in uniq], dtype=np.int64)
-        self.counts[slots] += n
-        self.sums[slots] += seg
-        self.stamp[slots] = self.epoch
-        return uniq.size
-
-    def keep_mask(self, center=None, half_extent=None, max_age=None):
-        keep = np.ones(self.cells.shape[0], dtype=bool)
-        if center is not None:
-            keep &= _box_keep(self.cells, center, half_extent, self.res)
-        if max_age is not None:
-            keep &= (self.epoch - self.stamp) <= max_age
-        return keep
-
-    def prune(self, center=None, half_extent=None, max_age=None):
-        keep = self.keep_mask(center, half_extent, max_age)
-        self.cells, self.counts, self.sums = self.cells[keep], self.counts[keep], self.sums[keep]
-        self.stamp, self.birth = self.stamp[keep], self.birth[keep]
-        self.slot = {int(k): s for s, k in enumerate(_pack(self.cells))}
-        return int((~keep).sum())
-
-    def live_points(self):
-        keys_live = _pack(self.cells)
-        order = np.argsort(keys_live)
-        out = []
-        for epoch, pts, keys in self.history:
-            pos = np.searchsorted(keys_live[order], keys)
-            pos = np.minimum(pos, max(keys_live.size - 1, 0))
-            hit = keys_live[order][pos] == keys if keys_live.size else np.zeros(keys.size, dtype=bool)
-            hit &= self.birth[order][pos] <= epoch if keys_live.size else hit
-            out.append(pts[hit])
-        return np.concatenate(out)
-
-    def expected(self, ctx, proper=True):
-        """The model's live voxels in slot order with the statistics of a one-shot build over their points (exact inputs)."""
-        from nonlinear_optimizer_for_slam_amd import api
-        pts = self.live_points()
-        assert pts.shape[0] == int(self.counts.sum())
-        gm, want = api.NdtMap.build(ctx, pts, self.res, 1.0, proper_sqrt_information=proper)
-        gm.close()
-        keys = _pack(want["cells"])
-        assert np.all(np.diff(keys) > 0) and keys.size == self.cells.shape[0]
-        at = np.searchsorted(keys, _pack(self.cells))
-        want = {k: want[k][at] for k in KEYS}
-        assert np.array_equal(want["cells"], self.cells) and np.array_equal(want["counts"], self.counts)
-        ok = want["valid"]  # a voxel below five points gets no mean from the finish
-        np.testing.assert_allclose(want["means"][ok], (self.sums[:, :3] / self.counts[:, None])[ok], rtol=0, atol=1e-12)
-        return want
-
-
-def _assert_is_model(ctx, vm, model, proper=True):
-    want = model.expected(ctx, proper)
-    _same_bits(vm.stats(), want)
-    assert len(vm) == model.cells.shape[0] and vm.n_points == int(model.counts.sum())
-    assert vm.n_valid == int(want["valid"].sum())
-    assert vm.memory()["epoch"] == model.epoch
-
-
-def _pow2_at_least(n, floor=16):
-    c = floor
-    while c < n:
-        c *= 2
-    return c
 
 
 # ------------------------------------------------------------------------------ 1. a prune removes the rule's voxels
