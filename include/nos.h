@@ -667,6 +667,78 @@ int nos_voxel_map_merge(nos_voxel_map* dst, const nos_voxel_map* src, const doub
  * failure left undefined. */
 int nos_voxel_map_match_map(nos_voxel_map* target, nos_voxel_map* source, const double R[9], const double t[3],
                             int max_neighbors, int dtype, nos_dataset** out_ds, size_t* n_matches);
+/* ---- a store's state: export, restore, page voxels out and in ----
+ * A voxel IS its cell, its count, its nine sums about the cell corner and its stamp; mean, sqrt-information and validity
+ * are a pure function of (sums, count, cell, flags, resolution) — the one per-voxel finish every kernel shares.  So the
+ * state below is all that has to leave the device for a store to outlive its process, or for a voxel a prune removes to
+ * come back later, and both contracts are bit for bit: no tolerance anywhere.
+ *
+ * nos_voxel_map_export: a host-side copy of the store's voxels (all of them, or one half of the partition a prune would
+ * make), a nos_voxel_state, handled like a nos_map_stats: read with nos_voxel_state_size / _info / _get, free with
+ * nos_voxel_state_destroy; it is independent of the store afterwards.
+ *   select == NULL: every voxel (side is still checked).  Otherwise `select` is read exactly as nos_voxel_map_prune reads
+ *   it — the same host-computed box bounds, the same age test against the store's epoch, the same validation and
+ *   statuses — and side picks the half: NOS_STATE_KEPT the voxels that prune would keep, NOS_STATE_REMOVED the ones it
+ *   would remove.  The two halves are disjoint and together are the store.
+ *   The selected voxels come out in voxel-id order; KEPT is, entry for entry, what an export of everything gives after
+ *   that prune.  An empty selection (or an empty store) gives a state of size 0.
+ *   The store is not modified: nos_voxel_map_memory, the voxels, epoch, generation and the stamps stay as they were.
+ *   Work: with select == NULL four copies of n_voxels entries and one host wait, nothing launched; with a selection a
+ *   prune's keep flags and scan, one gather kernel into arena memory, the copies, and two host waits (how many, then the
+ *   data); nothing is allocated or launched in proportion to anything but n_voxels.
+ *   Rejected before anything runs, *out_state unwritten: NOS_ERR_INVALID_ARGUMENT for map or out_state NULL, a side
+ *   outside 0-1 and everything nos_voxel_map_prune rejects in `select`; NOS_ERR_UNSUPPORTED for a multi-device context;
+ *   NOS_ERR_HIP for a store an earlier failure left undefined.
+ * nos_voxel_state_info (any pointer may be NULL): resolution, search radius, flags and epoch of the store at the export;
+ *   n_points = the points of the voxels in the state.
+ * nos_voxel_state_get (any pointer may be NULL): cells [n][3], counts [n], sums [n][9] = sx sy sz | mxx mxy mxz myy myz mzz
+ *   about the corner cell * voxel_resolution (the store's own numbers, not re-derived), stamps [n] (low 32 bits of the
+ *   epoch of the last insert that touched the voxel). */
+typedef struct nos_voxel_state nos_voxel_state;
+#define NOS_STATE_KEPT    0   /* the voxels a prune with `select` would keep   */
+#define NOS_STATE_REMOVED 1   /* the voxels it would remove                    */
+int nos_voxel_map_export(nos_voxel_map* map, const nos_voxel_prune* select /* NULL: every voxel */, int side,
+                         nos_voxel_state** out_state);
+size_t nos_voxel_state_size(const nos_voxel_state* state);
+int nos_voxel_state_info(const nos_voxel_state* state, double* voxel_resolution, double* search_radius_sq, int* flags,
+                         unsigned long long* epoch, unsigned long long* n_points);
+int nos_voxel_state_get(const nos_voxel_state* state, int64_t* cells_xyz, uint32_t* counts, double* sums, uint32_t* stamps);
+int nos_voxel_state_destroy(nos_voxel_state* state);
+/* nos_voxel_map_import: n voxels given as cells [n][3], counts [n], sums [n][9] (about the corner of their cell, at
+ * voxel_resolution) and, for a restore, stamps [n] go into the store.  Counts and sums are taken as given, with no
+ * arithmetic on them; moments that belong to no point set get whatever the per-voxel finish makes of them, never a fault.
+ *   NOS_IMPORT_RESTORE, into a store that holds no voxel: voxel i of the arrays becomes voxel id i with the count and the
+ *   nine sums as given and stamp stamps[i] (stamps == NULL: uint32(epoch) for every voxel); the store's epoch becomes
+ *   `epoch`; mean, sqrt-information and validity are the per-voxel finish with the STORE's flags and resolution; the key ->
+ *   slot table, n_valid and n_points follow.  The capacity doubles from the store's current one until n fits.
+ *   Consequence: a store restored from nos_voxel_map_export(map, NULL, ...) of a store with the same resolution and flags
+ *   cannot be told from it by any entry point — nos_voxel_map_stats bit for bit, the ids, the epoch, and the results of
+ *   every later call (inserts, age prunes, carves, merges, matches, scores) — except by capacity and generation
+ *   (nos_voxel_map_memory), on which results never depend.  n == 0 only sets the epoch.
+ *   NOS_IMPORT_ADD, into any store: the state is ONE batch, exactly as the runs of an insert are.  A cell the store holds
+ *   gets count += n and sums = sums + s (the store's first, as a merge adds); cells it does not hold are appended in
+ *   ascending cell order; the epoch advances by one and every touched voxel is stamped with it; n_points grows by the
+ *   state's.  stamps and epoch are ignored.  n == 0 is a no-op that leaves the epoch alone.
+ *   Consequence: a voxel that was exported and removed comes back, when its cell is absent, with the same count and sums
+ *   and therefore the same mean, sqrt-information and validity, bit for bit (its id and stamp are new).
+ * *n_touched (optional) = n.  Rejected with the store and *n_touched unwritten; the checks that need no device come
+ * first, and a repeated cell is found on the device before anything of the store is written:
+ *   NOS_ERR_INVALID_ARGUMENT  map NULL; an unknown mode; cells_xyz, counts or sums NULL with n > 0; voxel_resolution not
+ *                             equal, bit for bit, to the store's (the sums are about the corner cell * resolution); a
+ *                             count of 0; a non-finite sum; the same cell twice (the message names one such cell);
+ *                             NOS_IMPORT_RESTORE into a store that holds a voxel;
+ *   NOS_ERR_UNSUPPORTED       a multi-device context; more than 2^30 voxels; a cell outside +-2^20 per axis;
+ *                             NOS_IMPORT_ADD that would take a voxel past 2^32 - 1 points (the message names the voxel of
+ *                             the state);
+ *   NOS_ERR_HIP               a store an earlier failure left undefined.
+ * A restore fills a fresh device block and adopts it only when nothing failed: a failure half-way leaves the store
+ * exactly as it was.  Work: the copies of the arrays and one kernel with one lane per voxel (restore, one host wait); a
+ * sort of the n keys, one kernel with one lane per voxel and the back half of an insert (add, two host waits). */
+#define NOS_IMPORT_RESTORE 0
+#define NOS_IMPORT_ADD     1
+int nos_voxel_map_import(nos_voxel_map* map, int mode, double voxel_resolution, size_t n, const int64_t* cells_xyz,
+                         const uint32_t* counts, const double* sums, const uint32_t* stamps /* may be NULL */,
+                         unsigned long long epoch, size_t* n_touched);
 int nos_voxel_map_destroy(nos_voxel_map* map);
 
 /* ---- the hot path -------------------------------------------------------------

@@ -802,7 +802,9 @@ class VoxelMap:
     Voxel ids (the order of stats(), the matcher's tie-break) follow the sequence of batches: batch of first appearance,
     then ascending cell.  proper_sqrt_information as in NdtMap.build; capacity (voxels) only avoids early growth.
     prune() removes voxels by a box and / or by age (a sliding window) and renumbers the survivors by their rank;
-    carve() removes, the same way, the voxels a scan's rays pass through (line of sight)."""
+    carve() removes, the same way, the voxels a scan's rays pass through (line of sight).
+    export() copies the state — cells, counts, the nine sums, stamps — to the host, whole or by a prune's rule; restore()
+    makes an empty store that state again, bit for bit, add() takes it as one more batch; save() / load() keep it in a file."""
 
     def __init__(self, ctx, voxel_resolution=1.0, search_radius_sq=1.0, proper_sqrt_information=True, capacity=0,
                  flags=None):
@@ -927,15 +929,13 @@ class VoxelMap:
         finally:
             self._lib.nos_map_stats_destroy(hs)
 
-    def prune(self, center=None, half_extent=None, max_age=None):
-        """Sliding window (nos_voxel_map_prune) → number of voxels removed.  center [3] with half_extent ([3], or a scalar
-        for a cube): keep the voxels whose cell meets the closed box center ± half_extent.  max_age: keep the voxels an
-        insert touched within the last max_age inserts (0 = the last insert only).  Both: a voxel must pass both.  The
-        survivors keep their order and are renumbered by rank; the store may shrink."""
+    @staticmethod
+    def _keep_rule(who, center, half_extent, max_age):
+        """→ the nos_voxel_prune that prune() and export() hand down: a box, an age, or both."""
         if (center is None) != (half_extent is None):
             raise ValueError("center and half_extent go together")
         if center is None and max_age is None:
-            raise ValueError("prune needs a box (center, half_extent), max_age, or both")
+            raise ValueError("%s needs a box (center, half_extent), max_age, or both" % who)
         rule = _lib.NosVoxelPrune()
         rule.struct_size = ctypes.sizeof(_lib.NosVoxelPrune)
         if center is not None:
@@ -950,9 +950,123 @@ class VoxelMap:
                 raise ValueError("max_age must be >= 0")
             rule.what |= _lib.NOS_PRUNE_AGE
             rule.max_age = int(max_age)
+        return rule
+
+    def prune(self, center=None, half_extent=None, max_age=None):
+        """Sliding window (nos_voxel_map_prune) → number of voxels removed.  center [3] with half_extent ([3], or a scalar
+        for a cube): keep the voxels whose cell meets the closed box center ± half_extent.  max_age: keep the voxels an
+        insert touched within the last max_age inserts (0 = the last insert only).  Both: a voxel must pass both.  The
+        survivors keep their order and are renumbered by rank; the store may shrink."""
+        rule = self._keep_rule("prune", center, half_extent, max_age)
         n = ctypes.c_size_t()
         check(self._lib.nos_voxel_map_prune(self._h, ctypes.byref(rule), ctypes.byref(n)), "nos_voxel_map_prune")
         return int(n.value)
+
+    def export(self, center=None, half_extent=None, max_age=None, removed=False):
+        """The store's state on the host (nos_voxel_map_export) → dict with cells [n,3] int64, counts [n]
+        uint32, sums [n,9] (about the cell corner, the store's own numbers), stamps [n] uint32 in voxel-id order, and epoch,
+        voxel_resolution, search_radius_sq, proper_sqrt_information.  Without a rule: every voxel.  center / half_extent /
+        max_age are prune()'s, read exactly as prune() reads them: the voxels that prune would KEEP, or with removed=True
+        the ones it would remove — what a caller pages out before pruning.  The store is not modified."""
+        rule = None
+        if center is not None or half_extent is not None or max_age is not None:
+            rule = self._keep_rule("export", center, half_extent, max_age)
+        elif removed:
+            raise ValueError("removed=True needs a box (center, half_extent), max_age, or both")
+        hs = ctypes.c_void_p()
+        check(self._lib.nos_voxel_map_export(self._h, ctypes.byref(rule) if rule is not None else None,
+                                             _lib.NOS_STATE_REMOVED if removed else _lib.NOS_STATE_KEPT, ctypes.byref(hs)),
+              "nos_voxel_map_export")
+        try:
+            n = int(self._lib.nos_voxel_state_size(hs))
+            cells = np.zeros((n, 3), dtype=np.int64)
+            counts, stamps = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+            sums = np.zeros((n, 9))
+            res, radius = ctypes.c_double(), ctypes.c_double()
+            flags, epoch = ctypes.c_int(), ctypes.c_ulonglong()
+            check(self._lib.nos_voxel_state_info(hs, ctypes.byref(res), ctypes.byref(radius), ctypes.byref(flags),
+                                                 ctypes.byref(epoch), None), "nos_voxel_state_info")
+            u32p = ctypes.POINTER(ctypes.c_uint32)
+            check(self._lib.nos_voxel_state_get(hs, cells.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), counts.ctypes.data_as(u32p),
+                                                _dp(sums), stamps.ctypes.data_as(u32p)), "nos_voxel_state_get")
+        finally:
+            self._lib.nos_voxel_state_destroy(hs)
+        return {"cells": cells, "counts": counts, "sums": sums, "stamps": stamps, "epoch": int(epoch.value),
+                "voxel_resolution": float(res.value), "search_radius_sq": float(radius.value),
+                "proper_sqrt_information": bool(flags.value & 1)}
+
+    def _import(self, mode, state):
+        cells = np.ascontiguousarray(state["cells"], dtype=np.int64).reshape(-1, 3)
+        counts = np.ascontiguousarray(state["counts"], dtype=np.uint32).reshape(-1)
+        sums = np.ascontiguousarray(state["sums"], dtype=np.float64).reshape(-1, 9)
+        stamps = state.get("stamps")
+        if stamps is not None:
+            stamps = np.ascontiguousarray(stamps, dtype=np.uint32).reshape(-1)
+        n = counts.size
+        if cells.shape[0] != n or sums.shape[0] != n or (stamps is not None and stamps.size != n):
+            raise ValueError("cells, counts, sums and stamps of a state have one entry per voxel")
+        res = state.get("voxel_resolution")
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        touched = ctypes.c_size_t()
+        check(self._lib.nos_voxel_map_import(self._h, mode, ctypes.c_double(self.voxel_resolution if res is None else res), n,
+                                             cells.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), counts.ctypes.data_as(u32p),
+                                             _dp(sums), stamps.ctypes.data_as(u32p) if stamps is not None else None,
+                                             int(state.get("epoch", 0)), ctypes.byref(touched)), "nos_voxel_map_import")
+        return int(touched.value)
+
+    def restore(self, state):
+        """A state (the dict export() returns) into this store, which must hold no voxel (nos_voxel_map_import,
+        NOS_IMPORT_RESTORE): voxel i of the state becomes voxel id i with its count, sums and stamp as given, the epoch
+        becomes the state's, and the statistics are re-derived with THIS store's flags.  Restored from export() of a store
+        with the same resolution and flags, this store cannot be told from that one by anything but memory()'s capacity
+        and generation.  Without "stamps" every voxel is stamped with the epoch.  → number of voxels."""
+        return self._import(_lib.NOS_IMPORT_RESTORE, state)
+
+    def add(self, state):
+        """A state added to this store as ONE batch (nos_voxel_map_import, NOS_IMPORT_ADD) → number of voxels touched.
+        Cells the store holds get count += n and sums += s; the others are appended in ascending cell order; the epoch
+        advances by one.  The state's stamps and epoch are ignored.  A voxel that was exported, pruned and added back
+        where its cell is absent has the count, sums, mean, sqrt-information and validity it had, bit for bit."""
+        return self._import(_lib.NOS_IMPORT_ADD, state)
+
+    @classmethod
+    def from_state(cls, ctx, state, capacity=0):
+        """→ a new VoxelMap with the state's resolution, search radius and flags, restored from it.  The new store is closed
+        before an exception leaves."""
+        out = cls(ctx, state["voxel_resolution"], state["search_radius_sq"],
+                  proper_sqrt_information=bool(state["proper_sqrt_information"]), capacity=capacity)
+        try:
+            out.restore(state)
+        except Exception:
+            out.close()
+            raise
+        return out
+
+    STATE_FORMAT_VERSION = 1
+
+    def save(self, path):
+        """export() written as one .npz (np.savez; a path is written as it is given) that load() reads back."""
+        state = self.export()
+        with open(path, "wb") as f:
+            np.savez(f, format_version=np.int64(self.STATE_FORMAT_VERSION), cells=state["cells"], counts=state["counts"],
+                     sums=state["sums"], stamps=state["stamps"], epoch=np.uint64(state["epoch"]),
+                     voxel_resolution=np.float64(state["voxel_resolution"]), search_radius_sq=np.float64(state["search_radius_sq"]),
+                     proper_sqrt_information=np.bool_(state["proper_sqrt_information"]))
+
+    @classmethod
+    def load(cls, ctx, path, capacity=0):
+        """→ the VoxelMap that save() wrote, as from_state gives it.  A file of an unknown format_version raises ValueError
+        before any store is created."""
+        with np.load(path, allow_pickle=False) as z:
+            version = int(z["format_version"]) if "format_version" in z.files else None
+            if version != cls.STATE_FORMAT_VERSION:
+                raise ValueError("%s: format_version %r of a voxel map file is not known (this build reads %d)"
+                                 % (path, version, cls.STATE_FORMAT_VERSION))
+            state = {"cells": z["cells"], "counts": z["counts"], "sums": z["sums"], "stamps": z["stamps"],
+                     "epoch": int(z["epoch"]), "voxel_resolution": float(z["voxel_resolution"]),
+                     "search_radius_sq": float(z["search_radius_sq"]),
+                     "proper_sqrt_information": bool(z["proper_sqrt_information"])}
+        return cls.from_state(ctx, state, capacity)
 
     def carve(self, scan, R, t, min_crossings=2, min_hits=1, end_margin=None, min_range=0.0, max_range=None, origin=(0, 0, 0),
               dry_run=False, counts=False):
@@ -1201,6 +1315,38 @@ class PlaceDatabase:
         check(self._lib.nos_place_db_search(self._h, _dp(q), q.shape[0], first, count, _dp(dist), shift.ctypes.data_as(i32p)),
               "nos_place_db_search")
         return (dist[0], shift[0]) if single else (dist, shift)
+
+    FILE_FORMAT_VERSION = 1
+
+    def save(self, path):
+        """The parameters and every stored descriptor (get) written as one .npz that load() reads back."""
+        desc = np.zeros((len(self), self.n_rings, self.n_sectors), dtype=np.float64)
+        for k in range(desc.shape[0]):
+            desc[k] = self.get(k)
+        with open(path, "wb") as f:
+            np.savez(f, format_version=np.int64(self.FILE_FORMAT_VERSION), n_rings=np.int64(self.n_rings),
+                     n_sectors=np.int64(self.n_sectors), max_range=np.float64(self.max_range), z_floor=np.float64(self.z_floor),
+                     descriptors=desc)
+
+    @classmethod
+    def load(cls, ctx, path):
+        """→ the PlaceDatabase that save() wrote: same parameters, the descriptors added (add) in their order.  A file of
+        an unknown format_version raises ValueError before any database is created."""
+        with np.load(path, allow_pickle=False) as z:
+            version = int(z["format_version"]) if "format_version" in z.files else None
+            if version != cls.FILE_FORMAT_VERSION:
+                raise ValueError("%s: format_version %r of a place database file is not known (this build reads %d)"
+                                 % (path, version, cls.FILE_FORMAT_VERSION))
+            params = (int(z["n_rings"]), int(z["n_sectors"]), float(z["max_range"]), float(z["z_floor"]))
+            desc = z["descriptors"]
+        out = cls(ctx, *params, reserve=desc.shape[0])
+        try:
+            for d in desc:
+                out.add(d)
+        except Exception:
+            out.close()
+            raise
+        return out
 
     def close(self):
         if self._h:

@@ -10,6 +10,7 @@
 #include "voxelmerge_kernels.hpp"
 #include "voxeld2d_kernels.hpp"
 #include "voxelcarve_kernels.hpp"
+#include "voxelstate_kernels.hpp"
 
 using namespace nosd;
 
@@ -30,6 +31,19 @@ struct nos_voxel_map {
   unsigned int* d_info = nullptr; // [nos::kInfoWords]
   bool broken = false;            // a merge reported a probe error: the store's content is undefined
   nos::VoxelStoreView view{};
+};
+
+// A store's state on the host, whole or in part: what nos_voxel_map_export returns.
+struct nos_voxel_state {
+  double voxel_resolution = 1.0;
+  double search_radius_sq = 1.0;
+  int flags = 0;
+  unsigned long long epoch = 0;     // the store's at the export
+  unsigned long long n_points = 0;  // the counts below, added up
+  std::vector<int64_t> cells;       // [n][3]
+  std::vector<uint32_t> counts;     // [n]
+  std::vector<double> sums;         // [n][9] about the cell corner, the store's own
+  std::vector<uint32_t> stamps;     // [n]
 };
 
 namespace {
@@ -360,6 +374,33 @@ struct KeepPass {
   }
 };
 
+// What a prune and an export by selection read a nos_voxel_prune with, ONE copy: its validation in the header's order, the
+// box bounds in cells, the age test's two words.  `what` is not NULL.
+int keep_rule(const nos_voxel_map* vm, const nos_voxel_prune* what, nos::VoxelKeepRule* rule) {
+  *rule = nos::VoxelKeepRule{};
+  if (what->struct_size < sizeof(nos_voxel_prune)) return fail(NOS_ERR_INVALID_ARGUMENT, "struct_size is smaller than nos_voxel_prune");
+  if (what->what == 0 || (what->what & ~(NOS_PRUNE_BOX | NOS_PRUNE_AGE)))
+    return fail(NOS_ERR_INVALID_ARGUMENT, "what must be NOS_PRUNE_BOX, NOS_PRUNE_AGE or both");
+  rule->use_box = (what->what & NOS_PRUNE_BOX) ? 1 : 0;
+  rule->use_age = (what->what & NOS_PRUNE_AGE) ? 1 : 0;
+  if (rule->use_box) {
+    const double inv_res = 1.0 / vm->voxel_resolution;  // what voxel_points_kernel is handed
+    const double lim = double(1 << 20);
+    for (int k = 0; k < 3; ++k) {
+      const double c = what->center[k], h = what->half_extent[k];
+      if (!std::isfinite(c) || !std::isfinite(h) || h < 0.0)
+        return fail(NOS_ERR_INVALID_ARGUMENT, "the box needs a finite center and a finite, non-negative half extent");
+      // a cell survives iff it intersects the closed box; a box beyond the addressable grid keeps nothing
+      const double lo = std::floor((c - h) * inv_res), hi = std::floor((c + h) * inv_res);
+      rule->lo[k] = int32_t(std::min(std::max(lo, -lim), lim));
+      rule->hi[k] = int32_t(std::min(std::max(hi, -lim - 1.0), lim - 1.0));
+    }
+  }
+  rule->epoch = uint32_t(vm->epoch);
+  rule->max_age = what->max_age > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(what->max_age);
+  return NOS_OK;
+}
+
 // One prune: keep flags and totals by box and / or age, then KeepPass.
 int store_prune(nos_voxel_map* vm, const nos::VoxelKeepRule& rule, size_t* n_removed) {
   if (vm->n_voxels == 0) {
@@ -443,6 +484,190 @@ int store_carve(nos_voxel_map* vm, const nos_scan* scan, const nos::PosePod& pos
   if (crossings_out) std::memcpy(crossings_out, h_counters.data(), V * sizeof(uint32_t));
   if (hits_out) std::memcpy(hits_out, h_counters.data() + V, V * sizeof(uint32_t));
   return NOS_OK;
+}
+
+// One export.  rule == nullptr: the first n_voxels entries of key, count, acc and stamp as they are, one
+// wait.  Otherwise a prune's keep flags and their scan (KeepPass), the wait that tells how many slots are selected, the
+// gather of those slots into arena arrays, the wait for the data.  Nothing of the store is written; `out` is written
+// once nothing can fail any more.
+int store_export(nos_voxel_map* vm, const nos::VoxelKeepRule* rule, int side, nos_voxel_state* out) {
+  const size_t V = vm->n_voxels;
+  DeviceSlot& slot = vm->ctx->slots[0];
+  hipStream_t st = slot.stream;
+  DeviceBuffers buf(&slot);
+  const nos::VoxelStoreView& v = vm->view;
+  const uint64_t* d_key = v.key;
+  const uint32_t *d_count = v.count, *d_stamp = v.stamp;
+  const double* d_acc = v.acc;
+  size_t m = V;
+  hipError_t e = V > 0 ? hipSetDevice(slot.device) : hipSuccess;
+  if (e != hipSuccess) return hip_fail(e, "voxel store export");
+  if (rule && V > 0) {
+    KeepPass pass(vm);
+    buf.reserve(V * 2 * sizeof(uint32_t) + (size_t(1) << 20));
+    e = pass.plan(buf);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(nos::voxel_keep_kernel, pass.grid, dim3(256), 0, st, v, *rule, pass.keep, vm->d_info);
+      e = hipGetLastError();
+    }
+    if (e != hipSuccess) return hip_fail(e, "voxel store export (keep)");
+    unsigned int h_info[nos::kInfoWords] = {};
+    const int rc = pass.wait(h_info, nos::kInfoRemoved, 4);  // wait 1 of 2: how many slots go out
+    if (rc != NOS_OK) return rc;
+    m = side == NOS_STATE_REMOVED ? size_t(pass.totals[0]) : V - size_t(pass.totals[0]);
+    if (m > 0) {
+      uint64_t* g_key = nullptr;
+      uint32_t *g_count = nullptr, *g_stamp = nullptr;
+      double* g_acc = nullptr;
+      buf.reserve(m * (sizeof(uint64_t) + 2 * sizeof(uint32_t) + 9 * sizeof(double)) + (size_t(1) << 20));
+      e = buf.alloc(&g_key, m);
+      if (e == hipSuccess) e = buf.alloc(&g_count, m);
+      if (e == hipSuccess) e = buf.alloc(&g_acc, m * 9);
+      if (e == hipSuccess) e = buf.alloc(&g_stamp, m);
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(nos::voxel_state_gather_kernel, pass.grid, dim3(256), 0, st, v, pass.keep, pass.new_slot,
+                           side == NOS_STATE_REMOVED ? 0u : 1u, g_key, g_count, g_acc, g_stamp);
+        e = hipGetLastError();
+      }
+      if (e != hipSuccess) return hip_fail(e, "voxel store export (gather)");
+      d_key = g_key, d_count = g_count, d_acc = g_acc, d_stamp = g_stamp;
+    }
+  }
+  std::vector<uint64_t> h_keys(m);
+  std::vector<int64_t> cells(m * 3);
+  std::vector<uint32_t> counts(m), stamps(m);
+  std::vector<double> sums(m * 9);
+  if (m > 0) {
+    e = hipMemcpyAsync(h_keys.data(), d_key, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_count, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(sums.data(), d_acc, m * 9 * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(stamps.data(), d_stamp, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // the wait for the data
+    if (e != hipSuccess) return hip_fail(e, "voxel store export (download)");
+  }
+  unsigned long long points = 0;
+  for (size_t i = 0; i < m; ++i) {
+    int32_t c[3];
+    nos::unpack_cell(h_keys[i], c);
+    for (int k = 0; k < 3; ++k) cells[3 * i + k] = c[k];
+    points += counts[i];
+  }
+  out->voxel_resolution = vm->voxel_resolution, out->search_radius_sq = vm->search_radius_sq, out->flags = vm->flags;
+  out->epoch = vm->epoch, out->n_points = points;
+  out->cells.swap(cells), out->counts.swap(counts), out->sums.swap(sums), out->stamps.swap(stamps);
+  return NOS_OK;
+}
+
+// NOS_IMPORT_RESTORE into a store that holds no voxel: the n voxels as given become slots 0 … n − 1 of
+// a FRESH block — keys, counts, sums and stamps copied in, voxel_restore_kernel for the rest — which adopt_block makes
+// the store's only when nothing failed, a repeated cell included.  keys: the cells packed, on the host.
+int store_restore(nos_voxel_map* vm, size_t n, const std::vector<uint64_t>& keys, const int64_t* cells_xyz, const uint32_t* counts,
+                  const double* sums, const uint32_t* stamps, unsigned long long epoch, size_t* n_touched) {
+  if (n == 0) {
+    vm->epoch = epoch;
+    if (n_touched) *n_touched = 0;
+    return NOS_OK;
+  }
+  DeviceSlot& slot = vm->ctx->slots[0];
+  hipStream_t st = slot.stream;
+  size_t capacity = vm->capacity;
+  while (capacity < n) capacity *= 2;
+  void* block = nullptr;
+  size_t block_bytes = 0;
+  nos::VoxelStoreView nv{};
+  hipError_t e = hipSetDevice(slot.device);
+  if (e == hipSuccess) e = store_alloc(capacity, st, &block, &block_bytes, &nv);
+  if (e != hipSuccess) return hip_fail(e, "voxel store restore (new block)");
+  nv.n_voxels = uint32_t(n);
+  const nos::MapBuildParams prm{5, 0.01, 0.01, (vm->flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0, vm->voxel_resolution};
+  unsigned int h_info[nos::kInfoWords] = {};
+  e = hipMemcpyAsync(nv.key, keys.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(nv.count, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(nv.acc, sums, n * 9 * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && stamps) e = hipMemcpyAsync(nv.stamp, stamps, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(vm->d_info, 0, 3 * sizeof(unsigned int), st);  // bad, far, probe error
+  if (e == hipSuccess) e = hipMemsetAsync(vm->d_info + nos::kInfoRemoved, 0, 4 * sizeof(unsigned int), st);  // a keep pass's totals
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(nos::voxel_restore_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, nv, uint32_t(n), stamps ? 1 : 0,
+                       uint32_t(epoch), prm, vm->d_info);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h_info, vm->d_info, nos::kInfoWords * sizeof(unsigned int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the one wait; the old block is freed by adopt_block
+  if (e == hipSuccess && h_info[nos::kInfoBadPoint] != 0) {
+    (void)hipFree(block);
+    const int64_t* c = cells_xyz + 3 * size_t(h_info[nos::kInfoBadPoint] - 1u);
+    return fail(NOS_ERR_INVALID_ARGUMENT, "cell (%lld, %lld, %lld) comes twice", (long long)c[0], (long long)c[1], (long long)c[2]);
+  }
+  const char* what = "voxel store restore";
+  if (e == hipSuccess && h_info[nos::kInfoProbeError] == 0) {
+    // the device-side valid counter follows (in stream order before any later merge)
+    e = hipMemcpyAsync(vm->d_info + nos::kInfoValid, vm->d_info + nos::kInfoKeptValid, sizeof(unsigned int), hipMemcpyDeviceToDevice, st);
+    what = "voxel store restore (counter)";
+  }
+  const int rc = adopt_block(vm, e, h_info[nos::kInfoProbeError], what, "voxel store restore failed: the new table overflowed", block,
+                             block_bytes, nv, capacity);
+  if (rc != NOS_OK) return rc;
+  vm->n_voxels = uint32_t(n);
+  vm->n_valid = h_info[nos::kInfoKeptValid];
+  vm->n_points = (unsigned long long)h_info[nos::kInfoRemovedPoints] | ((unsigned long long)h_info[nos::kInfoRemovedPoints + 1] << 32);
+  vm->epoch = epoch;
+  if (n_touched) *n_touched = n;
+  return NOS_OK;
+}
+
+// NOS_IMPORT_ADD: the state as ONE batch of an insert whose runs are given — its keys grouped by cell,
+// counts and sums brought into that order (a repeated cell and a voxel taken past 2^32 − 1 points flagged on the way), the
+// wait that reads the flags, then store_merge_runs.  Nothing of the store is written before that.
+int store_add(nos_voxel_map* vm, size_t n, const std::vector<uint64_t>& keys, const int64_t* cells_xyz, const uint32_t* counts,
+              const double* sums, size_t* n_touched) {
+  if (n == 0) {
+    if (n_touched) *n_touched = 0;
+    return NOS_OK;
+  }
+  DeviceSlot& slot = vm->ctx->slots[0];
+  hipStream_t st = slot.stream;
+  DeviceBuffers buf(&slot);  // arena: every temporary comes from the slot's buffer pool
+  uint32_t *d_count = nullptr, *run_count = nullptr;
+  double *d_acc = nullptr, *run_acc = nullptr;
+  KeyGroups<uint64_t> g;  // the state's voxels grouped by cell: every run has ONE member, or the state is rejected
+  std::vector<uint32_t> iota(n);
+  unsigned long long points = 0;
+  for (size_t i = 0; i < n; ++i) iota[i] = uint32_t(i), points += counts[i];
+  hipError_t e = hipSetDevice(slot.device);
+  buf.reserve(n * (18 * sizeof(double) + 3 * sizeof(uint64_t) + 9 * sizeof(uint32_t)) + (size_t(16) << 20));
+  if (e == hipSuccess) e = buf.alloc(&d_count, n);
+  if (e == hipSuccess) e = buf.alloc(&run_count, n);
+  if (e == hipSuccess) e = buf.alloc(&d_acc, n * 9);
+  if (e == hipSuccess) e = buf.alloc(&run_acc, n * 9);
+  if (e == hipSuccess) e = g.arrays(buf, st, n);
+  if (e == hipSuccess) e = g.temporaries(buf, 63);  // all planning ahead of the first kernel
+  unsigned int h_info[nos::kInfoWords] = {};
+  uint32_t U = 0;
+  if (e == hipSuccess) e = hipMemsetAsync(vm->d_info, 0, 4 * sizeof(unsigned int), st);  // bad, far, probe error, new
+  if (e == hipSuccess) e = hipMemcpyAsync(g.keys, keys.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(g.idx, iota.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_count, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_acc, sums, n * 9 * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = g.queue(&U);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(nos::voxel_state_runs_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, vm->view, g.keys_sorted,
+                       g.idx_sorted, uint32_t(n), d_count, d_acc, run_count, run_acc, vm->d_info);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h_info, vm->d_info, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // the one wait in the middle: the flags
+  if (e != hipSuccess) return hip_fail(e, "voxel store add (sort)");
+  // nothing of the store has been written so far: a rejected state leaves it as it was
+  if (h_info[nos::kInfoBadPoint] != 0) {
+    const int64_t* c = cells_xyz + 3 * size_t(h_info[nos::kInfoBadPoint] - 1u);
+    return fail(NOS_ERR_INVALID_ARGUMENT, "cell (%lld, %lld, %lld) comes twice", (long long)c[0], (long long)c[1], (long long)c[2]);
+  }
+  if (h_info[nos::kInfoFarPoint] != 0)
+    return fail(NOS_ERR_UNSUPPORTED, "voxel %u of the state takes its destination voxel past 2^32 - 1 points", h_info[nos::kInfoFarPoint] - 1u);
+  if (h_info[nos::kInfoProbeError] != 0) return fail(NOS_ERR_HIP, "voxel store add failed: a table probe found no free entry");
+  // without a repeated cell the sorted keys ARE the runs' keys (U == n)
+  return store_merge_runs(vm, buf, g.keys_sorted, run_count, run_acc, uint32_t(n), points, "voxel store add", n_touched);
 }
 
 // The store as whatever matches against it is handed it: the view the live matcher reads (nothing of it is written), the
@@ -639,28 +864,10 @@ int nos_voxel_map_info(const nos_voxel_map* vm, size_t* n_voxels, size_t* n_vali
 int nos_voxel_map_prune(nos_voxel_map* vm, const nos_voxel_prune* what, size_t* n_removed) {
   nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
   if (!vm || !what) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (what->struct_size < sizeof(nos_voxel_prune)) return fail(NOS_ERR_INVALID_ARGUMENT, "struct_size is smaller than nos_voxel_prune");
-  if (what->what == 0 || (what->what & ~(NOS_PRUNE_BOX | NOS_PRUNE_AGE)))
-    return fail(NOS_ERR_INVALID_ARGUMENT, "what must be NOS_PRUNE_BOX, NOS_PRUNE_AGE or both");
   nos::VoxelKeepRule rule{};
-  rule.use_box = (what->what & NOS_PRUNE_BOX) ? 1 : 0;
-  rule.use_age = (what->what & NOS_PRUNE_AGE) ? 1 : 0;
-  if (rule.use_box) {
-    const double inv_res = 1.0 / vm->voxel_resolution;  // what voxel_points_kernel is handed
-    const double lim = double(1 << 20);
-    for (int k = 0; k < 3; ++k) {
-      const double c = what->center[k], h = what->half_extent[k];
-      if (!std::isfinite(c) || !std::isfinite(h) || h < 0.0)
-        return fail(NOS_ERR_INVALID_ARGUMENT, "the box needs a finite center and a finite, non-negative half extent");
-      // a cell survives iff it intersects the closed box; a box beyond the addressable grid keeps nothing
-      const double lo = std::floor((c - h) * inv_res), hi = std::floor((c + h) * inv_res);
-      rule.lo[k] = int32_t(std::min(std::max(lo, -lim), lim));
-      rule.hi[k] = int32_t(std::min(std::max(hi, -lim - 1.0), lim - 1.0));
-    }
-  }
+  const int rc = keep_rule(vm, what, &rule);
+  if (rc != NOS_OK) return rc;
   if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
-  rule.epoch = uint32_t(vm->epoch);
-  rule.max_age = what->max_age > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(what->max_age);
   return store_prune(vm, rule, n_removed);
 }
 
@@ -826,6 +1033,86 @@ int nos_voxel_map_stats(nos_voxel_map* vm, nos_map_stats** out_stats) {
   cells_from_packed_keys(h_keys, stats.get());
   *out_stats = stats.release();
   return NOS_OK;
+}
+
+int nos_voxel_map_export(nos_voxel_map* vm, const nos_voxel_prune* select, int side, nos_voxel_state** out_state) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!vm || !out_state) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (side != NOS_STATE_KEPT && side != NOS_STATE_REMOVED) return fail(NOS_ERR_INVALID_ARGUMENT, "side must be NOS_STATE_KEPT or NOS_STATE_REMOVED");
+  nos::VoxelKeepRule rule{};
+  if (select) {
+    const int rc = keep_rule(vm, select, &rule);
+    if (rc != NOS_OK) return rc;
+  }
+  if (vm->ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "exporting a voxel store needs a single-device context");
+  if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+  std::unique_ptr<nos_voxel_state> state(new (std::nothrow) nos_voxel_state());
+  if (!state) return fail(NOS_ERR_OUT_OF_MEMORY, "host allocation failed");
+  const int rc = store_export(vm, select ? &rule : nullptr, side, state.get());
+  if (rc != NOS_OK) return rc;
+  *out_state = state.release();
+  return NOS_OK;
+}
+
+size_t nos_voxel_state_size(const nos_voxel_state* state) { return state ? state->counts.size() : 0; }
+
+int nos_voxel_state_info(const nos_voxel_state* state, double* voxel_resolution, double* search_radius_sq, int* flags,
+                         unsigned long long* epoch, unsigned long long* n_points) {
+  if (!state) return fail(NOS_ERR_INVALID_ARGUMENT, "state is NULL");
+  if (voxel_resolution) *voxel_resolution = state->voxel_resolution;
+  if (search_radius_sq) *search_radius_sq = state->search_radius_sq;
+  if (flags) *flags = state->flags;
+  if (epoch) *epoch = state->epoch;
+  if (n_points) *n_points = state->n_points;
+  return NOS_OK;
+}
+
+int nos_voxel_state_get(const nos_voxel_state* state, int64_t* cells_xyz, uint32_t* counts, double* sums, uint32_t* stamps) {
+  if (!state) return fail(NOS_ERR_INVALID_ARGUMENT, "state is NULL");
+  const size_t n = state->counts.size();
+  if (cells_xyz && n > 0) std::memcpy(cells_xyz, state->cells.data(), n * 3 * sizeof(int64_t));
+  if (counts && n > 0) std::memcpy(counts, state->counts.data(), n * sizeof(uint32_t));
+  if (sums && n > 0) std::memcpy(sums, state->sums.data(), n * 9 * sizeof(double));
+  if (stamps && n > 0) std::memcpy(stamps, state->stamps.data(), n * sizeof(uint32_t));
+  return NOS_OK;
+}
+
+int nos_voxel_state_destroy(nos_voxel_state* state) {
+  delete state;
+  return NOS_OK;
+}
+
+int nos_voxel_map_import(nos_voxel_map* vm, int mode, double voxel_resolution, size_t n, const int64_t* cells_xyz,
+                         const uint32_t* counts, const double* sums, const uint32_t* stamps, unsigned long long epoch,
+                         size_t* n_touched) {
+  nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  // the checks that need no device, the NOS_ERR_INVALID_ARGUMENT ones that read nothing of the store first
+  if (!vm) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map is NULL");
+  if (mode != NOS_IMPORT_RESTORE && mode != NOS_IMPORT_ADD) return fail(NOS_ERR_INVALID_ARGUMENT, "unknown import mode %d", mode);
+  if (n > 0 && (!cells_xyz || !counts || !sums)) return fail(NOS_ERR_INVALID_ARGUMENT, "cells / counts / sums is NULL");
+  if (std::memcmp(&voxel_resolution, &vm->voxel_resolution, sizeof(double)) != 0)
+    return fail(NOS_ERR_INVALID_ARGUMENT, "the state's voxel resolution is not the store's: its sums are about the corners of another grid");
+  if (vm->ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "importing into a voxel store needs a single-device context");
+  if (n > (size_t(1) << 30)) return fail(NOS_ERR_UNSUPPORTED, "too many voxels for one store");
+  for (size_t i = 0; i < n; ++i) {
+    if (counts[i] == 0) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel %zu has a count of 0: a voxel holds at least one point", i);
+    for (int k = 0; k < 9; ++k)
+      if (!std::isfinite(sums[9 * i + k])) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel %zu has a non-finite sum", i);
+  }
+  const int64_t lim = int64_t(1) << 20;
+  std::vector<uint64_t> keys(n);
+  for (size_t i = 0; i < n; ++i) {
+    const int64_t* c = cells_xyz + 3 * i;
+    for (int k = 0; k < 3; ++k)
+      if (c[k] < -lim || c[k] >= lim)
+        return fail(NOS_ERR_UNSUPPORTED, "voxel %zu lies outside the addressable grid (+-2^20 cells per axis)", i);
+    keys[i] = nos::pack_cell(c[0], c[1], c[2]);
+  }
+  if (mode == NOS_IMPORT_RESTORE && vm->n_voxels != 0)
+    return fail(NOS_ERR_INVALID_ARGUMENT, "NOS_IMPORT_RESTORE needs a store that holds no voxel (this one holds %u)", vm->n_voxels);
+  if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+  if (mode == NOS_IMPORT_RESTORE) return store_restore(vm, n, keys, cells_xyz, counts, sums, stamps, epoch, n_touched);
+  return store_add(vm, n, keys, cells_xyz, counts, sums, n_touched);
 }
 
 int nos_voxel_map_destroy(nos_voxel_map* vm) {

@@ -377,12 +377,118 @@ def candidate_poses(candidates, stored_poses):
     return out
 
 
+def combine_cells(cells, counts, sums, stamps):
+    """Voxels of one grid that may name a cell more than once → one voxel per cell, in ascending cell order: counts added,
+    sums added in ARRIVAL order (left to right, as they stand in the arrays), stamp the last one's.  A plain function over
+    arrays: cells [n,3] int64, counts [n], sums [n,9], stamps [n] → the same four.  A cell whose count passes 2^32 − 1
+    raises OverflowError."""
+    cells = np.asarray(cells, dtype=np.int64).reshape(-1, 3)
+    counts = np.asarray(counts, dtype=np.uint32).reshape(-1)
+    sums = np.asarray(sums, dtype=np.float64).reshape(-1, 9)
+    stamps = np.asarray(stamps, dtype=np.uint32).reshape(-1)
+    uniq, inverse = np.unique(cells, axis=0, return_inverse=True)
+    inverse = inverse.reshape(-1)
+    if uniq.shape[0] == cells.shape[0]:  # nothing came twice: only the order changes
+        order = np.argsort(inverse, kind="stable")
+        return uniq, counts[order], sums[order], stamps[order]
+    total = np.zeros(uniq.shape[0], dtype=np.uint64)
+    np.add.at(total, inverse, counts.astype(np.uint64))
+    if total.size and int(total.max()) > 0xFFFFFFFF:
+        raise OverflowError("a cached voxel would hold more than 2^32 - 1 points")
+    out = np.zeros((uniq.shape[0], 9))
+    np.add.at(out, inverse, sums)  # unbuffered: one addition per row, in the order of the rows
+    last = np.zeros(uniq.shape[0], dtype=np.uint32)
+    last[inverse] = stamps  # a repeated index keeps the last assignment
+    return uniq, total.astype(np.uint32), out, last
+
+
+def tiles_of_cells(cells, tile_cells):
+    """→ the tile floor(cell / tile_cells) of every cell, [n,3] int64 (floor, so negative cells land in negative tiles)."""
+    return np.floor_divide(np.asarray(cells, dtype=np.int64).reshape(-1, 3), np.int64(tile_cells))
+
+
+class TileCache:
+    """Host-side cache of voxels paged out of an api.VoxelMap, keyed by tile = floor(cell / tile_cells) per
+    axis: the sliding window of odometry() as a cache over a larger map.  put() takes a state (VoxelMap.export), take()
+    gives one back (for VoxelMap.add) and forgets it.  All voxels belong to one grid: a state of another
+    voxel_resolution raises ValueError.  Nothing here touches a device."""
+
+    def __init__(self, tile_cells=16):
+        if int(tile_cells) < 1:
+            raise ValueError("tile_cells must be >= 1")
+        self.tile_cells = int(tile_cells)
+        self._tiles = {}  # (tx, ty, tz) → (cells, counts, sums, stamps), one voxel per cell, ascending cell
+        self._meta = None  # voxel_resolution, search_radius_sq, proper_sqrt_information of the first state
+        self._epoch = 0
+        self._n = 0
+
+    def __len__(self):
+        """Number of cached voxels."""
+        return self._n
+
+    def put(self, state):
+        """The voxels of a state, grouped by tile.  A cell that is cached already (or comes twice) is combined in arrival
+        order: counts added, sums added, stamp the later one (combine_cells).  → number of voxels the state held."""
+        counts = np.asarray(state["counts"], dtype=np.uint32).reshape(-1)
+        n = counts.size
+        if n == 0:
+            return 0
+        meta = (float(state["voxel_resolution"]), float(state["search_radius_sq"]), bool(state["proper_sqrt_information"]))
+        if self._meta is None:
+            self._meta = meta
+        elif meta[0] != self._meta[0]:
+            raise ValueError("the cache holds voxels of resolution %r, the state has %r" % (self._meta[0], meta[0]))
+        self._epoch = max(self._epoch, int(state.get("epoch", 0)))
+        cells = np.asarray(state["cells"], dtype=np.int64).reshape(-1, 3)
+        sums = np.asarray(state["sums"], dtype=np.float64).reshape(-1, 9)
+        stamps = state.get("stamps")
+        stamps = np.zeros(n, dtype=np.uint32) if stamps is None else np.asarray(stamps, dtype=np.uint32).reshape(-1)
+        tiles = tiles_of_cells(cells, self.tile_cells)
+        uniq, inverse = np.unique(tiles, axis=0, return_inverse=True)
+        order = np.argsort(inverse.reshape(-1), kind="stable")  # by tile, arrival order within a tile
+        bounds = np.searchsorted(inverse.reshape(-1)[order], np.arange(uniq.shape[0] + 1))
+        for k in range(uniq.shape[0]):
+            rows = order[bounds[k]:bounds[k + 1]]
+            key = tuple(int(x) for x in uniq[k])
+            new = (cells[rows], counts[rows], sums[rows], stamps[rows])
+            old = self._tiles.get(key)
+            if old is not None:
+                self._n -= old[1].size
+                new = tuple(np.concatenate([a, b]) for a, b in zip(old, new))
+            self._tiles[key] = combine_cells(*new)
+            self._n += self._tiles[key][1].size
+        return n
+
+    def take(self, lo_cell, hi_cell):
+        """Removes and returns, as ONE state, every cached tile that meets the closed cell box lo_cell … hi_cell ([3] each,
+        inclusive): whole tiles, so voxels outside the box come along.  Tiles in ascending order, cells ascending within
+        a tile.  The state's epoch is the largest one put() has seen."""
+        lo = tiles_of_cells(np.asarray(lo_cell, dtype=np.int64), self.tile_cells)[0]
+        hi = tiles_of_cells(np.asarray(hi_cell, dtype=np.int64), self.tile_cells)[0]
+        hit = sorted(key for key in self._tiles if all(lo[k] <= key[k] <= hi[k] for k in range(3)))
+        parts = [self._tiles.pop(key) for key in hit]
+        res, radius, proper = self._meta if self._meta is not None else (None, None, None)
+        if parts:
+            cells, counts, sums, stamps = (np.concatenate(a) for a in zip(*parts))
+        else:
+            cells, counts = np.zeros((0, 3), dtype=np.int64), np.zeros(0, dtype=np.uint32)
+            sums, stamps = np.zeros((0, 9)), np.zeros(0, dtype=np.uint32)
+        self._n -= counts.size
+        return {"cells": cells, "counts": counts, "sums": sums, "stamps": stamps, "epoch": self._epoch,
+                "voxel_resolution": res, "search_radius_sq": radius, "proper_sqrt_information": proper}
+
+    def take_all(self):
+        """take() of everything."""
+        lim = 1 << 40
+        return self.take((-lim,) * 3, (lim,) * 3)
+
+
 _ONE_LAUNCH_KWARGS = ("loss", "options", "max_outer_iterations", "dof", "dtype", "keep_multiple")
 
 
 def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, max_voxel_age=None, filter_voxel_size=None,
              insert_filtered=False, live_match=None, one_launch=False, live_indexed=False, sweep_times=None, sweep_reference=1.0,
-             carve=None, place_db=None, **scan_to_map_kwargs):
+             carve=None, place_db=None, tiles=None, **scan_to_map_kwargs):
     """Scan-to-map odometry over a growing map (api.VoxelMap): for each scan, snapshot the store → scan_to_map from the
     previous scan's pose → insert the scan at the pose found (VoxelMap.insert_scan, warped on the device).  The harness's
     sequence UpdateNdtMap → OptimizePose → UpdateNdtMap (MDM/tests/simple_optimization_test.cc:236-281, 474-503) with the
@@ -424,7 +530,16 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
     the device), built from the scan the frame registers, after the deskew and before the filter, and added once the
     registration has succeeded: an empty database's index of a frame is then its index in the returned poses, ready for
     loop_candidates.  None: nothing is added, bit for bit.
+    tiles: a TileCache, only together with window_half_extent — the window becomes a cache over a larger map (DESIGN.md
+    §31).  After each pose the voxels the prune is about to remove are paged out (tiles.put(VoxelMap.export(...,
+    removed=True))), the prune runs as it always did, and every cached tile that meets the new window is paged back in
+    (VoxelMap.add(tiles.take(...)), the window's cells by the prune's own bounds): when the vehicle returns to a place the
+    map there is what it was, count and sums bit for bit, instead of empty.  Whole tiles come back, so voxels of a tile
+    that reach beyond the window travel in and out until the window has passed; what is paged in is stamped as touched.
+    None: nothing is exported or added, bit for bit.
     → (list of Poses, list of per-scan round lists)."""
+    if tiles is not None and window_half_extent is None:
+        raise ValueError("tiles pages voxels in and out of the window: it needs window_half_extent")
     if live_indexed:
         if live_match is not None and not live_match:
             raise ValueError("live_indexed=True matches against the live store: live_match=False contradicts it")
@@ -481,8 +596,17 @@ def odometry(ctx, voxel_map, scans, initial_pose=None, window_half_extent=None, 
                 scan.close()
         if windowed:
             box = window_half_extent is not None
+            if tiles is not None:
+                tiles.put(voxel_map.export(center=pose.t, half_extent=window_half_extent, max_age=max_voxel_age, removed=True))
             voxel_map.prune(center=pose.t if box else None, half_extent=window_half_extent if box else None,
                             max_age=max_voxel_age)
+            if tiles is not None and len(tiles):
+                # the window in cells, as the prune bounds it: floor((center -+ half_extent) * (1 / resolution))
+                c, h = np.asarray(pose.t, dtype=np.float64).reshape(3), np.asarray(window_half_extent, dtype=np.float64)
+                inv_res = 1.0 / voxel_map.voxel_resolution
+                paged = tiles.take(np.floor((c - h) * inv_res), np.floor((c + h) * inv_res))
+                if paged["counts"].size:
+                    voxel_map.add(paged)
         poses.append(Pose(pose.R, pose.t))
         all_rounds.append(rounds)
     return poses, all_rounds
