@@ -615,6 +615,55 @@ typedef struct nos_voxel_carve {
 int nos_voxel_map_carve(nos_voxel_map* map, nos_scan* scan, const double R[9], const double t[3],
                         const nos_voxel_carve* what, size_t* n_removed, size_t* n_skipped,
                         uint32_t* crossings_out, uint32_t* hits_out);
+/* Ray casting: what would a sensor at this pose see?  Every point p of `rays` (any scan, its local frame)
+ * is a beam from the sensor origin through p: a measured scan asks what the map predicts along each measured beam, a
+ * pattern of unit vectors renders a view.  Each beam is walked through the grid on the device with the carve's walk and
+ * ends at the first voxel it hits; the hit test is the one of NDT occupancy maps (Saarinen et al. 2013): the
+ * maximum-likelihood point of the voxel's Gaussian along the ray, taken inside the cell.  The store is only read.
+ * Rule (every operation an IEEE double operation, fused only where it says so):
+ *   Ray.  a = R origin + t and e = R p + t with the carve's warp (per row fma(R2, z, fma(R0, x, R1 * y)) + t).
+ *     d = e - a per component, len = sqrt((dx dx + dy dy) + dz dz), not fused.  sc = max_range / len,
+ *     b_k = a_k + sc d_k (product rounded, then the sum), w_k = b_k - a_k.  The ray is SKIPPED (voxel -1, range 0.0,
+ *     counted in *n_skipped) iff e has a non-finite component, or !(len > 0), or one of the cells floor(a inv_res),
+ *     floor(b inv_res) lies outside the addressable +-2^20 per axis (inv_res = 1.0 / voxel_resolution).
+ *   Walk.  The walk of nos_voxel_map_carve from a to b: crossing parameters from their index, equal parameters to x
+ *     before y before z, 1 + n_x + n_y + n_z cells.  A visited cell has tau_in (0 for the first cell, else the tau of the
+ *     crossing that entered it) and tau_out (the tau of the crossing that leaves it, 1 for the last cell).
+ *   Test.  Only where the store holds the cell, the voxel v is valid and count[v] >= min_points.  m = mean_v - a;
+ *     Sw = S_v w and Sm = S_v m with the stored row-major sqrt-information; den = Sw.Sw, no hit unless den > 0;
+ *     tau* = (Sw.Sm) / den; tau_c = min(max(tau*, tau_in), tau_out); r = S_v (tau_c w - m), m2 = r.r.  Hit iff
+ *     m2 <= max_mahalanobis_sq and tau_c max_range >= min_range; a NaN is no hit.  Inside this block the compiler may
+ *     fuse and reorder: m2 and the range are defined to rounding error, not to the bit.
+ *   Result.  The first hit in walk order ends the walk: voxel_out[i] = v, range_out[i] = tau_c max_range.  No hit: -1
+ *     and 0.0.  A ray's result depends on that ray, the pose and the store alone, so it does not depend on the order of
+ *     the points, on the other points, nor on how often the call is made.
+ * voxel_out, range_out (optional): host arrays of nos_scan_size(rays) entries, indexed like the scan's STORED positions
+ * (nos_scan_order maps them to input indices).  *n_hit, *n_skipped (optional): rays that hit, rays skipped.
+ * *out_scan (optional): a new scan of the hits only, compacted in stored order; a hit point is
+ * origin + (range / len)(p - origin) per component (quotient, difference, product, sum: each rounded once), in the rays'
+ * frame, and the new scan's order is the original index of each hit's ray, composed with the order of `rays` as
+ * nos_scan_filter composes it.  Free it with nos_scan_destroy.
+ * An empty scan or an empty store is a no-op: every entry -1 and 0.0, both counts 0, an empty *out_scan.
+ * Rejected, every output unwritten, before any device work:
+ *   NOS_ERR_INVALID_ARGUMENT  map, rays, R, t or what NULL; struct_size < sizeof(nos_voxel_raycast); a non-finite entry of
+ *                             R, t or origin; max_range not finite or not above 0; min_range or max_mahalanobis_sq
+ *                             negative or not finite; a scan of another context;
+ *   NOS_ERR_UNSUPPORTED       a multi-device context; 3 (ceil(max_range / voxel_resolution) + 1) > NOS_CARVE_MAX_CELLS;
+ *                             a scan of 2^32 - 1 points or more;
+ *   NOS_ERR_HIP               a store left undefined by an earlier failure.
+ * Work: one table probe per visited cell, twelve doubles read per visited valid voxel; one host wait, two when
+ * *out_scan is asked for and a ray hit. */
+typedef struct nos_voxel_raycast {
+  size_t struct_size;        /* sizeof(nos_voxel_raycast), for later growth */
+  double origin[3];          /* sensor origin in the RAYS' frame (usually 0, 0, 0) */
+  double min_range;          /* a hit nearer than this is passed over, >= 0 */
+  double max_range;          /* every beam is walked up to this length; finite, > 0 */
+  double max_mahalanobis_sq; /* finite, >= 0 */
+  uint32_t min_points;       /* a voxel with fewer points is passed through */
+} nos_voxel_raycast;
+int nos_voxel_map_raycast(nos_voxel_map* map, nos_scan* rays, const double R[9], const double t[3],
+                          const nos_voxel_raycast* what, int32_t* voxel_out, double* range_out,
+                          nos_scan** out_scan, size_t* n_hit, size_t* n_skipped);
 /* Any output pointer may be NULL.  capacity: slots the arrays have room for; bytes: device memory the store holds;
  * epoch: see NOS_PRUNE_AGE; generation: times the store's device block was replaced (growth, a prune that removed
  * something). */

@@ -6,13 +6,13 @@ reference's Solve()/Options surface).  This package only binds them; importing i
 a GPU, using it does — there is no CPU fallback.
 """
 from . import _lib
-from .api import (Context, NdtDataset, NdtIndexedDataset, PlaceDatabase, ReprojDataset, VoxelMap, make_loss,
+from .api import (Context, NdtDataset, NdtIndexedDataset, PlaceDatabase, ReprojDataset, VoxelMap, make_loss, ray_pattern,
                   reproj_solve_batch, solve3_batch, solve6_batch)
 from .solvers import (MahalanobisDistanceMinimizerHip, MahalanobisDistanceMinimizerHip3DOF, Options, Pose,
                       ReprojectionErrorMinimizerHip)
 
 __all__ = [
-    "Context", "NdtDataset", "NdtIndexedDataset", "ReprojDataset", "VoxelMap", "PlaceDatabase", "make_loss", "Options", "Pose",
+    "Context", "NdtDataset", "NdtIndexedDataset", "ReprojDataset", "VoxelMap", "PlaceDatabase", "make_loss", "ray_pattern", "Options", "Pose",
     "solve6_batch", "solve3_batch", "reproj_solve_batch",
     "MahalanobisDistanceMinimizerHip", "MahalanobisDistanceMinimizerHip3DOF",
     "ReprojectionErrorMinimizerHip",

@@ -33,7 +33,7 @@ C_ABI_SYMBOLS = (
     "nos_scan_destroy", "nos_scan_size", "nos_scan_sort_by_cell", "nos_scan_order", "nos_scan_filter", "nos_scan_points", "nos_scan_deskew", "nos_scan_descriptor", "nos_place_db_create", "nos_place_db_destroy", "nos_place_db_size", "nos_place_db_add", "nos_place_db_add_scan", "nos_place_db_get", "nos_place_db_search", "nos_place_db_search_scan", "nos_ndt_match", "nos_ndt_indexed_dataset_create", "nos_ndt_match_indexed", "nos_indexed_dataset_info", "nos_indexed_dataset_download", "nos_ndt_map_build", "nos_map_stats_size",
     "nos_map_stats_get", "nos_map_stats_get_eigen", "nos_map_stats_destroy",
     "nos_voxel_map_create", "nos_voxel_map_insert", "nos_voxel_map_insert_scan", "nos_voxel_map_info", "nos_voxel_map_snapshot",
-    "nos_voxel_map_stats", "nos_voxel_map_match", "nos_voxel_map_match_indexed", "nos_voxel_map_prune", "nos_voxel_map_carve", "nos_voxel_map_memory", "nos_voxel_map_merge", "nos_voxel_map_match_map", "nos_voxel_map_export", "nos_voxel_state_size", "nos_voxel_state_info", "nos_voxel_state_get", "nos_voxel_state_destroy", "nos_voxel_map_import", "nos_voxel_map_destroy", "nos_dataset_drop_last_matches", "nos_pgo_create", "nos_pgo_destroy", "nos_pgo_num_unknowns",
+    "nos_voxel_map_stats", "nos_voxel_map_match", "nos_voxel_map_match_indexed", "nos_voxel_map_prune", "nos_voxel_map_carve", "nos_voxel_map_raycast", "nos_voxel_map_memory", "nos_voxel_map_merge", "nos_voxel_map_match_map", "nos_voxel_map_export", "nos_voxel_state_size", "nos_voxel_state_info", "nos_voxel_state_get", "nos_voxel_state_destroy", "nos_voxel_map_import", "nos_voxel_map_destroy", "nos_dataset_drop_last_matches", "nos_pgo_create", "nos_pgo_destroy", "nos_pgo_num_unknowns",
     "nos_pgo_linearize", "nos_pgo_solve", "nos_pgo_retract", "nos_pgo_get_state", "nos_pgo_get_vector",
     "nos_pgo_matvec", "nos_pgo_precondition", "nos_pgo_time_sweep", "nos_pgo_layout_info", "nos_debug_lm_step", "nos_debug_voxel_finish", "nos_debug_voxel_moments", "nos_debug_voxel_pair_information", "nos_dataset_destroy", "nos_dataset_size", "nos_dataset_dtype", "nos_dataset_stream_bytes",
     "nos_dataset_set_simd_class",
@@ -106,6 +106,11 @@ class NosVoxelCarve(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_size_t), ("origin", ctypes.c_double * 3), ("end_margin", ctypes.c_double),
                 ("min_range", ctypes.c_double), ("max_range", ctypes.c_double), ("min_crossings", ctypes.c_uint32),
                 ("min_hits", ctypes.c_uint32), ("dry_run", ctypes.c_int)]
+
+
+class NosVoxelRaycast(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_size_t), ("origin", ctypes.c_double * 3), ("min_range", ctypes.c_double),
+                ("max_range", ctypes.c_double), ("max_mahalanobis_sq", ctypes.c_double), ("min_points", ctypes.c_uint32)]
 
 
 class NosPlaceParams(ctypes.Structure):
@@ -225,6 +230,9 @@ def _declare(lib):
             u32p = ctypes.POINTER(ctypes.c_uint32)
             lib.nos_voxel_map_carve.argtypes = [vp, vp, dp, dp, ctypes.POINTER(NosVoxelCarve), ctypes.POINTER(sz),
                                                 ctypes.POINTER(sz), u32p, u32p]
+        if hasattr(lib, "nos_voxel_map_raycast"):  # ray casting: absent from builds older still
+            lib.nos_voxel_map_raycast.argtypes = [vp, vp, dp, dp, ctypes.POINTER(NosVoxelRaycast), ctypes.POINTER(ctypes.c_int32), dp,
+                                                  c_void_pp, ctypes.POINTER(sz), ctypes.POINTER(sz)]
         if hasattr(lib, "nos_voxel_map_merge"):  # one store merged into another under a pose: absent from builds older still
             lib.nos_voxel_map_merge.argtypes = [vp, vp, dp, dp, ctypes.POINTER(sz)]
         if hasattr(lib, "nos_voxel_map_match_map"):  # one store matched against another: absent from builds older still

@@ -803,6 +803,7 @@ class VoxelMap:
     then ascending cell.  proper_sqrt_information as in NdtMap.build; capacity (voxels) only avoids early growth.
     prune() removes voxels by a box and / or by age (a sliding window) and renumbers the survivors by their rank;
     carve() removes, the same way, the voxels a scan's rays pass through (line of sight).
+    raycast() tells what a sensor at a pose would see: the first voxel every beam hits, and its range.
     export() copies the state — cells, counts, the nine sums, stamps — to the host, whole or by a prune's rule; restore()
     makes an empty store that state again, bit for bit, add() takes it as one more batch; save() / load() keep it in a file."""
 
@@ -1106,6 +1107,49 @@ class VoxelMap:
             info["crossings"], info["hits"] = crossings, hits
         return int(removed.value), info
 
+    def raycast(self, rays, R, t, max_range, min_range=0.0, max_mahalanobis_sq=1.0, min_points=0, origin=(0, 0, 0),
+                points=False):
+        """Ray casting (nos_voxel_map_raycast) → (voxels int32 [n], ranges float64 [n], info): what would a
+        sensor at the pose (R, t) see?  Every point p of the api.Scan `rays` is a beam from `origin` (rays' frame) through
+        p, warped by R p + t and walked cell by cell up to max_range; it ends at the first voxel — valid, with at least
+        min_points points — whose Gaussian comes within max_mahalanobis_sq of the beam inside its cell, no nearer than
+        min_range.  voxels[i] is that voxel's id (-1: none) and ranges[i] the range along the beam (0.0: none), indexed
+        like the scan's stored positions.  A measured scan gives the predicted range of every measured beam, a
+        ray_pattern renders a view.  info: {"hits": rays that hit, "skipped": rays with a non-finite point, of zero
+        length or leaving the addressable grid}; with points=True also "scan": the resident Scan of the hit points in the
+        rays' frame, in stored order, whose `order` names each hit's ray — descriptor(), PlaceDatabase.add, filtered,
+        match and insert_scan take it as any scan.  The store is only read."""
+        return self._raycast(rays, R, t, max_range, min_range, max_mahalanobis_sq, min_points, origin, points, True)
+
+    def _raycast(self, rays, R, t, max_range, min_range, max_mahalanobis_sq, min_points, origin, points, results):
+        """raycast(); results=False: the per-ray arrays are not brought to the host (→ None, None, info)"""
+        R = _dvec(R, 9)
+        t = _dvec(t, 3)
+        o = _dvec(origin, 3)
+        what = _lib.NosVoxelRaycast()
+        what.struct_size = ctypes.sizeof(_lib.NosVoxelRaycast)
+        for k in range(3):
+            what.origin[k] = o[k]
+        what.min_range, what.max_range = float(min_range), float(max_range)
+        what.max_mahalanobis_sq = float(max_mahalanobis_sq)
+        if not 0 <= int(min_points) <= 0xFFFFFFFF:
+            raise ValueError("min_points must be in 0 … 2^32 - 1")
+        what.min_points = int(min_points)
+        voxels = ranges = None
+        if results:
+            n = len(rays)
+            voxels, ranges = np.full(n, -1, dtype=np.int32), np.zeros(n, dtype=np.float64)
+        hits, skipped = ctypes.c_size_t(), ctypes.c_size_t()
+        h = ctypes.c_void_p()
+        check(self._lib.nos_voxel_map_raycast(self._h, rays._h, _dp(R), _dp(t), ctypes.byref(what),
+                                              voxels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if results else None,
+                                              _dp(ranges) if results else None, ctypes.byref(h) if points else None,
+                                              ctypes.byref(hits), ctypes.byref(skipped)), "nos_voxel_map_raycast")
+        info = {"hits": int(hits.value), "skipped": int(skipped.value)}
+        if points:
+            info["scan"] = Scan._adopted(self._ctx, h)
+        return voxels, ranges, info
+
     def memory(self):
         """→ dict: capacity (slots), bytes (device memory held), epoch (successful non-empty inserts so far), generation
         (times the device block was replaced: growth, a prune that removed something)."""
@@ -1168,6 +1212,16 @@ class Scan:
             self._h, kept._h = kept._h, None
         if sort_cell is not None:
             self.sort_by_cell(sort_cell)
+
+    @classmethod
+    def _adopted(cls, ctx, handle):
+        """a Scan around a handle the library returned"""
+        out = cls.__new__(cls)
+        out._ctx = ctx
+        out._lib = ctx._lib
+        out._h = handle
+        ctx._adopt(out)
+        return out
 
     def filtered(self, voxel_size):
         """→ a new Scan with the first point (smallest input index) of every voxel of edge voxel_size, in this scan's
@@ -1361,6 +1415,21 @@ class PlaceDatabase:
             self.close()
         except Exception:
             pass
+
+
+def ray_pattern(n_azimuth, elevations):
+    """→ [len(elevations) * n_azimuth, 3] unit directions of a spinning sensor, elevation-major: for every elevation
+    (radians above the horizon) n_azimuth beams at azimuth 2π (k + ½) / n_azimuth, k = 0 … n_azimuth − 1, as
+    (cos el cos az, cos el sin az, sin el).  The beams sit in the MIDDLE of their azimuth cells: where n_azimuth is a
+    multiple of a descriptor's n_sectors no beam lies on a sector border, so the last bit of an arctangent cannot move a
+    rendered point to the neighbouring sector.  A host helper: upload it as an api.Scan and hand it to VoxelMap.raycast."""
+    n_azimuth = int(n_azimuth)
+    if n_azimuth < 1:
+        raise ValueError("n_azimuth must be >= 1")
+    el = np.asarray(elevations, dtype=np.float64).reshape(-1, 1)
+    az = (2.0 * np.pi / n_azimuth) * (np.arange(n_azimuth, dtype=np.float64) + 0.5).reshape(1, -1)
+    d = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el) * np.ones_like(az)], axis=-1)
+    return np.ascontiguousarray(d.reshape(-1, 3))
 
 
 def download(dataset):

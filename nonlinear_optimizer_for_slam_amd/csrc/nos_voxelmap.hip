@@ -1,6 +1,6 @@
 // nos_voxelmap.hip — incremental NDT voxel store: a device-resident map that grows scan by scan; a batch
 // is grouped by voxel through group_host.hpp (§19), matched against through match_host.hpp (§18); it forgets by box and age
-// (prune, §13) and by line of sight (carve, §25).
+// (prune, §13) and by line of sight (carve, §25); it answers what a sensor at a pose would see (ray cast, §32).
 #define NOS_WITH_VOXEL_INDEX_KERNELS  // voxelmatch_kernels.hpp: this unit compiles (and launches) the two index kernels
 #include "group_host.hpp"
 #include "match_host.hpp"
@@ -10,6 +10,7 @@
 #include "voxelmerge_kernels.hpp"
 #include "voxeld2d_kernels.hpp"
 #include "voxelcarve_kernels.hpp"
+#include "voxelraycast_kernels.hpp"
 #include "voxelstate_kernels.hpp"
 
 using namespace nosd;
@@ -486,6 +487,130 @@ int store_carve(nos_voxel_map* vm, const nos_scan* scan, const nos::PosePod& pos
   return NOS_OK;
 }
 
+// An empty scan in nos_scan_create's form of one.
+int empty_scan(nos_ctx* ctx, nos_scan** out) {
+  std::unique_ptr<nos_scan> s(new (std::nothrow) nos_scan());
+  if (!s) return fail(NOS_ERR_OUT_OF_MEMORY, "host allocation failed");
+  s->ctx = ctx;
+  const hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->d_planes), 3 * sizeof(double));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return hip_fail(e, "voxel store ray cast (empty scan)");
+  }
+  *out = s.release();
+  return NOS_OK;
+}
+
+// One ray cast: every point of `rays` under `pose` is a beam walked through the grid until the first
+// voxel it hits.  The store is only read — its info block too: the three counters are the cast's own, in arena memory.
+// Waits: the one that brings the counters, the hit count of the select and the per-ray results; a second one behind the
+// gather when the caller wants the hit points and there are any.  The outputs are written once nothing can fail any more.
+int store_raycast(nos_voxel_map* vm, const nos_scan* rays, const nos::PosePod& pose, const nos::VoxelRaycastParams& prm,
+                  int32_t* voxel_out, double* range_out, nos_scan** out_scan, size_t* n_hit, size_t* n_skipped) {
+  const size_t n = rays->n;
+  if (n >= 0xFFFFFFFFull) return fail(NOS_ERR_UNSUPPORTED, "too many points for one ray cast");
+  DeviceSlot& slot = vm->ctx->slots[0];
+  hipStream_t st = slot.stream;
+  hipError_t e = hipSetDevice(slot.device);
+  if (e != hipSuccess) return hip_fail(e, "voxel store ray cast");
+  nos_scan* hits_scan = nullptr;
+  if (n == 0 || vm->n_voxels == 0) {  // nothing to cast, or nothing to hit
+    if (out_scan) {
+      const int rc = empty_scan(vm->ctx, &hits_scan);
+      if (rc != NOS_OK) return rc;
+      *out_scan = hits_scan;
+    }
+    for (size_t i = 0; i < n; ++i) {
+      if (voxel_out) voxel_out[i] = -1;
+      if (range_out) range_out[i] = 0.0;
+    }
+    if (n_hit) *n_hit = 0;
+    if (n_skipped) *n_skipped = 0;
+    return NOS_OK;
+  }
+  std::vector<int32_t> h_voxel;
+  std::vector<double> h_range;
+  try {
+    if (voxel_out) h_voxel.resize(n);
+    if (range_out) h_range.resize(n);
+  } catch (const std::bad_alloc&) {
+    return fail(NOS_ERR_OUT_OF_MEMORY, "host allocation failed");
+  }
+  unsigned int h_cnt[nos::kRaycastWords] = {};
+  uint32_t n_kept = 0;
+  double* out_planes = nullptr;
+  uint32_t* out_order = nullptr;
+  {
+    DeviceBuffers buf(&slot);  // arena for the temporaries; goes back when this block ends
+    buf.reserve(n * (sizeof(int32_t) + 2 * sizeof(double) + sizeof(uint32_t)) + (size_t(8) << 20));
+    int32_t* d_voxel = nullptr;
+    double *d_range = nullptr, *d_scale = nullptr;
+    uint32_t *kept = nullptr, *d_count = nullptr;
+    unsigned int* cnt = nullptr;
+    PrimTmp t_select;
+    e = buf.alloc(&d_voxel, n);
+    if (e == hipSuccess) e = buf.alloc(&d_range, n);
+    if (e == hipSuccess) e = buf.alloc(&cnt, size_t(nos::kRaycastWords));
+    if (e == hipSuccess && out_scan) e = buf.alloc(&d_scale, n);
+    if (e == hipSuccess && out_scan) e = buf.alloc(&kept, n);
+    if (e == hipSuccess && out_scan) e = buf.alloc(&d_count, 1);
+    const nos::RaycastHit is_hit{d_voxel};
+    const rocprim::counting_iterator<uint32_t> positions(0u);
+    const auto select = [&](void* tmp, size_t& bytes) { return rocprim::select(tmp, bytes, positions, kept, d_count, n, is_hit, st); };
+    if (e == hipSuccess && out_scan) e = prim_plan(buf, select, t_select);
+    if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof h_cnt, st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(nos::voxel_raycast_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, vm->view, rays->d_planes,
+                         uint64_t(n), pose, prm, d_voxel, d_range, d_scale, cnt);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess && out_scan) e = prim_run(select, t_select);
+    if (e == hipSuccess && out_scan) e = hipMemcpyAsync(&n_kept, d_count, sizeof n_kept, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && voxel_out) e = hipMemcpyAsync(h_voxel.data(), d_voxel, n * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && range_out) e = hipMemcpyAsync(h_range.data(), d_range, n * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // the first wait: counters, results, and what sizes the new scan
+    if (e != hipSuccess) return hip_fail(e, "voxel store ray cast");
+    if (h_cnt[nos::kRaycastProbeError] != 0)
+      return fail(NOS_ERR_HIP, "voxel store ray cast failed: a table probe or a ray's walk ran past its bound");
+    if (out_scan && n_kept != h_cnt[nos::kRaycastHits])
+      return fail(NOS_ERR_HIP, "voxel store ray cast: inconsistent hit count (%u selected, %u counted)", n_kept, h_cnt[nos::kRaycastHits]);
+    if (out_scan && n_kept == 0) {
+      const int rc = empty_scan(vm->ctx, &hits_scan);
+      if (rc != NOS_OK) return rc;
+    } else if (out_scan) {
+      e = hipMalloc(reinterpret_cast<void**>(&out_planes), size_t(n_kept) * 3 * sizeof(double));
+      if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&out_order), size_t(n_kept) * sizeof(uint32_t));
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(nos::voxel_raycast_gather_kernel, dim3((n_kept + 255) / 256), dim3(256), 0, st, rays->d_planes, uint32_t(n),
+                           rays->d_order, kept, n_kept, d_scale, prm.origin[0], prm.origin[1], prm.origin[2], out_planes, out_order);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = hipStreamSynchronize(st);  // the second wait: the gather has read the arena's arrays
+      if (e == hipSuccess) {
+        hits_scan = new (std::nothrow) nos_scan();
+        if (!hits_scan) e = hipErrorOutOfMemory;
+      }
+      if (e != hipSuccess) {
+        (void)hipGetLastError();  // a failed allocation must not surface as the next call's launch error
+        if (out_planes) (void)hipFree(out_planes);
+        if (out_order) (void)hipFree(out_order);
+        return hip_fail(e, "voxel store ray cast (hit points)");
+      }
+      hits_scan->ctx = vm->ctx;
+      hits_scan->n = n_kept;
+      hits_scan->d_planes = out_planes;
+      hits_scan->d_order = out_order;
+    }
+  }
+  if (voxel_out) std::memcpy(voxel_out, h_voxel.data(), n * sizeof(int32_t));
+  if (range_out) std::memcpy(range_out, h_range.data(), n * sizeof(double));
+  if (out_scan) *out_scan = hits_scan;
+  if (n_hit) *n_hit = h_cnt[nos::kRaycastHits];
+  if (n_skipped) *n_skipped = h_cnt[nos::kRaycastSkipped];
+  return NOS_OK;
+}
+
 // One export.  rule == nullptr: the first n_voxels entries of key, count, acc and stamp as they are, one
 // wait.  Otherwise a prune's keep flags and their scan (KeepPass), the wait that tells how many slots are selected, the
 // gather of those slots into arena arrays, the wait for the data.  Nothing of the store is written; `out` is written
@@ -900,6 +1025,36 @@ int nos_voxel_map_carve(nos_voxel_map* vm, nos_scan* scan, const double R[9], co
   prm.max_cells = NOS_CARVE_MAX_CELLS;
   return store_carve(vm, scan, make_pose(R, t), prm, what->min_crossings, what->min_hits, what->dry_run != 0, n_removed, n_skipped,
                      crossings_out, hits_out);
+}
+
+int nos_voxel_map_raycast(nos_voxel_map* vm, nos_scan* rays, const double R[9], const double t[3], const nos_voxel_raycast* what,
+                          int32_t* voxel_out, double* range_out, nos_scan** out_scan, size_t* n_hit, size_t* n_skipped) {
+  // the NULL, struct and value checks come before any device (and any handle's content) is touched
+  if (!vm || !rays || !R || !t || !what) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (what->struct_size < sizeof(nos_voxel_raycast)) return fail(NOS_ERR_INVALID_ARGUMENT, "struct_size is smaller than nos_voxel_raycast");
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(R[k])) return fail(NOS_ERR_INVALID_ARGUMENT, "R has a non-finite entry");
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(t[k]) || !std::isfinite(what->origin[k])) return fail(NOS_ERR_INVALID_ARGUMENT, "t or origin has a non-finite entry");
+  if (!std::isfinite(what->max_range) || !(what->max_range > 0.0)) return fail(NOS_ERR_INVALID_ARGUMENT, "max_range must be finite and > 0");
+  if (!std::isfinite(what->min_range) || what->min_range < 0.0 || !std::isfinite(what->max_mahalanobis_sq) || what->max_mahalanobis_sq < 0.0)
+    return fail(NOS_ERR_INVALID_ARGUMENT, "min_range and max_mahalanobis_sq must be finite and >= 0");
+  if (vm->ctx != rays->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map and scan belong to different contexts");
+  nosd::CtxGuard guard_(vm->ctx);  // one solve / accumulate / create at a time per context
+  if (vm->ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "ray casting a voxel store needs a single-device context");
+  // a ray's trip count: at most ceil(max_range / res) + 1 steps per axis
+  if (3.0 * (std::ceil(what->max_range / vm->voxel_resolution) + 1.0) > double(NOS_CARVE_MAX_CELLS))
+    return fail(NOS_ERR_UNSUPPORTED, "max_range spans more than NOS_CARVE_MAX_CELLS cells: 3 (ceil(max_range / resolution) + 1) > %d",
+                NOS_CARVE_MAX_CELLS);
+  if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
+  nos::VoxelRaycastParams prm{};
+  for (int k = 0; k < 3; ++k) prm.origin[k] = what->origin[k];
+  prm.min_range = what->min_range, prm.max_range = what->max_range, prm.max_mahalanobis_sq = what->max_mahalanobis_sq;
+  prm.res = vm->voxel_resolution;
+  prm.inv_res = 1.0 / vm->voxel_resolution;  // what voxel_points_kernel is handed
+  prm.min_points = what->min_points;
+  prm.max_cells = NOS_CARVE_MAX_CELLS;
+  return store_raycast(vm, rays, make_pose(R, t), prm, voxel_out, range_out, out_scan, n_hit, n_skipped);
 }
 
 int nos_voxel_map_memory(const nos_voxel_map* vm, size_t* capacity, size_t* bytes, unsigned long long* epoch,

@@ -377,6 +377,52 @@ def candidate_poses(candidates, stored_poses):
     return out
 
 
+def map_places(ctx, vmap, poses, pattern, db=None, max_range=None, n_rings=20, n_sectors=60, descriptor_max_range=80.0,
+               z_floor=-2.0, reserve=0, **raycast_kwargs):
+    """Places from a map nobody scanned: for every pose the store is ray-cast along `pattern` and the hit
+    points, a scan in that pose's sensor frame, go into a PlaceDatabase — ray cast → db.add(scan), nothing visits the
+    host but the counts.  → (db, hits_per_pose).  The database is indexed like `poses`, so loop_candidates →
+    candidate_poses(found, poses) → relocalize work on a map that was merged, coarsened, paged in or built elsewhere.
+    vmap: api.VoxelMap; poses: Poses or (R, t) pairs; pattern: an api.Scan of beam directions (api.ray_pattern uploaded)
+    or the [n, 3] array itself; max_range: the ray cast's (required).  db: an api.PlaceDatabase to append to (it must be
+    empty for its indices to be those of `poses`); None: a new one with n_rings, n_sectors, descriptor_max_range and
+    z_floor (with `reserve` or len(poses) places reserved).  raycast_kwargs (min_range, max_mahalanobis_sq, min_points,
+    origin) go to VoxelMap.raycast unchanged."""
+    from .api import PlaceDatabase
+    if max_range is None:
+        raise ValueError("map_places needs the ray cast's max_range")
+    rc = {"min_range": 0.0, "max_mahalanobis_sq": 1.0, "min_points": 0, "origin": (0, 0, 0)}  # VoxelMap.raycast's defaults
+    unknown = set(raycast_kwargs) - set(rc)
+    if unknown:
+        raise TypeError("map_places: unknown ray cast parameters %s" % sorted(unknown))
+    rc.update(raycast_kwargs)
+    poses = list(poses)
+    own_pattern = not isinstance(pattern, Scan)
+    rays = Scan(ctx, pattern) if own_pattern else pattern
+    own_db = db is None
+    if own_db:
+        db = PlaceDatabase(ctx, n_rings, n_sectors, descriptor_max_range, z_floor, reserve=max(int(reserve), len(poses)))
+    hits = []
+    try:
+        for pose in poses:
+            R, t = (pose.R, pose.t) if hasattr(pose, "R") else pose
+            _, _, info = vmap._raycast(rays, R, t, max_range, rc["min_range"], rc["max_mahalanobis_sq"], rc["min_points"], rc["origin"],
+                                       True, False)  # the hit points stay on the device, the per-ray arrays are not fetched
+            try:
+                db.add(info["scan"])
+            finally:
+                info["scan"].close()
+            hits.append(info["hits"])
+    except Exception:
+        if own_db:
+            db.close()
+        raise
+    finally:
+        if own_pattern:
+            rays.close()
+    return db, hits
+
+
 def combine_cells(cells, counts, sums, stamps):
     """Voxels of one grid that may name a cell more than once → one voxel per cell, in ascending cell order: counts added,
     sums added in ARRIVAL order (left to right, as they stand in the arrays), stamp the last one's.  A plain function over
