@@ -1068,6 +1068,38 @@ int nos_pgo_create(nos_ctx* ctx, size_t n_poses, const double* poses, size_t n_e
                    const int32_t* ref, const int32_t* qry, const double* meas,
                    const double* switch_init, const unsigned char* switch_free,
                    const unsigned char* fixed, nos_pose_graph** out_pg);
+/* The same graph with a 6 x 6 information matrix per constraint.
+ * THE RULE.  A constraint measures the pose of the query frame in the reference frame, (t_m, q_m).  Its information
+ * Omega (6 x 6, symmetric, positive semi-definite) is over the error xi = (dt, dtheta) of that measurement, with
+ *   t_true = t_m + dt  in the reference frame,   R_true = R_m Exp(dtheta).
+ * These are the coordinates (t_x ... w_z) and the update (t += dt, R <- R Exp(dw)) of the 6-DoF NDT solvers: the 21
+ * numbers H of nos_ndt6_accumulate / nos_voxel_map_match_map's sums at the pose the registration returns (target =
+ * reference, source = query) are an Omega as they stand (tests/test_pgo_information_pipeline.py checks it).
+ * Per constraint, with e = q_q^* q_r q_m, r_R = 2 vec(e), u = R_r^T (p_q - p_r):
+ *   residual  r~ = (u - t_m, r_R).  dtheta = -r_R to first order, so the off-diagonal 3 x 3 blocks of Omega change
+ *             sign: Omega' = D Omega D, D = diag(I, -I) (done once at upload);
+ *   Jacobians under p += dp, q <- q Exp(dw):  reference end [-R_r^T | [u]x ; 0 | B],  query end [R_r^T | 0 ; 0 | C]
+ *             (B = (e_w I + [e_v]x) R_m^T, C = -e_w I + [e_v]x).  The world-frame r_t of nos_pgo_create is NOT used:
+ *             rotating Omega into the world frame at the current estimate drops a Jacobian term of the size of the residual;
+ *   cost      s^2 r~^T Omega' r~ (+ (1 - s)^2 c^2);   gradient g_i += s^2 J~^T Omega' r~;   H_ii += s^2 J~^T Omega' J~;
+ *   product   v = s (J~_i x_i + J~_j x_j) + r~ x_s,  out += s J~^T Omega' v;
+ *   switches  row (Omega' r~) . s (J~_r x_r + J~_q x_q) + h_s (1 + lambda) x_s,  h_s = r~^T Omega' r~ + c^2,
+ *             g_s = s r~^T Omega' r~ - c^2 (1 - s).
+ * With Omega = I the cost is the same function of the poses as nos_pgo_create's, and cost and gradient agree with it to
+ * rounding; the diagonal blocks do not (the Jacobians belong to another residual with the same norm).
+ * information: [n_edges][21], upper triangle row-major; NULL = nos_pgo_create.  NOS_ERR_INVALID_ARGUMENT, with nothing
+ * created, *out_pg untouched and before any device work, for a matrix with a non-finite entry, a zero matrix, or one whose
+ * smallest eigenvalue is below -1e-12 x its largest; semi-definite matrices (a registration in a corridor) are accepted.
+ * A direction that NO constraint observes (every information matrix around a pose has it in its null space) leaves a zero
+ * pivot in that pose's diagonal block, which the damping lambda diag(H) does not lift.  Where the zeros are exact (identity
+ * rotations) the solve never enters it; under general rotations the pivot is of rounding size, the block-Jacobi inverse
+ * huge and the step along that direction meaningless: give such a pose a weak prior constraint instead.
+ * A graph with information runs the owner-computes product (no block lists: nos_pgo_layout_info entries = 0) and the
+ * probed coarse operator, whatever pgo_block / pgo_coarse_probe say.  Every other nos_pgo_* call works on it. */
+int nos_pgo_create_weighted(nos_ctx* ctx, size_t n_poses, const double* poses, size_t n_edges,
+                            const int32_t* ref, const int32_t* qry, const double* meas,
+                            const double* switch_init, const unsigned char* switch_free,
+                            const unsigned char* fixed, const double* information, nos_pose_graph** out_pg);
 int nos_pgo_destroy(nos_pose_graph* pg);
 size_t nos_pgo_num_unknowns(const nos_pose_graph* pg); /* 6 n_poses + n_edges */
 int nos_pgo_linearize(nos_pose_graph* pg, double* cost, double* gradient_norm);

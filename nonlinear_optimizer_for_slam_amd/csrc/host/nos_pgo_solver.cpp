@@ -66,12 +66,30 @@ bool PoseGraphOptimizerHip::Solve(const Options& options) {
     sw_free[e] = (c.type == ConstraintType::kLoop) ? 1 : 0;  // pose_graph_optimizer_ceres.cc:29-36
   }
 
+  // information set for some constraint: 21 upper entries per constraint, identity where none was given
+  std::vector<double> information;
+  if (!information_.empty()) {
+    if (information_.rbegin()->first >= m) {
+      std::cerr << "[nos-hip] SetConstraintInformation: constraint " << information_.rbegin()->first << " of " << m
+                << " was never registered.\n";
+      report_.status = NOS_ERR_INVALID_ARGUMENT;
+      return false;
+    }
+    information.assign(21 * m, 0.0);
+    for (size_t e = 0; e < m; ++e) {
+      const auto it = information_.find(e);
+      int k = 0;
+      for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b) information[21 * e + k++] = it == information_.end() ? (a == b ? 1.0 : 0.0) : it->second[6 * a + b];
+    }
+  }
+
   nos_ctx* ctx = nullptr;
   int status = nos_ctx_create(&hip_options_.device_id, 1, &ctx);
   nos_pose_graph* pg = nullptr;
   if (status == NOS_OK)
-    status = nos_pgo_create(ctx, ordered.size(), poses.data(), m, ref.data(), qry.data(), meas.data(), sw.data(),
-                            sw_free.data(), fixed.data(), &pg);
+    status = nos_pgo_create_weighted(ctx, ordered.size(), poses.data(), m, ref.data(), qry.data(), meas.data(), sw.data(),
+                                     sw_free.data(), fixed.data(), information.empty() ? nullptr : information.data(), &pg);
   if (status != NOS_OK) {
     std::cerr << "[nos-hip] pose-graph setup failed: " << nos_status_string(status) << " — " << nos_last_error()
               << std::endl;
@@ -143,12 +161,15 @@ bool PoseGraphOptimizerHip::Solve(const Options& options) {
 }  // namespace nonlinear_optimizer
 
 // ---- C entry point for the Python test-suite: builds Pose / Constraint objects and calls the class ----
-extern "C" int nos_host_pgo_solve(size_t n_poses, const int* pose_indices, double* poses /*[n][7] in/out*/,
-                                  size_t n_constraints, const int* ref_index, const int* qry_index,
-                                  const double* meas /*[m][7]*/, const unsigned char* is_loop, size_t n_fixed,
-                                  const int* fixed_indices, int max_iterations, double gradient_tolerance,
-                                  double parameter_tolerance, int pcg_max_iterations, double pcg_tolerance,
-                                  double* switches_out, double report[6]) {
+// information: [m][36] row-major, or NULL; has_information: [m] flags (NULL: every constraint has), SetConstraintInformation
+// is called for the flagged ones.
+extern "C" int nos_host_pgo_solve_weighted(size_t n_poses, const int* pose_indices, double* poses /*[n][7] in/out*/,
+                                           size_t n_constraints, const int* ref_index, const int* qry_index,
+                                           const double* meas /*[m][7]*/, const unsigned char* is_loop, size_t n_fixed,
+                                           const int* fixed_indices, int max_iterations, double gradient_tolerance,
+                                           double parameter_tolerance, int pcg_max_iterations, double pcg_tolerance,
+                                           const double* information, const unsigned char* has_information,
+                                           double* switches_out, double report[6]) {
   using namespace nonlinear_optimizer;
   using namespace nonlinear_optimizer::pose_graph_optimizer;
   try {
@@ -182,7 +203,11 @@ extern "C" int nos_host_pgo_solve(size_t n_poses, const int* pose_indices, doubl
       c.query_pose_index = qry_index[e];
       c.relative_pose_from_reference_to_query = to_pose(meas + 7 * e);
       c.type = is_loop[e] ? ConstraintType::kLoop : ConstraintType::kOdometry;
+      const size_t before = optimizer.NumConstraints();
       optimizer.SetConstraint(c);
+      // a dropped constraint ("Constraint is invalid.") has no position: its matrix goes with it, the later ones keep theirs
+      if (optimizer.NumConstraints() > before && information != nullptr && (has_information == nullptr || has_information[e]))
+        optimizer.SetConstraintInformation(before, information + 36 * e);
     }
     Options options;
     options.max_iterations = max_iterations;
@@ -217,4 +242,15 @@ extern "C" int nos_host_pgo_solve(size_t n_poses, const int* pose_indices, doubl
   } catch (...) {
     return 0;
   }
+}
+
+extern "C" int nos_host_pgo_solve(size_t n_poses, const int* pose_indices, double* poses /*[n][7] in/out*/,
+                                  size_t n_constraints, const int* ref_index, const int* qry_index,
+                                  const double* meas /*[m][7]*/, const unsigned char* is_loop, size_t n_fixed,
+                                  const int* fixed_indices, int max_iterations, double gradient_tolerance,
+                                  double parameter_tolerance, int pcg_max_iterations, double pcg_tolerance,
+                                  double* switches_out, double report[6]) {
+  return nos_host_pgo_solve_weighted(n_poses, pose_indices, poses, n_constraints, ref_index, qry_index, meas, is_loop, n_fixed,
+                                     fixed_indices, max_iterations, gradient_tolerance, parameter_tolerance, pcg_max_iterations,
+                                     pcg_tolerance, nullptr, nullptr, switches_out, report);
 }

@@ -11,7 +11,9 @@
 #ifndef NOS_PGO_SOLVER_HPP_
 #define NOS_PGO_SOLVER_HPP_
 
+#include <array>
 #include <iostream>
+#include <map>
 #include <memory>
 #include <set>
 #include <unordered_map>
@@ -86,6 +88,22 @@ class PoseGraphOptimizerHip : public PoseGraphOptimizer {
   /// pose_graph_optimizer.h:62-67).
   bool Solve(const Options& options) final;
 
+  /// Constraints registered so far.  SetConstraint drops a constraint whose pose was never registered ("Constraint is
+  /// invalid."), so the position of the constraint just set is NumConstraints() - 1 if the count grew, and it has none
+  /// otherwise: take the index for SetConstraintInformation from here, not from a count of the calls.
+  size_t NumConstraints() const { return constraints_.size(); }
+
+  /// 6 x 6 information matrix (row-major, symmetric, positive semi-definite; the upper triangle is read) of the
+  /// constraint at position constraint_index (see NumConstraints), over the error (dt, dtheta) of its
+  /// relative pose: t_true = t + dt in the reference frame, R_true = R Exp(dtheta) — the rule of nos_pgo_create_weighted
+  /// (include/nos.h).  Kept beside the constraints: the Constraint struct stays the reference's.  Once one constraint
+  /// has information the graph is a weighted one and the constraints without take the identity (the same cost as
+  /// before).  A matrix the library refuses makes Solve return false with the poses unchanged.
+  void SetConstraintInformation(size_t constraint_index, const double information[36]) {
+    std::array<double, 36>& dst = information_[constraint_index];
+    for (int k = 0; k < 36; ++k) dst[k] = information[k];
+  }
+
   const PgoSolveReport& report() const { return report_; }
   /// Optimised switch values of the constraints, in SetConstraint order (1 for odometry constraints).
   const std::vector<double>& switch_parameters() const { return switches_; }
@@ -94,6 +112,7 @@ class PoseGraphOptimizerHip : public PoseGraphOptimizer {
   PgoHipOptions hip_options_;
   PgoSolveReport report_;
   std::vector<double> switches_;
+  std::map<size_t, std::array<double, 36>> information_;  // by position in constraints_
 };
 
 }  // namespace pose_graph_optimizer

@@ -21,18 +21,37 @@ int nos_pgo_destroy(nos_pose_graph* pg) {
 int nos_pgo_create(nos_ctx* ctx, size_t n_poses, const double* poses, size_t n_edges, const int32_t* ref,
                    const int32_t* qry, const double* meas, const double* switch_init,
                    const unsigned char* switch_free, const unsigned char* fixed, nos_pose_graph** out_pg) {
+  return nos_pgo_create_weighted(ctx, n_poses, poses, n_edges, ref, qry, meas, switch_init, switch_free, fixed, nullptr, out_pg);
+}
+
+// information: [n_edges][21], the upper triangle (row-major) of every constraint's 6x6 information matrix in the
+// measurement frame (include/nos.h); NULL = nos_pgo_create.  A graph with information takes the two general paths: the
+// owner-computes product (no block lists) and the probed coarse operator.  A matrix that is not finite, zero or not
+// positive semi-definite is refused before any device work, with *out_pg as the caller left it.
+int nos_pgo_create_weighted(nos_ctx* ctx, size_t n_poses, const double* poses, size_t n_edges, const int32_t* ref,
+                            const int32_t* qry, const double* meas, const double* switch_init,
+                            const unsigned char* switch_free, const unsigned char* fixed, const double* information,
+                            nos_pose_graph** out_pg) {
   nosd::CtxGuard guard_(ctx);  // one solve / accumulate / create at a time per context
   if (!ctx || !out_pg) return fail(NOS_ERR_INVALID_ARGUMENT, "ctx / out_pg is NULL");
+  const bool weighted = information != nullptr && n_edges > 0;
+  std::vector<double> packed;
+  if (weighted) {
+    if (n_edges > 0x7FFFFFFFull) return fail(NOS_ERR_INVALID_ARGUMENT, "bad graph size");
+    const long long bad = pgo_pack_information(n_edges, information, &packed);
+    if (bad >= 0)
+      return fail(NOS_ERR_INVALID_ARGUMENT, "the information matrix of constraint %lld is not finite, zero or not positive semi-definite", bad);
+  }
   *out_pg = nullptr;
   if (ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "pose-graph optimisation needs a single-device context");
   if (n_poses == 0 || n_poses > 0x7FFFFFFFull || n_edges > 0x7FFFFFFFull) return fail(NOS_ERR_INVALID_ARGUMENT, "bad graph size");
   if (!poses || (n_edges > 0 && (!ref || !qry || !meas))) return fail(NOS_ERR_INVALID_ARGUMENT, "graph arrays are NULL");
   nos::PgoLayout L;
-  const bool want_blocks = ctx->settings.pgo_block != 0 && n_edges > 0;
+  const bool want_blocks = ctx->settings.pgo_block != 0 && n_edges > 0 && !weighted;
   if (!nos::build_pgo_layout(n_poses, poses, n_edges, ref, qry, meas, switch_init, switch_free, fixed, want_blocks, &L))
     return fail(NOS_ERR_INVALID_ARGUMENT, "constraint %zu has an invalid pose index", L.bad_constraint);  // "Constraint is invalid."
   // block-local product where the lists fit their packing and a workgroup's LDS; owner-computes kernels otherwise
-  const bool blocks = L.blocks_fit && pgo_blocks_fit_lds(ctx, L);
+  const bool blocks = !weighted && L.blocks_fit && pgo_blocks_fit_lds(ctx, L);
   nos_pose_graph* pg = new (std::nothrow) nos_pose_graph();
   if (!pg) return fail(NOS_ERR_OUT_OF_MEMORY, "host allocation failed");
   pg->ctx = ctx;
@@ -41,7 +60,7 @@ int nos_pgo_create(nos_ctx* ctx, size_t n_poses, const double* poses, size_t n_e
   pg->n_unknowns = size_t(6) * L.n_poses + L.n_edges;
   pg->n_free_switches = L.n_free_switches;
   pg->partial_blocks = std::max<uint32_t>(kPgoDotBlocks, (L.n_poses + 255) / 256 + (L.n_edges + 255) / 256 + 2);
-  const hipError_t e = pgo_upload_graph(pg, L, ref, qry, blocks);
+  const hipError_t e = pgo_upload_graph(pg, L, ref, qry, blocks, weighted ? &packed : nullptr);
   if (e != hipSuccess) {
     nos_pgo_destroy(pg);
     return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "pose-graph upload failed: %s", hipGetErrorString(e));

@@ -23,6 +23,7 @@ struct nos_pose_graph {
   double* d_pose = nullptr;       // [n_poses][8]: px py pz qw qx qy qz pad
   int32_t *d_ref = nullptr, *d_qry = nullptr;
   double* d_edge = nullptr;       // [n_edges][8]: t_m (3) q_m wxyz (4) switch (1)
+  double* d_info = nullptr;       // [n_edges][24]: Omega' = D Omega D, 21 upper entries + 3 pads (nos_pgo_create_weighted); NULL: unweighted
   uint8_t *d_sw_free = nullptr, *d_fixed = nullptr;
   uint32_t *d_adj_off = nullptr, *d_adj = nullptr, *d_adj_nbr = nullptr;
   // linear system
@@ -94,6 +95,71 @@ hipError_t pgo_upload(nos_pose_graph* pg, T** out, const std::vector<T>& host) {
   return pgo_upload(pg, out, host.data(), host.size());
 }
 
+// ---- information matrices (nos_pgo_create_weighted)
+
+// Eigenvalues of a symmetric 6x6 by cyclic Jacobi rotations (host; a dozen sweeps reach float64 rounding).  The matrix is
+// divided by its largest |entry| first and the eigenvalues scaled back: the convergence test squares entries, and those of
+// a finite matrix above 1e154 would overflow it (the loop would leave at once and hand back the diagonal).
+inline void pgo_sym6_eigenvalues(const double A_in[36], double ev[6]) {
+  double A[6][6], top = 0.0;
+  for (int k = 0; k < 36; ++k) top = std::max(top, std::fabs(A_in[k]));
+  if (!(top > 0.0)) {
+    for (int a = 0; a < 6; ++a) ev[a] = 0.0;
+    return;
+  }
+  for (int a = 0; a < 6; ++a)
+    for (int b = 0; b < 6; ++b) A[a][b] = A_in[6 * a + b] / top;
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    double off = 0.0, diag = 0.0;
+    for (int a = 0; a < 6; ++a)
+      for (int b = 0; b < 6; ++b) (a == b ? diag : off) += A[a][b] * A[a][b];
+    if (!(off > 1e-40 * diag)) break;
+    for (int p = 0; p < 5; ++p)
+      for (int q = p + 1; q < 6; ++q) {
+        if (A[p][q] == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < 6; ++k) {  // columns p, q
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = c * akp - s * akq;
+          A[k][q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < 6; ++k) {  // rows p, q
+          const double apk = A[p][k], aqk = A[q][k];
+          A[p][k] = c * apk - s * aqk;
+          A[q][k] = s * apk + c * aqk;
+        }
+      }
+  }
+  for (int a = 0; a < 6; ++a) ev[a] = A[a][a] * top;
+}
+
+// information: [n_edges][21] upper triangles, row-major.  → -1 when every matrix is finite, not zero and positive
+// semi-definite (smallest eigenvalue >= -1e-12 x the largest), else the index of the first constraint that is not;
+// packed: [n_edges][24] records of Omega' = D Omega D, D = diag(I, -I) (pgo_kernels.hpp), pads zero.
+inline long long pgo_pack_information(size_t n_edges, const double* information, std::vector<double>* packed) {
+  packed->assign(n_edges * 24, 0.0);
+  for (size_t e = 0; e < n_edges; ++e) {
+    const double* u = information + 21 * e;
+    double A[36], ev[6];
+    bool finite = true, zero = true;
+    int k = 0;
+    for (int a = 0; a < 6; ++a)
+      for (int b = a; b < 6; ++b, ++k) {
+        finite = finite && std::isfinite(u[k]);
+        zero = zero && u[k] == 0.0;
+        A[6 * a + b] = A[6 * b + a] = u[k];
+        (*packed)[24 * e + k] = (a < 3 && b >= 3) ? -u[k] : u[k];
+      }
+    if (!finite || zero) return (long long)e;
+    pgo_sym6_eigenvalues(A, ev);
+    const double lo = *std::min_element(ev, ev + 6), hi = *std::max_element(ev, ev + 6);
+    if (!(hi > 0.0) || lo < -1e-12 * hi) return (long long)e;
+  }
+  return -1;
+}
+
 // LDS of the block-local product (pgo_matvec_block_kernel<128, 256>): 14 doubles per own and halo pose, 6 per slot.
 // halo_cap / slot_cap are the capacities the kernel is launched with: the largest halo rounded up to 8, the largest slot
 // count but at least 256 (the tail's sum re-uses the slots: >= 1024 doubles).
@@ -155,7 +221,7 @@ inline hipError_t pgo_upload_blocks(nos_pose_graph* pg, const nos::PgoLayout& L)
 // Everything a graph holds on the device, from its layout; `blocks`: with the lists of the block-local product.  Separate
 // allocations in a fixed order: the kernels' speed has been measured with these addresses, not with an arena's.
 inline hipError_t pgo_upload_graph(nos_pose_graph* pg, const nos::PgoLayout& L, const int32_t* ref, const int32_t* qry,
-                                   bool blocks) {
+                                   bool blocks, const std::vector<double>* information = nullptr) {
   const uint32_t N = L.n_poses, M = L.n_edges;
   hipError_t e = hipSetDevice(pg->ctx->slots[0].device);
   if (e == hipSuccess) e = pgo_upload(pg, &pg->d_pose, L.pose_rec);
@@ -168,6 +234,7 @@ inline hipError_t pgo_upload_graph(nos_pose_graph* pg, const nos::PgoLayout& L, 
   if (e == hipSuccess && blocks) e = pgo_upload_blocks(pg, L);
   if (e == hipSuccess) e = pgo_upload(pg, &pg->d_ref, ref, M);
   if (e == hipSuccess) e = pgo_upload(pg, &pg->d_qry, qry, M);
+  if (e == hipSuccess && information != nullptr) e = pgo_upload(pg, &pg->d_info, *information);  // behind the unweighted graph's buffers
   auto zeroed = [&](double** p, size_t count) {
     if (e == hipSuccess) e = pgo_alloc(pg, p, count);
     if (e == hipSuccess) e = hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(double));
@@ -233,6 +300,14 @@ inline int pgo_dot(nos_pose_graph* pg, const double* a, const double* b, double*
 // Diagonal blocks, gradient, switch curvature and the block partials of the cost (one row per workgroup of the first launch).
 inline void pgo_launch_linearize(nos_pose_graph* pg) {
   DeviceSlot& slot = pg->ctx->slots[0];
+  if (pg->d_info != nullptr) {  // constraints with information: the weighted siblings
+    hipLaunchKernelGGL(nos::pgo_linearize_weighted_kernel, dim3((pg->n_poses + 255) / 256), dim3(256), 0, slot.stream, pg->view,
+                       pg->d_info, pg->d_hdiag, pg->d_grad, pg->d_partials);
+    if (pg->n_edges > 0)
+      hipLaunchKernelGGL(nos::pgo_switch_linearize_weighted_kernel, dim3((pg->n_edges + 255) / 256), dim3(256), 0, slot.stream,
+                         pg->view, pg->d_info, pg->d_grad + size_t(6) * pg->n_poses, pg->d_hs);
+    return;
+  }
   hipLaunchKernelGGL(nos::pgo_linearize_kernel, dim3((pg->n_poses + 255) / 256), dim3(256), 0, slot.stream, pg->view,
                      pg->d_hdiag, pg->d_grad, pg->d_partials);
   if (pg->n_edges > 0)
@@ -268,7 +343,11 @@ inline int pgo_launch_product(nos_pose_graph* pg, double lambda, const double* x
   } else {
     const uint32_t pose_blocks = (pg->n_poses + 255) / 256;
     const uint32_t mv_blocks = pose_blocks + (switch_rows ? (pg->n_edges + 255) / 256 : 0u);
-    hipLaunchKernelGGL(nos::pgo_matvec_cg_kernel, dim3(mv_blocks), dim3(256), 0, slot.stream, pg->view, pg->d_hdiag, pg->d_hs,
+    if (pg->d_info != nullptr)
+      hipLaunchKernelGGL(nos::pgo_matvec_cg_weighted_kernel, dim3(mv_blocks), dim3(256), 0, slot.stream, pg->view, pg->d_info,
+                         pg->d_hdiag, pg->d_hs, lambda, x, y, pose_blocks, tail);
+    else
+      hipLaunchKernelGGL(nos::pgo_matvec_cg_kernel, dim3(mv_blocks), dim3(256), 0, slot.stream, pg->view, pg->d_hdiag, pg->d_hs,
                        lambda, x, y, pose_blocks, tail);
   }
   NOS_HIP_CHECK(hipGetLastError());
@@ -343,7 +422,7 @@ inline int pgo_coarse_setup(nos_pose_graph* pg, double lambda, uint32_t agg) {
   const uint32_t N = pg->n_poses, C = pg->n_agg;
   const uint32_t pose_blocks = (N + 255) / 256, cblocks = (C + 127) / 128;
   const size_t N6 = size_t(6) * N;
-  if (pg->ctx->settings.pgo_coarse_probe == 0) {
+  if (pg->ctx->settings.pgo_coarse_probe == 0 && pg->d_info == nullptr) {
     // the three block diagonals of A_c = P^T H' P, assembled directly: one sweep over the constraints each
     const dim3 grid((C + 3) / 4);
     hipLaunchKernelGGL(nos::pgo_coarse_assemble_kernel<0>, grid, dim3(256), 0, slot.stream, pg->view, pg->d_hdiag, lambda, agg, C,
@@ -353,15 +432,21 @@ inline int pgo_coarse_setup(nos_pose_graph* pg, double lambda, uint32_t agg) {
     hipLaunchKernelGGL(nos::pgo_coarse_assemble_kernel<2>, grid, dim3(256), 0, slot.stream, pg->view, pg->d_hdiag, lambda, agg, C,
                        pg->c_U[0]);
   } else {
-    // round 2's way, kept for comparison (option pgo_coarse_probe): A_c probed with 18 masked matrix-free products
+    // round 2's way, kept for comparison (option pgo_coarse_probe) and the way of every graph with information (the
+    // sigma / P / Q structure of the direct assembly does not survive a general Omega): A_c probed with 18 masked
+    // matrix-free products
     NOS_HIP_CHECK(hipMemsetAsync(pg->c_L[0], 0, size_t(3) * 36 * C * sizeof(double), slot.stream));  // L, D, U of buffer 0
     NOS_HIP_CHECK(hipMemsetAsync(pg->d_p + N6, 0, size_t(pg->n_edges) * sizeof(double), slot.stream));  // switch part of the probe
     for (int colour = 0; colour < 3; ++colour)
       for (int dof = 0; dof < 6; ++dof) {
         hipLaunchKernelGGL(nos::pgo_coarse_probe_kernel, dim3(pose_blocks), dim3(256), 0, slot.stream, pg->view, agg, colour, dof,
                            pg->d_p);
-        hipLaunchKernelGGL(nos::pgo_matvec_pose_kernel, dim3(pose_blocks), dim3(256), 0, slot.stream, pg->view, pg->d_hdiag,
-                           lambda, pg->d_p, pg->d_p + N6, pg->d_ap, pg->d_partials, agg);
+        if (pg->d_info != nullptr)
+          hipLaunchKernelGGL(nos::pgo_matvec_pose_weighted_kernel, dim3(pose_blocks), dim3(256), 0, slot.stream, pg->view,
+                             pg->d_info, pg->d_hdiag, lambda, pg->d_p, pg->d_p + N6, pg->d_ap, pg->d_partials, agg);
+        else
+          hipLaunchKernelGGL(nos::pgo_matvec_pose_kernel, dim3(pose_blocks), dim3(256), 0, slot.stream, pg->view, pg->d_hdiag,
+                             lambda, pg->d_p, pg->d_p + N6, pg->d_ap, pg->d_partials, agg);
         hipLaunchKernelGGL(nos::pgo_coarse_restrict_kernel, dim3((C + 3) / 4), dim3(256), 0, slot.stream, pg->view, agg, C,
                            pg->d_ap, pg->c_b[0]);
         hipLaunchKernelGGL(nos::pgo_coarse_scatter_kernel, dim3(cblocks), dim3(128), 0, slot.stream, C, colour, dof, pg->c_b[0],

@@ -1116,4 +1116,346 @@ __global__ __launch_bounds__(256) void pgo_retract_kernel(uint32_t n_poses, uint
   }
 }
 
+// ---- constraints weighted by a 6x6 information matrix (include/nos.h, nos_pgo_create_weighted)
+//
+// The information Omega of a constraint is over the error (dt, dtheta) of its MEASUREMENT, t_true = t_m + dt in the
+// reference frame, R_true = R_m Exp(dtheta).  The residual it weighs is therefore the measurement-frame one,
+//     r~ = (u - t_m, r_R),   u = R_r^T (p_q - p_r),   r_R = 2 vec(q_q^* q_r q_m)  (= -dtheta to first order),
+// not the world-frame r_t of the unweighted kernels above: rotating Omega into the world frame at the current estimate
+// would freeze R_r in the weight and drop a Jacobian term of the size of the residual.  Jacobians under p += dp,
+// q <- q Exp(dw):
+//     d r~ / d x_r = [ -R_r^T  [u]x ]      d r~ / d x_q = [ R_r^T  0 ]
+//                    [  0       B   ]                     [ 0      C ]
+// with B, C as above.  What is stored per constraint is Omega' = D Omega D, D = diag(I, -I) (the sign of r_R against
+// dtheta, applied once on the host): 24 doubles = the 21 upper entries row-major + three pads = three 64-byte lines, the
+// file's rule for gathered data.  Cost s^2 r~^T Omega' r~ (+ (1 - s)^2 c^2); g_i += s^2 J~^T Omega' r~;
+// H_ii += s^2 J~^T Omega' J~; product v = s (J~_i x_i + J~_j x_j) + r~ x_s, out += s J~^T Omega' v; switch row
+// (Omega' r~) . s (J~_r x_r + J~_q x_q) + h_s (1 + lambda) x_s with h_s = r~^T Omega' r~ + c^2.
+// These are siblings of the unweighted sweeps, which are untouched: a graph without information runs the code above.
+// With Omega = I the cost and the gradient are those of the unweighted graph (|r~| = |r|, J~^T r~ = J^T r); the diagonal
+// blocks are not — the Jacobians belong to another residual with the same norm.
+
+struct WeightedEdgeTerms {
+  double r[6];   // unscaled residual (u - t_m, r_R)
+  double Rt[9];  // R_r^T
+  double u[3];   // R_r^T (p_q - p_r)
+  double B[9];   // d r_R / d w_r
+  double C[9];   // d r_R / d w_q
+};
+
+__device__ __forceinline__ double weighted_edge_terms(const PgoView& G, uint32_t e, uint32_t ir, uint32_t iq,
+                                                      WeightedEdgeTerms& T) {
+  double pr[8], pq[8], ed[8];
+  load_record(G.pose, ir, pr);
+  load_record(G.pose, iq, pq);
+  load_record(G.edge, e, ed);
+  const Quat4 qr{pr[3], pr[4], pr[5], pr[6]};
+  const Quat4 qq{pq[3], pq[4], pq[5], pq[6]};
+  const Quat4 qm{ed[3], ed[4], ed[5], ed[6]};
+  double Rr[9], Rm[9];
+  qrot_matrix(qr, Rr);
+  qrot_matrix(qm, Rm);
+  const double d[3] = {pq[0] - pr[0], pq[1] - pr[1], pq[2] - pr[2]};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) T.Rt[3 * i + j] = Rr[3 * j + i];
+    T.u[i] = Rr[i] * d[0] + Rr[3 + i] * d[1] + Rr[6 + i] * d[2];
+    T.r[i] = T.u[i] - ed[i];
+  }
+  const Quat4 qqc{qq.w, -qq.x, -qq.y, -qq.z};
+  const Quat4 eq = qmul(qmul(qqc, qr), qm);
+  T.r[3] = 2 * eq.x;
+  T.r[4] = 2 * eq.y;
+  T.r[5] = 2 * eq.z;
+  const double Ep[9] = {eq.w, -eq.z, eq.y, eq.z, eq.w, -eq.x, -eq.y, eq.x, eq.w};
+  T.C[0] = -eq.w;
+  T.C[1] = -eq.z;
+  T.C[2] = eq.y;
+  T.C[3] = eq.z;
+  T.C[4] = -eq.w;
+  T.C[5] = -eq.x;
+  T.C[6] = -eq.y;
+  T.C[7] = eq.x;
+  T.C[8] = -eq.w;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      T.B[3 * i + j] = Ep[3 * i] * Rm[3 * j] + Ep[3 * i + 1] * Rm[3 * j + 1] + Ep[3 * i + 2] * Rm[3 * j + 2];
+  return ed[7];  // current switch value
+}
+
+// The 21 upper entries of constraint e's Omega' (192-byte record as twelve 16-byte loads; the pads are dropped).
+__device__ __forceinline__ void load_information(const double* __restrict__ info, uint32_t e, double (&W)[21]) {
+  using V2 = double __attribute__((ext_vector_type(2)));
+  const V2* p = reinterpret_cast<const V2*>(info + size_t(24) * e);
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+    const V2 t = p[k];
+    W[2 * k] = t[0];
+    W[2 * k + 1] = t[1];
+  }
+  W[20] = p[10][0];
+}
+
+// y = Omega' v  (W: 21 upper entries, row-major)
+__device__ __forceinline__ void apply_information(const double (&W)[21], const double v[6], double y[6]) {
+  const int row0[6] = {0, 6, 11, 15, 18, 20};  // index of the diagonal entry of every row
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    double acc = 0.0;
+#pragma unroll
+    for (int b = 0; b < 6; ++b) acc += (b >= a ? W[row0[a] + (b - a)] : W[row0[b] + (a - b)]) * v[b];
+    y[a] = acc;
+  }
+}
+
+// y = J~_role x
+__device__ __forceinline__ void apply_Jw(const WeightedEdgeTerms& T, int role, const double x[6], double y[6]) {
+  if (role == 0) {
+    const double ux[3] = {T.u[1] * x[5] - T.u[2] * x[4], T.u[2] * x[3] - T.u[0] * x[5], T.u[0] * x[4] - T.u[1] * x[3]};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      y[i] = ux[i] - (T.Rt[3 * i] * x[0] + T.Rt[3 * i + 1] * x[1] + T.Rt[3 * i + 2] * x[2]);
+      y[3 + i] = T.B[3 * i] * x[3] + T.B[3 * i + 1] * x[4] + T.B[3 * i + 2] * x[5];
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      y[i] = T.Rt[3 * i] * x[0] + T.Rt[3 * i + 1] * x[1] + T.Rt[3 * i + 2] * x[2];
+      y[3 + i] = T.C[3 * i] * x[3] + T.C[3 * i + 1] * x[4] + T.C[3 * i + 2] * x[5];
+    }
+  }
+}
+
+// out += scale * J~_role^T y
+__device__ __forceinline__ void add_JwT(const WeightedEdgeTerms& T, int role, const double y[6], double scale,
+                                        double out[6]) {
+  if (role == 0) {
+    const double yu[3] = {y[1] * T.u[2] - y[2] * T.u[1], y[2] * T.u[0] - y[0] * T.u[2], y[0] * T.u[1] - y[1] * T.u[0]};  // [u]x^T y_t
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      out[j] += scale * -(T.Rt[j] * y[0] + T.Rt[3 + j] * y[1] + T.Rt[6 + j] * y[2]);
+      out[3 + j] += scale * (yu[j] + T.B[j] * y[3] + T.B[3 + j] * y[4] + T.B[6 + j] * y[5]);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      out[j] += scale * (T.Rt[j] * y[0] + T.Rt[3 + j] * y[1] + T.Rt[6 + j] * y[2]);
+      out[3 + j] += scale * (T.C[j] * y[3] + T.C[3 + j] * y[4] + T.C[6 + j] * y[5]);
+    }
+  }
+}
+
+// pgo_linearize_kernel with information.  The diagonal block goes column by column: column c of J~^T Omega' J~ is
+// J~^T (Omega' (J~ e_c)) — three 6-vectors live at a time, not a 6x6 of Jacobian columns next to the 21 weights.
+__global__ __launch_bounds__(256) void pgo_linearize_weighted_kernel(PgoView G, const double* __restrict__ info,
+                                                                     double* __restrict__ hdiag, double* __restrict__ grad,
+                                                                     double* __restrict__ cost_partials) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  double cost = 0.0;
+  if (i < G.n_poses) {
+    double H[21], g[6];
+#pragma unroll
+    for (int k = 0; k < 21; ++k) H[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) g[k] = 0.0;
+    const bool fixed = G.fixed[i] != 0;
+    for (uint32_t a = G.adj_off[i]; a < G.adj_off[i + 1]; ++a) {
+      const uint32_t e = G.adj[a] >> 1;
+      const int role = int(G.adj[a] & 1u);
+      const uint32_t j = G.adj_nbr[a];
+      WeightedEdgeTerms T;
+      const double s = weighted_edge_terms(G, e, role == 0 ? i : j, role == 0 ? j : i, T);
+      double W[21], wr[6];
+      load_information(info, e, W);
+      apply_information(W, T.r, wr);
+      if (role == 0) {
+        double rr = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) rr += T.r[k] * wr[k];
+        cost += s * s * rr;
+        if (G.sw_free[e]) cost += (1.0 - s) * (1.0 - s) * kSwitchPrior * kSwitchPrior;
+      }
+      if (fixed) continue;
+      add_JwT(T, role, wr, s * s, g);
+      const int row0[6] = {0, 6, 11, 15, 18, 20};
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double ec[6] = {0, 0, 0, 0, 0, 0}, jc[6], wc[6], col[6] = {0, 0, 0, 0, 0, 0};
+        ec[c] = 1.0;
+        apply_Jw(T, role, ec, jc);
+        apply_information(W, jc, wc);
+        add_JwT(T, role, wc, s * s, col);
+#pragma unroll
+        for (int r0 = 0; r0 <= c; ++r0) H[row0[r0] + (c - r0)] += col[r0];
+      }
+    }
+    if (fixed) {  // identity block keeps the system SPD; the gradient of a fixed pose is zero
+      const int dg[6] = {0, 6, 11, 15, 18, 20};
+#pragma unroll
+      for (int k = 0; k < 6; ++k) H[dg[k]] = 1.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 21; ++k) hdiag[size_t(k) * G.n_poses + i] = H[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) grad[size_t(6) * i + k] = g[k];
+  }
+  __shared__ double lds[4];
+  const double bs = pgo_block_sum256(cost, lds);  // the fixed order of pgo_linearize_kernel's block sum
+  if (threadIdx.x == 0) cost_partials[blockIdx.x] = bs;
+}
+
+// pgo_switch_linearize_kernel with information: gradient s r~^T Omega' r~ - c^2 (1 - s), curvature r~^T Omega' r~ + c^2.
+__global__ __launch_bounds__(256) void pgo_switch_linearize_weighted_kernel(PgoView G, const double* __restrict__ info,
+                                                                            double* __restrict__ g_s,
+                                                                            double* __restrict__ h_s) {
+  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= G.n_edges) return;
+  if (!G.sw_free[e]) {
+    g_s[e] = 0.0;
+    h_s[e] = 1.0;
+    return;
+  }
+  WeightedEdgeTerms T;
+  const double s = weighted_edge_terms(G, e, uint32_t(G.ref[e]), uint32_t(G.qry[e]), T);
+  double W[21], wr[6];
+  load_information(info, e, W);
+  apply_information(W, T.r, wr);
+  double rr = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) rr += T.r[k] * wr[k];
+  g_s[e] = s * rr - kSwitchPrior * kSwitchPrior * (1.0 - s);
+  h_s[e] = rr + kSwitchPrior * kSwitchPrior;
+}
+
+// pgo_matvec_pose_row with information (mask_agg as there: the operator the coarse level is probed with).
+__device__ __forceinline__ double pgo_matvec_pose_row_weighted(const PgoView& G, const double* __restrict__ info,
+                                                               const double* __restrict__ hdiag, double lambda,
+                                                               const double* __restrict__ x, const double* __restrict__ xs,
+                                                               double* __restrict__ y, uint32_t mask_agg, uint32_t i) {
+  const size_t N = G.n_poses;
+  double xy = 0.0;
+  if (i >= G.n_poses) return xy;
+  double xi[6], out[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) xi[k] = x[size_t(6) * i + k];
+  if (G.fixed[i]) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      out[k] = (1.0 + lambda) * xi[k];
+      y[size_t(6) * i + k] = out[k];
+      xy += xi[k] * out[k];
+    }
+    return xy;
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) out[k] = 0.0;
+  for (uint32_t a = G.adj_off[i]; a < G.adj_off[i + 1]; ++a) {
+    const uint32_t e = G.adj[a] >> 1;
+    const int role = int(G.adj[a] & 1u);
+    const uint32_t j = G.adj_nbr[a];
+    WeightedEdgeTerms T;
+    const double s = weighted_edge_terms(G, e, role == 0 ? i : j, role == 0 ? j : i, T);
+    double W[21];
+    load_information(info, e, W);
+    double xj[6], v[6], vj[6], wv[6];
+    bool jfixed = G.fixed[j] != 0;
+    if (mask_agg != 0) {
+      const uint32_t ai = i / mask_agg, aj = j / mask_agg;
+      jfixed = jfixed || ai > aj + 1u || aj > ai + 1u;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) xj[k] = jfixed ? 0.0 : x[size_t(6) * j + k];
+    apply_Jw(T, role, xi, v);
+    apply_Jw(T, 1 - role, xj, vj);
+    const double xse = G.sw_free[e] ? xs[e] : 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] = s * (v[k] + vj[k]) + T.r[k] * xse;
+    apply_information(W, v, wv);
+    add_JwT(T, role, wv, s, out);
+  }
+  const int dg[6] = {0, 6, 11, 15, 18, 20};
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const double v = out[k] + lambda * hdiag[size_t(dg[k]) * N + i] * xi[k];
+    y[size_t(6) * i + k] = v;
+    xy += xi[k] * v;
+  }
+  return xy;
+}
+
+// pgo_matvec_switch_row with information.
+__device__ __forceinline__ double pgo_matvec_switch_row_weighted(const PgoView& G, const double* __restrict__ info,
+                                                                 const double* __restrict__ h_s, double lambda,
+                                                                 const double* __restrict__ x, const double* __restrict__ xs,
+                                                                 double* __restrict__ ys, uint32_t e) {
+  if (e >= G.n_edges) return 0.0;
+  double out;
+  if (!G.sw_free[e]) {
+    out = (1.0 + lambda) * xs[e];
+  } else {
+    const uint32_t ir = uint32_t(G.ref[e]), iq = uint32_t(G.qry[e]);
+    WeightedEdgeTerms T;
+    const double s = weighted_edge_terms(G, e, ir, iq, T);
+    double W[21], wr[6], xr[6], xq[6], vr[6], vq[6];
+    load_information(info, e, W);
+    apply_information(W, T.r, wr);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      xr[k] = G.fixed[ir] ? 0.0 : x[size_t(6) * ir + k];
+      xq[k] = G.fixed[iq] ? 0.0 : x[size_t(6) * iq + k];
+    }
+    apply_Jw(T, 0, xr, vr);
+    apply_Jw(T, 1, xq, vq);
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) acc += wr[k] * (s * (vr[k] + vq[k]));
+    out = acc + h_s[e] * (1.0 + lambda) * xs[e];
+  }
+  ys[e] = out;
+  return xs[e] * out;
+}
+
+// pgo_matvec_pose_kernel with information (the probing products of the coarse level).
+__global__ __launch_bounds__(256) void pgo_matvec_pose_weighted_kernel(PgoView G, const double* __restrict__ info,
+                                                                       const double* __restrict__ hdiag, double lambda,
+                                                                       const double* __restrict__ x,
+                                                                       const double* __restrict__ xs, double* __restrict__ y,
+                                                                       double* __restrict__ dot_partials, uint32_t mask_agg) {
+  const double xy = pgo_matvec_pose_row_weighted(G, info, hdiag, lambda, x, xs, y, mask_agg, blockIdx.x * 256 + threadIdx.x);
+  __shared__ double lds[4];
+  const double bs = pgo_block_sum256(xy, lds);
+  if (threadIdx.x == 0) dot_partials[blockIdx.x] = bs;
+}
+
+// pgo_matvec_cg_kernel with information: the product of one PCG iteration with its in-launch tail (p.Ap, alpha).
+__global__ __launch_bounds__(256) void pgo_matvec_cg_weighted_kernel(PgoView G, const double* __restrict__ info,
+                                                                     const double* __restrict__ hdiag,
+                                                                     const double* __restrict__ h_s, double lambda,
+                                                                     const double* __restrict__ x, double* __restrict__ y,
+                                                                     uint32_t pose_blocks, PgoTail tail) {
+  const size_t N6 = size_t(6) * G.n_poses;
+  double xy;
+  if (blockIdx.x < pose_blocks)
+    xy = pgo_matvec_pose_row_weighted(G, info, hdiag, lambda, x, x + N6, y, 0u, blockIdx.x * 256 + threadIdx.x);
+  else
+    xy = pgo_matvec_switch_row_weighted(G, info, h_s, lambda, x, x + N6, y + N6, (blockIdx.x - pose_blocks) * 256 + threadIdx.x);
+  __shared__ double lds[1024];
+  __shared__ unsigned int last_flag;
+  const double bs = pgo_block_sum256(xy, lds);
+  if (threadIdx.x == 0) {
+    const double v[1] = {bs};
+    pgo_publish_partials<1>(tail, v);
+  }
+  if (!pgo_tail_is_last(tail, &last_flag)) return;
+  double total[1];
+  pgo_sum_rows<256, 1>(tail.partials, gridDim.x, lds, total);
+  if (threadIdx.x == 0) {
+    tail.scalars[0] = total[0];
+    pgo_cg_alpha(tail.scalars);
+  }
+}
+
 }  // namespace nos

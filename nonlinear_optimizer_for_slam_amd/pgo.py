@@ -13,10 +13,41 @@ def _dp(a):
     return a.ctypes.data_as(c_double_p)
 
 
-class PoseGraph:
-    """Device-resident pose graph (nos_pose_graph).  poses [n,7] = px py pz qw qx qy qz, meas [m,7] likewise."""
+_UPPER = np.triu_indices(6)
 
-    def __init__(self, ctx, poses, ref, qry, meas, switch_init=None, switch_free=None, fixed=None):
+
+def information_from_sums(sums):
+    """The 6x6 information matrix of a pose-graph edge from an accumulate6 / map_to_map result (its 21 numbers H, upper
+    triangle row-major, in front of b and the cost): sums [>= 21] → [6, 6] symmetric.  At the pose a registration returns,
+    target = reference and source = query, H is the information of that relative pose in the convention of
+    PoseGraph(information=...) as it stands (include/nos.h, nos_pgo_create_weighted)."""
+    h = np.asarray(sums, dtype=np.float64).reshape(-1)[:21]
+    if h.size != 21:
+        raise ValueError("sums holds fewer than 21 numbers")
+    out = np.zeros((6, 6))
+    out[_UPPER] = h
+    return out + np.triu(out, 1).T
+
+
+def pack_information(information, m):
+    """[m, 6, 6] (symmetric; the upper triangle is read) or [m, 21] → contiguous [m, 21], upper triangle row-major."""
+    a = np.asarray(information, dtype=np.float64)
+    if a.shape == (m, 6, 6):
+        if not np.array_equal(a, np.swapaxes(a, 1, 2)):
+            raise ValueError("information matrices must be symmetric")
+        a = a[:, _UPPER[0], _UPPER[1]]
+    elif a.shape != (m, 21):
+        raise ValueError("information must be [m, 6, 6] or [m, 21] for m = %d constraints, got %r" % (m, a.shape))
+    return np.ascontiguousarray(a)
+
+
+class PoseGraph:
+    """Device-resident pose graph (nos_pose_graph).  poses [n,7] = px py pz qw qx qy qz, meas [m,7] likewise.
+    information: [m, 6, 6] or [m, 21] (upper triangle row-major) — one information matrix per constraint over the error
+    (dt, dtheta) of its measurement, t_true = t_m + dt, R_true = R_m Exp(dtheta) (nos_pgo_create_weighted in
+    include/nos.h states the rule); None: every constraint weighs |r|^2 (nos_pgo_create)."""
+
+    def __init__(self, ctx, poses, ref, qry, meas, switch_init=None, switch_free=None, fixed=None, information=None):
         self._ctx = ctx
         self._lib = ctx._lib
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
@@ -29,9 +60,16 @@ class PoseGraph:
         swf = None if switch_free is None else np.ascontiguousarray(switch_free, dtype=np.uint8).tobytes()
         fx = None if fixed is None else np.ascontiguousarray(fixed, dtype=np.uint8).tobytes()
         h = ctypes.c_void_p()
-        check(self._lib.nos_pgo_create(ctx.handle, self.n_poses, _dp(poses), self.n_edges, ref.ctypes.data_as(ip),
-                                       qry.ctypes.data_as(ip), _dp(meas), None if sw is None else _dp(sw), swf, fx,
-                                       ctypes.byref(h)), "nos_pgo_create")
+        if information is None:
+            check(self._lib.nos_pgo_create(ctx.handle, self.n_poses, _dp(poses), self.n_edges, ref.ctypes.data_as(ip),
+                                           qry.ctypes.data_as(ip), _dp(meas), None if sw is None else _dp(sw), swf, fx,
+                                           ctypes.byref(h)), "nos_pgo_create")
+        else:
+            info = pack_information(information, self.n_edges)
+            check(self._lib.nos_pgo_create_weighted(ctx.handle, self.n_poses, _dp(poses), self.n_edges,
+                                                    ref.ctypes.data_as(ip), qry.ctypes.data_as(ip), _dp(meas),
+                                                    None if sw is None else _dp(sw), swf, fx, _dp(info), ctypes.byref(h)),
+                  "nos_pgo_create_weighted")
         self._h = h
         ctx._adopt(self)
 
@@ -148,9 +186,11 @@ class PoseGraphOptimizerHip:
     def SetPose(self, pose_index, pose7):
         self._poses[int(pose_index)] = pose7  # kept by reference, overwritten on success
 
-    def SetConstraint(self, reference_pose_index, query_pose_index, relative_pose7, is_loop=False):
+    def SetConstraint(self, reference_pose_index, query_pose_index, relative_pose7, is_loop=False, information=None):
+        """information: 6 x 6 (SetConstraintInformation of the C++ class; the rule of PoseGraph(information=...))."""
+        info = None if information is None else np.array(information, dtype=np.float64).reshape(36)
         self._constraints.append((int(reference_pose_index), int(query_pose_index),
-                                  np.asarray(relative_pose7, dtype=np.float64).reshape(7), bool(is_loop)))
+                                  np.asarray(relative_pose7, dtype=np.float64).reshape(7), bool(is_loop), info))
 
     def SetPoseConstant(self, pose_index):
         self._fixed.append(int(pose_index))
@@ -168,12 +208,17 @@ class PoseGraphOptimizerHip:
         sw = np.ones(max(m, 1))
         rep = np.zeros(6)
         ip = ctypes.POINTER(ctypes.c_int)
-        ok = host_lib().nos_host_pgo_solve(
-            ctypes.c_size_t(idx.size), idx.ctypes.data_as(ip), _dp(poses), ctypes.c_size_t(m), ref.ctypes.data_as(ip),
-            qry.ctypes.data_as(ip), _dp(meas), loop, ctypes.c_size_t(fixed.size), fixed.ctypes.data_as(ip),
-            ctypes.c_int(options.max_iterations), ctypes.c_double(options.gradient_tolerance),
-            ctypes.c_double(options.parameter_tolerance), ctypes.c_int(self.pcg_max_iterations),
-            ctypes.c_double(self.pcg_tolerance), _dp(sw), _dp(rep))
+        head = (ctypes.c_size_t(idx.size), idx.ctypes.data_as(ip), _dp(poses), ctypes.c_size_t(m), ref.ctypes.data_as(ip),
+                qry.ctypes.data_as(ip), _dp(meas), loop, ctypes.c_size_t(fixed.size), fixed.ctypes.data_as(ip),
+                ctypes.c_int(options.max_iterations), ctypes.c_double(options.gradient_tolerance),
+                ctypes.c_double(options.parameter_tolerance), ctypes.c_int(self.pcg_max_iterations),
+                ctypes.c_double(self.pcg_tolerance))
+        has = np.array([c[4] is not None for c in self._constraints], dtype=np.uint8)
+        if has.any():
+            info = np.ascontiguousarray(np.stack([np.zeros(36) if c[4] is None else c[4] for c in self._constraints]))
+            ok = host_lib().nos_host_pgo_solve_weighted(*head, _dp(info), has.tobytes(), _dp(sw), _dp(rep))
+        else:
+            ok = host_lib().nos_host_pgo_solve(*head, _dp(sw), _dp(rep))
         self.report = {"iterations": int(rep[0]), "initial_cost": rep[1], "final_cost": rep[2],
                        "final_gradient_norm": rep[3], "total_pcg_iterations": int(rep[4]), "status": int(rep[5])}
         if ok:

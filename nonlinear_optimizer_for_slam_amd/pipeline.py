@@ -246,6 +246,39 @@ def map_to_map(ctx, target, source, initial_pose=None, loss=("exponential", 1.0,
     return pose, rounds, outer, info
 
 
+def _quat_wxyz(R):
+    """Unit quaternion (w x y z, w >= 0) of a rotation matrix: the largest of the four components from the diagonal, the
+    other three from the off-diagonal sums and differences."""
+    R = np.asarray(R, dtype=np.float64).reshape(3, 3)
+    d = np.array([R[0, 0] + R[1, 1] + R[2, 2], R[0, 0] - R[1, 1] - R[2, 2], R[1, 1] - R[0, 0] - R[2, 2],
+                  R[2, 2] - R[0, 0] - R[1, 1]])
+    k = int(np.argmax(d))
+    q = np.zeros(4)
+    q[k] = 0.5 * np.sqrt(1.0 + d[k])
+    f = 0.25 / q[k]
+    if k == 0:
+        q[1:] = (R[2, 1] - R[1, 2]) * f, (R[0, 2] - R[2, 0]) * f, (R[1, 0] - R[0, 1]) * f
+    else:
+        i, j, l = k - 1, k % 3, (k + 1) % 3
+        q[0] = (R[l, j] - R[j, l]) * f
+        q[1 + j] = (R[j, i] + R[i, j]) * f
+        q[1 + l] = (R[l, i] + R[i, l]) * f
+    q /= np.linalg.norm(q)
+    return -q if q[0] < 0.0 else q
+
+
+def map_edge(ctx, target, source, guess=None, **map_to_map_kwargs):
+    """A pose-graph edge between two submaps: map_to_map(ctx, target, source, guess, **map_to_map_kwargs) and the packing
+    pgo.PoseGraph takes.  → {"meas": pose7 = px py pz qw qx qy qz of the source (query) in the frame of the target
+    (reference), "information": 6 x 6 = pgo.information_from_sums(info["sums"]) — the normal matrix of the registration
+    at that pose, which is the information of the measurement in PoseGraph's convention as it stands (include/nos.h),
+    "matches": info["matches"], "rounds": map_to_map's rounds}."""
+    from .pgo import information_from_sums
+    pose, rounds, _, info = map_to_map(ctx, target, source, guess, **map_to_map_kwargs)
+    meas = np.concatenate([np.asarray(pose.t, dtype=np.float64).reshape(3), _quat_wxyz(pose.R)])
+    return {"meas": meas, "information": information_from_sums(info["sums"]), "matches": info["matches"], "rounds": rounds}
+
+
 def scan_to_map_batch(ctx, ndt_map, scans, initial_poses=None, loss=("exponential", 1.0, 1.0), options=None,
                       max_outer_iterations=10, dof=6, dtype="f64", keep_multiple=None):
     """scan_to_map for many scans against one map in ONE launch (api.register6_batch / register3_batch): the outer loop
