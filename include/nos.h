@@ -1100,6 +1100,38 @@ int nos_pgo_create_weighted(nos_ctx* ctx, size_t n_poses, const double* poses, s
                             const int32_t* ref, const int32_t* qry, const double* meas,
                             const double* switch_init, const unsigned char* switch_free,
                             const unsigned char* fixed, const double* information, nos_pose_graph** out_pg);
+/* A robust loss on the constraints of a graph WITH information: the back end's defence against a wrong loop closure that
+ * no switch was declared for.
+ * THE RULE.  For constraint e, with r~, Omega', J~, s as above, q = r~^T Omega' r~, c the switch prior, rho the loss and
+ * w = rho'(q):
+ *   cost      s^2 rho(q) (+ (1 - s)^2 c^2);
+ *   gradient  g_i += s^2 w J~^T Omega' r~;         diagonal blocks  H_ii += s^2 w J~^T Omega' J~;
+ *   product   v = s (J~_i x_i + J~_j x_j) + r~ x_s,  out += s w J~^T Omega' v;
+ *   switches  row w (Omega' r~) . s (J~_r x_r + J~_q x_q) + h_s (1 + lambda) x_s,
+ *             g_s = s rho(q) - c^2 (1 - s),  h_s = rho(q) + c^2.
+ * Iteratively reweighted Gauss-Newton without a second-order (Triggs) correction, as in the NDT solvers: rho and w are
+ * evaluated once per nos_pgo_linearize and stay fixed through the products and solves that follow.  The 2 x 2 Schur
+ * complement of a switch is rho + c^2 - w q (a projection <= 1); a concave rho with rho(0) = 0 has rho(q) >= q rho'(q),
+ * so the matrix stays positive semi-definite and neither kind below needs a guard.
+ *   NOS_LOSS_NONE                        rho = q,  w = 1;
+ *   NOS_LOSS_HUBER (a = delta)           q <= delta^2: rho = q, w = 1;  else rho = 2 delta sqrt(q) - delta^2, w = delta / sqrt(q);
+ *   NOS_LOSS_EXPONENTIAL (a = c1, b = c2)  rho = c1 - c1 exp(-c2 q),  w = c1 c2 exp(-c2 q).
+ * THE WEIGHT IS THE DERIVATIVE OF THE COST THAT IS REPORTED.  For the exponential kind that is HALF the output[1] =
+ * 2 c1 c2 exp(-c2 q) of the reference's loss_function.h:31, which the NDT entry points above follow for parity with the
+ * reference's captured runs; the pose graph has no captured run to follow, and with the doubled weight the gradient is not
+ * the gradient of the cost.  exp, sqrt and the division are the accurate library ones (one evaluation per constraint and
+ * linearisation).
+ * robust: [n_edges] flags of the constraints the loss applies to (usually the loop closures), NULL = all; a constraint
+ * that is not flagged has rho = q, w = 1.  The flags are copied.
+ * Callable at any time, any number of times; loss == NULL or kind NONE removes the loss.  It takes effect at the NEXT
+ * nos_pgo_linearize: nos_pgo_matvec / nos_pgo_solve / nos_pgo_precondition before that keep the weights of the last
+ * linearisation — an annealed schedule (large threshold first, then smaller) is a loop of set_loss, linearize, solve,
+ * retract in the caller.  A graph with information and no loss computes the bits it computed before this call existed, and
+ * so does one whose loss never leaves its quadratic zone (Huber with a huge delta).
+ * NOS_ERR_INVALID_ARGUMENT, the graph's loss unchanged: an unknown kind; a Huber threshold that is not finite or <= 0;
+ * exponential c1 or c2 not finite or < 0.  NOS_ERR_UNSUPPORTED: a loss (other than NONE) on a graph created without
+ * information — create it with identity matrices. */
+int nos_pgo_set_loss(nos_pose_graph* pg, const nos_loss* loss, const unsigned char* robust /*[n_edges] or NULL*/);
 int nos_pgo_destroy(nos_pose_graph* pg);
 size_t nos_pgo_num_unknowns(const nos_pose_graph* pg); /* 6 n_poses + n_edges */
 int nos_pgo_linearize(nos_pose_graph* pg, double* cost, double* gradient_norm);
@@ -1108,7 +1140,9 @@ int nos_pgo_solve(nos_pose_graph* pg, double lambda, int max_iterations, double 
 int nos_pgo_retract(nos_pose_graph* pg);
 int nos_pgo_get_state(nos_pose_graph* pg, double* poses, double* switches);
 /* which: 0 gradient, 1 last step (both 6 planes of n_poses then n_edges switch entries),
- * 2 diagonal blocks (21 planes of n_poses, upper triangle row-major).  Diagnostics. */
+ * 2 diagonal blocks (21 planes of n_poses, upper triangle row-major), 3 the weight w of every constraint at the last
+ * nos_pgo_linearize (n_edges values: 1.0 where no loss applied, all ones on a graph without information or without a
+ * loss) — how a caller sees which loop closures the loss has rejected.  Diagnostics. */
 int nos_pgo_get_vector(nos_pose_graph* pg, int which, double* out);
 /* y = (J^T J with its diagonal scaled by 1 + lambda) x for host vectors.  Diagnostics. */
 int nos_pgo_matvec(nos_pose_graph* pg, double lambda, const double* x, double* y);

@@ -33,7 +33,7 @@ C_ABI_SYMBOLS = (
     "nos_scan_destroy", "nos_scan_size", "nos_scan_sort_by_cell", "nos_scan_order", "nos_scan_filter", "nos_scan_points", "nos_scan_deskew", "nos_scan_descriptor", "nos_place_db_create", "nos_place_db_destroy", "nos_place_db_size", "nos_place_db_add", "nos_place_db_add_scan", "nos_place_db_get", "nos_place_db_search", "nos_place_db_search_scan", "nos_ndt_match", "nos_ndt_indexed_dataset_create", "nos_ndt_match_indexed", "nos_indexed_dataset_info", "nos_indexed_dataset_download", "nos_ndt_map_build", "nos_map_stats_size",
     "nos_map_stats_get", "nos_map_stats_get_eigen", "nos_map_stats_destroy",
     "nos_voxel_map_create", "nos_voxel_map_insert", "nos_voxel_map_insert_scan", "nos_voxel_map_info", "nos_voxel_map_snapshot",
-    "nos_voxel_map_stats", "nos_voxel_map_match", "nos_voxel_map_match_indexed", "nos_voxel_map_prune", "nos_voxel_map_carve", "nos_voxel_map_raycast", "nos_voxel_map_memory", "nos_voxel_map_merge", "nos_voxel_map_match_map", "nos_voxel_map_export", "nos_voxel_state_size", "nos_voxel_state_info", "nos_voxel_state_get", "nos_voxel_state_destroy", "nos_voxel_map_import", "nos_voxel_map_destroy", "nos_dataset_drop_last_matches", "nos_pgo_create", "nos_pgo_create_weighted", "nos_pgo_destroy", "nos_pgo_num_unknowns",
+    "nos_voxel_map_stats", "nos_voxel_map_match", "nos_voxel_map_match_indexed", "nos_voxel_map_prune", "nos_voxel_map_carve", "nos_voxel_map_raycast", "nos_voxel_map_memory", "nos_voxel_map_merge", "nos_voxel_map_match_map", "nos_voxel_map_export", "nos_voxel_state_size", "nos_voxel_state_info", "nos_voxel_state_get", "nos_voxel_state_destroy", "nos_voxel_map_import", "nos_voxel_map_destroy", "nos_dataset_drop_last_matches", "nos_pgo_create", "nos_pgo_create_weighted", "nos_pgo_set_loss", "nos_pgo_destroy", "nos_pgo_num_unknowns",
     "nos_pgo_linearize", "nos_pgo_solve", "nos_pgo_retract", "nos_pgo_get_state", "nos_pgo_get_vector",
     "nos_pgo_matvec", "nos_pgo_precondition", "nos_pgo_time_sweep", "nos_pgo_layout_info", "nos_debug_lm_step", "nos_debug_voxel_finish", "nos_debug_voxel_moments", "nos_debug_voxel_pair_information", "nos_dataset_destroy", "nos_dataset_size", "nos_dataset_dtype", "nos_dataset_stream_bytes",
     "nos_dataset_set_simd_class",
@@ -258,6 +258,8 @@ def _declare(lib):
     lib.nos_pgo_create.argtypes = [vp, sz, dp, sz, ip, ip, dp, dp, ctypes.c_char_p, ctypes.c_char_p, c_void_pp]
     if hasattr(lib, "nos_pgo_create_weighted"):  # absent from older builds loaded through NOS_HIP_LIB
         lib.nos_pgo_create_weighted.argtypes = [vp, sz, dp, sz, ip, ip, dp, dp, ctypes.c_char_p, ctypes.c_char_p, dp, c_void_pp]
+    if hasattr(lib, "nos_pgo_set_loss"):  # absent from older builds loaded through NOS_HIP_LIB
+        lib.nos_pgo_set_loss.argtypes = [vp, ctypes.POINTER(NosLoss), ctypes.c_char_p]
     lib.nos_pgo_destroy.argtypes = [vp]
     lib.nos_pgo_num_unknowns.argtypes = [vp]
     lib.nos_pgo_num_unknowns.restype = sz

@@ -40,6 +40,15 @@ bool PoseGraphOptimizerHip::Solve(const Options& options) {
 #endif
   report_ = PgoSolveReport();
   if (ordered.empty()) return false;
+  // SetLossFunction: the loss goes to every constraint, as the reference's Ceres path hands it to every residual block
+  nos_loss loss;
+  if (!DescribeLossFunction(loss_function_.get(), &loss)) {
+    std::cerr << "[nos-hip] unsupported LossFunction subclass: only Exponential and Huber have a device "
+                 "restatement and there is no CPU fallback"
+              << std::endl;
+    report_.status = NOS_ERR_UNSUPPORTED;
+    return false;
+  }
   // compact pose indices (the reference keys poses by arbitrary ints)
   std::map<int, int> slot_of;
   std::vector<double> poses(7 * ordered.size());
@@ -66,10 +75,11 @@ bool PoseGraphOptimizerHip::Solve(const Options& options) {
     sw_free[e] = (c.type == ConstraintType::kLoop) ? 1 : 0;  // pose_graph_optimizer_ceres.cc:29-36
   }
 
-  // information set for some constraint: 21 upper entries per constraint, identity where none was given
+  // information set for some constraint, or a loss (which lives on graphs with information): 21 upper entries per
+  // constraint, identity where none was given
   std::vector<double> information;
-  if (!information_.empty()) {
-    if (information_.rbegin()->first >= m) {
+  if (!information_.empty() || (loss.kind != NOS_LOSS_NONE && m > 0)) {
+    if (!information_.empty() && information_.rbegin()->first >= m) {
       std::cerr << "[nos-hip] SetConstraintInformation: constraint " << information_.rbegin()->first << " of " << m
                 << " was never registered.\n";
       report_.status = NOS_ERR_INVALID_ARGUMENT;
@@ -90,10 +100,12 @@ bool PoseGraphOptimizerHip::Solve(const Options& options) {
   if (status == NOS_OK)
     status = nos_pgo_create_weighted(ctx, ordered.size(), poses.data(), m, ref.data(), qry.data(), meas.data(), sw.data(),
                                      sw_free.data(), fixed.data(), information.empty() ? nullptr : information.data(), &pg);
+  if (status == NOS_OK && loss.kind != NOS_LOSS_NONE && m > 0) status = nos_pgo_set_loss(pg, &loss, nullptr);
   if (status != NOS_OK) {
     std::cerr << "[nos-hip] pose-graph setup failed: " << nos_status_string(status) << " — " << nos_last_error()
               << std::endl;
     report_.status = status;
+    if (pg != nullptr) nos_pgo_destroy(pg);
     if (ctx != nullptr) nos_ctx_destroy(ctx);
     return false;
   }
@@ -163,15 +175,23 @@ bool PoseGraphOptimizerHip::Solve(const Options& options) {
 // ---- C entry point for the Python test-suite: builds Pose / Constraint objects and calls the class ----
 // information: [m][36] row-major, or NULL; has_information: [m] flags (NULL: every constraint has), SetConstraintInformation
 // is called for the flagged ones.
-extern "C" int nos_host_pgo_solve_weighted(size_t n_poses, const int* pose_indices, double* poses /*[n][7] in/out*/,
-                                           size_t n_constraints, const int* ref_index, const int* qry_index,
-                                           const double* meas /*[m][7]*/, const unsigned char* is_loop, size_t n_fixed,
-                                           const int* fixed_indices, int max_iterations, double gradient_tolerance,
-                                           double parameter_tolerance, int pcg_max_iterations, double pcg_tolerance,
-                                           const double* information, const unsigned char* has_information,
-                                           double* switches_out, double report[6]) {
+// loss_kind: nos_loss_kind (a = c1 | threshold, b = c2) → SetLossFunction with the reference's class; any other value
+// sets a LossFunction subclass the library has no device restatement of (Solve then refuses).
+extern "C" int nos_host_pgo_solve_robust(size_t n_poses, const int* pose_indices, double* poses /*[n][7] in/out*/,
+                                         size_t n_constraints, const int* ref_index, const int* qry_index,
+                                         const double* meas /*[m][7]*/, const unsigned char* is_loop, size_t n_fixed,
+                                         const int* fixed_indices, int max_iterations, double gradient_tolerance,
+                                         double parameter_tolerance, int pcg_max_iterations, double pcg_tolerance,
+                                         const double* information, const unsigned char* has_information, int loss_kind,
+                                         double loss_a, double loss_b, double* switches_out, double report[6]) {
   using namespace nonlinear_optimizer;
   using namespace nonlinear_optimizer::pose_graph_optimizer;
+  struct UnknownLoss final : LossFunction {
+    void Evaluate(const double squared_residual, double* output) final {
+      output[0] = squared_residual;
+      output[1] = 1.0;
+    }
+  };
   try {
     auto to_pose = [](const double* p) {
       Pose pose = Pose::Identity();
@@ -195,6 +215,12 @@ extern "C" int nos_host_pgo_solve_weighted(size_t n_poses, const int* pose_indic
     hip.pcg_relative_tolerance = pcg_tolerance;
     hip.print_summary = false;
     PoseGraphOptimizerHip optimizer(hip);
+    if (loss_kind == NOS_LOSS_EXPONENTIAL)
+      optimizer.SetLossFunction(std::make_shared<ExponentialLossFunction>(loss_a, loss_b));
+    else if (loss_kind == NOS_LOSS_HUBER)
+      optimizer.SetLossFunction(std::make_shared<HuberLossFunction>(loss_a));
+    else if (loss_kind != NOS_LOSS_NONE)
+      optimizer.SetLossFunction(std::make_shared<UnknownLoss>());
     for (size_t i = 0; i < n_poses; ++i) optimizer.SetPose(pose_indices[i], &pose_objects[i]);
     for (size_t i = 0; i < n_fixed; ++i) optimizer.SetPoseConstant(fixed_indices[i]);
     for (size_t e = 0; e < n_constraints; ++e) {
@@ -242,6 +268,18 @@ extern "C" int nos_host_pgo_solve_weighted(size_t n_poses, const int* pose_indic
   } catch (...) {
     return 0;
   }
+}
+
+extern "C" int nos_host_pgo_solve_weighted(size_t n_poses, const int* pose_indices, double* poses /*[n][7] in/out*/,
+                                           size_t n_constraints, const int* ref_index, const int* qry_index,
+                                           const double* meas /*[m][7]*/, const unsigned char* is_loop, size_t n_fixed,
+                                           const int* fixed_indices, int max_iterations, double gradient_tolerance,
+                                           double parameter_tolerance, int pcg_max_iterations, double pcg_tolerance,
+                                           const double* information, const unsigned char* has_information,
+                                           double* switches_out, double report[6]) {
+  return nos_host_pgo_solve_robust(n_poses, pose_indices, poses, n_constraints, ref_index, qry_index, meas, is_loop, n_fixed,
+                                   fixed_indices, max_iterations, gradient_tolerance, parameter_tolerance, pcg_max_iterations,
+                                   pcg_tolerance, information, has_information, NOS_LOSS_NONE, 0.0, 0.0, switches_out, report);
 }
 
 extern "C" int nos_host_pgo_solve(size_t n_poses, const int* pose_indices, double* poses /*[n][7] in/out*/,

@@ -7,7 +7,9 @@
 // check convergence, with the LM bookkeeping of the reference's other analytic solvers (always step,
 // lambda x2 / x0.6 on the cost, clamp [1e-6, 1e-2], convergence tested after the update).  Odometry
 // constraints keep switch 1; loop constraints carry a free switch variable exactly as the Ceres path sets
-// them up (pose_graph_optimizer_ceres.cc:29-42).
+// them up (pose_graph_optimizer_ceres.cc:29-42).  SetLossFunction is honoured: the loss (Exponential or Huber; another
+// subclass makes Solve return false) goes to every constraint through nos_pgo_set_loss, on q = r~^T Omega' r~ of the
+// measurement-frame residual — a graph none of whose constraints has information takes the identity for all of them.
 #ifndef NOS_PGO_SOLVER_HPP_
 #define NOS_PGO_SOLVER_HPP_
 

@@ -71,6 +71,51 @@ int nos_pgo_create_weighted(nos_ctx* ctx, size_t n_poses, const double* poses, s
 
 size_t nos_pgo_num_unknowns(const nos_pose_graph* pg) { return pg ? pg->n_unknowns : 0; }
 
+// The robust loss the NEXT nos_pgo_linearize applies (include/nos.h states the rule).  Nothing is launched here: products,
+// solves and preconditioner applications until then keep the weights of the last linearisation.  A refused call leaves
+// the loss and the flags as they were.
+int nos_pgo_set_loss(nos_pose_graph* pg, const nos_loss* loss, const unsigned char* robust) {
+  nosd::CtxGuard guard_(pg ? pg->ctx : nullptr);  // one solve / accumulate / create at a time per context
+  if (!pg) return fail(NOS_ERR_INVALID_ARGUMENT, "pg is NULL");
+  nos_loss want{NOS_LOSS_NONE, 0, 0.0, 0.0};
+  if (loss != nullptr) {
+    if (loss->kind == NOS_LOSS_HUBER) {
+      if (!std::isfinite(loss->a) || !(loss->a > 0.0))
+        return fail(NOS_ERR_INVALID_ARGUMENT, "pose-graph loss: the Huber threshold must be finite and > 0, got %g", loss->a);
+      want = nos_loss{NOS_LOSS_HUBER, 0, loss->a, 0.0};
+    } else if (loss->kind == NOS_LOSS_EXPONENTIAL) {
+      if (!std::isfinite(loss->a) || !std::isfinite(loss->b) || loss->a < 0.0 || loss->b < 0.0)
+        return fail(NOS_ERR_INVALID_ARGUMENT, "pose-graph loss: exponential c1, c2 must be finite and >= 0, got %g, %g", loss->a,
+                    loss->b);
+      want = nos_loss{NOS_LOSS_EXPONENTIAL, 0, loss->a, loss->b};
+    } else if (loss->kind != NOS_LOSS_NONE) {
+      return fail(NOS_ERR_INVALID_ARGUMENT, "pose-graph loss: unknown kind %d", int(loss->kind));
+    }
+  }
+  if (want.kind == NOS_LOSS_NONE) {  // removing the loss is fine on any graph
+    pg->loss = want;
+    pg->robust_flags = false;
+    return NOS_OK;
+  }
+  if (pg->d_info == nullptr)
+    return fail(NOS_ERR_UNSUPPORTED,
+                "a robust loss needs a pose graph with information: pass identity matrices to nos_pgo_create_weighted");
+  if (robust != nullptr) {
+    DeviceSlot& slot = pg->ctx->slots[0];
+    NOS_HIP_CHECK(hipSetDevice(slot.device));
+    if (pg->d_robust == nullptr) {
+      const hipError_t e = pgo_alloc(pg, &pg->d_robust, pg->n_edges);
+      if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "pose-graph loss flags: %s", hipGetErrorString(e));
+    }
+    NOS_HIP_CHECK(hipStreamSynchronize(slot.stream));  // no weights kernel is reading the old flags
+    NOS_HIP_CHECK(hipMemcpy(pg->d_robust, robust, pg->n_edges, hipMemcpyHostToDevice));
+  }
+  pg->robust_flags = robust != nullptr;
+  pg->loss = want;
+  return NOS_OK;
+}
+
 // Linearise at the current estimate: diagonal blocks, gradient, cost = sum of squared residuals,
 // |gradient|_2.  Must precede nos_pgo_solve / nos_pgo_matvec.
 int nos_pgo_linearize(nos_pose_graph* pg, double* cost, double* gradient_norm) {
@@ -149,12 +194,29 @@ int nos_pgo_get_state(nos_pose_graph* pg, double* poses, double* switches) {
   return NOS_OK;
 }
 
-// Diagnostics for the parity tests: which = 0 gradient, 1 last step, 2 diagonal blocks (21 planes).
+// Diagnostics for the parity tests: which = 0 gradient, 1 last step, 2 diagonal blocks (21 planes), 3 the robust weight
+// of every constraint at the last linearisation (n_edges values; 1.0 where no loss applied).
 int nos_pgo_get_vector(nos_pose_graph* pg, int which, double* out) {
   nosd::CtxGuard guard_(pg ? pg->ctx : nullptr);  // one solve / accumulate / create at a time per context
   if (!pg || !out) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
   NOS_HIP_CHECK(hipSetDevice(pg->ctx->slots[0].device));
   NOS_HIP_CHECK(hipStreamSynchronize(pg->ctx->slots[0].stream));
+  if (which == 3) {
+    const size_t M = pg->n_edges;
+    if (pg->d_info == nullptr || !pg->lin_robust) {
+      for (size_t e = 0; e < M; ++e) out[e] = 1.0;
+      return NOS_OK;
+    }
+    // entry 21 of every 24-double record, a slab of records at a time
+    constexpr size_t kSlab = 65536;
+    std::vector<double> rec(std::min(M, kSlab) * 24);
+    for (size_t e0 = 0; e0 < M; e0 += kSlab) {
+      const size_t count = std::min(kSlab, M - e0);
+      NOS_HIP_CHECK(hipMemcpy(rec.data(), pg->d_info + 24 * e0, count * 24 * sizeof(double), hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < count; ++k) out[e0 + k] = rec[24 * k + 21];
+    }
+    return NOS_OK;
+  }
   const double* src = which == 0 ? pg->d_grad : which == 1 ? pg->d_x : pg->d_hdiag;
   if (which == 2) {
     NOS_HIP_CHECK(hipMemcpy(out, src, size_t(21) * pg->n_poses * sizeof(double), hipMemcpyDeviceToHost));

@@ -24,6 +24,12 @@ struct nos_pose_graph {
   int32_t *d_ref = nullptr, *d_qry = nullptr;
   double* d_edge = nullptr;       // [n_edges][8]: t_m (3) q_m wxyz (4) switch (1)
   double* d_info = nullptr;       // [n_edges][24]: Omega' = D Omega D, 21 upper entries + 3 pads (nos_pgo_create_weighted); NULL: unweighted
+  // robust loss (nos_pgo_set_loss): `loss` is what the NEXT linearisation will apply; `lin_robust` says whether the last one
+  // applied one, that is, whether entries 21 / 22 of the Omega' records hold its w / rho and the robust sweeps are to run
+  nos_loss loss{NOS_LOSS_NONE, 0, 0.0, 0.0};
+  uint8_t* d_robust = nullptr;    // [n_edges] flags of the constraints the loss applies to (allocated at the first call with flags)
+  bool robust_flags = false;      // d_robust is in force (false: the loss applies to every constraint)
+  bool lin_robust = false;
   uint8_t *d_sw_free = nullptr, *d_fixed = nullptr;
   uint32_t *d_adj_off = nullptr, *d_adj = nullptr, *d_adj_nbr = nullptr;
   // linear system
@@ -300,6 +306,19 @@ inline int pgo_dot(nos_pose_graph* pg, const double* a, const double* b, double*
 // Diagonal blocks, gradient, switch curvature and the block partials of the cost (one row per workgroup of the first launch).
 inline void pgo_launch_linearize(nos_pose_graph* pg) {
   DeviceSlot& slot = pg->ctx->slots[0];
+  if (pg->d_info != nullptr && pg->loss.kind != NOS_LOSS_NONE) {  // … under a robust loss: rho and w once, then the robust siblings
+    pg->lin_robust = true;
+    if (pg->n_edges > 0)
+      hipLaunchKernelGGL(nos::pgo_robust_weights_kernel, dim3((pg->n_edges + 255) / 256), dim3(256), 0, slot.stream, pg->view,
+                         pg->d_info, pg->loss, pg->robust_flags ? pg->d_robust : static_cast<const uint8_t*>(nullptr));
+    hipLaunchKernelGGL(nos::pgo_linearize_robust_kernel, dim3((pg->n_poses + 255) / 256), dim3(256), 0, slot.stream, pg->view,
+                       pg->d_info, pg->d_hdiag, pg->d_grad, pg->d_partials);
+    if (pg->n_edges > 0)
+      hipLaunchKernelGGL(nos::pgo_switch_linearize_robust_kernel, dim3((pg->n_edges + 255) / 256), dim3(256), 0, slot.stream,
+                         pg->view, pg->d_info, pg->d_grad + size_t(6) * pg->n_poses, pg->d_hs);
+    return;
+  }
+  pg->lin_robust = false;
   if (pg->d_info != nullptr) {  // constraints with information: the weighted siblings
     hipLaunchKernelGGL(nos::pgo_linearize_weighted_kernel, dim3((pg->n_poses + 255) / 256), dim3(256), 0, slot.stream, pg->view,
                        pg->d_info, pg->d_hdiag, pg->d_grad, pg->d_partials);
@@ -343,7 +362,10 @@ inline int pgo_launch_product(nos_pose_graph* pg, double lambda, const double* x
   } else {
     const uint32_t pose_blocks = (pg->n_poses + 255) / 256;
     const uint32_t mv_blocks = pose_blocks + (switch_rows ? (pg->n_edges + 255) / 256 : 0u);
-    if (pg->d_info != nullptr)
+    if (pg->d_info != nullptr && pg->lin_robust)  // the weights of the last linearisation, whatever nos_pgo_set_loss said since
+      hipLaunchKernelGGL(nos::pgo_matvec_cg_robust_kernel, dim3(mv_blocks), dim3(256), 0, slot.stream, pg->view, pg->d_info,
+                         pg->d_hdiag, pg->d_hs, lambda, x, y, pose_blocks, tail);
+    else if (pg->d_info != nullptr)
       hipLaunchKernelGGL(nos::pgo_matvec_cg_weighted_kernel, dim3(mv_blocks), dim3(256), 0, slot.stream, pg->view, pg->d_info,
                          pg->d_hdiag, pg->d_hs, lambda, x, y, pose_blocks, tail);
     else
@@ -441,7 +463,10 @@ inline int pgo_coarse_setup(nos_pose_graph* pg, double lambda, uint32_t agg) {
       for (int dof = 0; dof < 6; ++dof) {
         hipLaunchKernelGGL(nos::pgo_coarse_probe_kernel, dim3(pose_blocks), dim3(256), 0, slot.stream, pg->view, agg, colour, dof,
                            pg->d_p);
-        if (pg->d_info != nullptr)
+        if (pg->d_info != nullptr && pg->lin_robust)  // the operator the solve multiplies by, or the preconditioner is another matrix's
+          hipLaunchKernelGGL(nos::pgo_matvec_pose_robust_kernel, dim3(pose_blocks), dim3(256), 0, slot.stream, pg->view,
+                             pg->d_info, pg->d_hdiag, lambda, pg->d_p, pg->d_p + N6, pg->d_ap, pg->d_partials, agg);
+        else if (pg->d_info != nullptr)
           hipLaunchKernelGGL(nos::pgo_matvec_pose_weighted_kernel, dim3(pose_blocks), dim3(256), 0, slot.stream, pg->view,
                              pg->d_info, pg->d_hdiag, lambda, pg->d_p, pg->d_p + N6, pg->d_ap, pg->d_partials, agg);
         else

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/nos.h"  // nos_loss (pgo_robust_weights_kernel)
 #include "assemble_kernels.hpp"
 #include "pgo_layout.hpp"  // packing constants of the block lists (kPgoNoSlot), shared with the host-side builder
 
@@ -1199,6 +1200,22 @@ __device__ __forceinline__ void load_information(const double* __restrict__ info
   W[20] = p[10][0];
 }
 
+// The same loads, keeping what they already fetch of the first pad: entry 21 = the robust weight w of the constraint at
+// the last linearisation (pgo_robust_weights_kernel) — the upper half of the eleventh 16-byte piece.
+__device__ __forceinline__ double load_information_weight(const double* __restrict__ info, uint32_t e, double (&W)[21]) {
+  using V2 = double __attribute__((ext_vector_type(2)));
+  const V2* p = reinterpret_cast<const V2*>(info + size_t(24) * e);
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+    const V2 t = p[k];
+    W[2 * k] = t[0];
+    W[2 * k + 1] = t[1];
+  }
+  const V2 t = p[10];
+  W[20] = t[0];
+  return t[1];
+}
+
 // y = Omega' v  (W: 21 upper entries, row-major)
 __device__ __forceinline__ void apply_information(const double (&W)[21], const double v[6], double y[6]) {
   const int row0[6] = {0, 6, 11, 15, 18, 20};  // index of the diagonal entry of every row
@@ -1248,64 +1265,116 @@ __device__ __forceinline__ void add_JwT(const WeightedEdgeTerms& T, int role, co
   }
 }
 
+// ---- robust loss on constraints with information (include/nos.h, nos_pgo_set_loss)
+//
+// q = r~^T Omega' r~ of a constraint goes through a loss rho: cost s^2 rho(q) (+ (1 - s)^2 c^2), and with w = rho'(q) every
+// term above that carries Omega' carries w Omega' — iteratively reweighted Gauss-Newton, no second-order term; the switch
+// takes g_s = s rho - c^2 (1 - s), h_s = rho + c^2.  rho and w are constant between two linearisations, and the product runs
+// hundreds of times in between: pgo_robust_weights_kernel evaluates them once per linearisation into two of the three pads
+// of the constraint's 24-double Omega' record (entry 21 = w, entry 22 = rho).  The record's third 64-byte line is fetched
+// by every reader of Omega' anyway (entry 20 lies in it), so a sweep pays one multiply per visit and no memory traffic.
+// w is folded into the scalar the sweeps already multiply by (s^2 w, s w): with w = 1 that scalar has the bits of s^2, s,
+// and a loss that never leaves its quadratic zone gives the bits of no loss.
+// The weight is the derivative of the cost that is reported: for the exponential kind c1 c2 exp(-c2 q), HALF the
+// 2 c1 c2 exp(-c2 q) the NDT kernels take over from the reference's loss_function.h.
+// ROBUST = false below is the weighted rule as it was.
+
+// One lane per constraint: q → (rho, w) into the pads of its Omega' record.  robust: per-constraint flags, NULL = all;
+// a constraint that is not flagged keeps rho = q, w = 1.  exp, sqrt and the division are the correctly rounded-ish library
+// ones: one evaluation per constraint and linearisation.
+__global__ __launch_bounds__(256) void pgo_robust_weights_kernel(PgoView G, double* __restrict__ info, nos_loss loss,
+                                                                 const uint8_t* __restrict__ robust) {
+  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= G.n_edges) return;
+  WeightedEdgeTerms T;
+  (void)weighted_edge_terms(G, e, uint32_t(G.ref[e]), uint32_t(G.qry[e]), T);
+  double W[21], wr[6];
+  load_information(info, e, W);
+  apply_information(W, T.r, wr);
+  double q = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) q += T.r[k] * wr[k];
+  double rho = q, w = 1.0;
+  if (robust == nullptr || robust[e] != 0) {
+    if (loss.kind == NOS_LOSS_HUBER) {
+      if (q > loss.a * loss.a) {
+        const double root = sqrt(q);
+        rho = 2.0 * loss.a * root - loss.a * loss.a;
+        w = loss.a / root;
+      }
+    } else if (loss.kind == NOS_LOSS_EXPONENTIAL) {
+      const double ex = exp(-loss.b * q);
+      rho = loss.a - loss.a * ex;
+      w = loss.a * loss.b * ex;
+    }
+  }
+  info[size_t(24) * e + 21] = w;
+  info[size_t(24) * e + 22] = rho;
+}
+
 // pgo_linearize_kernel with information.  The diagonal block goes column by column: column c of J~^T Omega' J~ is
 // J~^T (Omega' (J~ e_c)) — three 6-vectors live at a time, not a 6x6 of Jacobian columns next to the 21 weights.
-__global__ __launch_bounds__(256) void pgo_linearize_weighted_kernel(PgoView G, const double* __restrict__ info,
-                                                                     double* __restrict__ hdiag, double* __restrict__ grad,
-                                                                     double* __restrict__ cost_partials) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  double cost = 0.0;
-  if (i < G.n_poses) {
-    double H[21], g[6];
-#pragma unroll
-    for (int k = 0; k < 21; ++k) H[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) g[k] = 0.0;
-    const bool fixed = G.fixed[i] != 0;
-    for (uint32_t a = G.adj_off[i]; a < G.adj_off[i + 1]; ++a) {
-      const uint32_t e = G.adj[a] >> 1;
-      const int role = int(G.adj[a] & 1u);
-      const uint32_t j = G.adj_nbr[a];
-      WeightedEdgeTerms T;
-      const double s = weighted_edge_terms(G, e, role == 0 ? i : j, role == 0 ? j : i, T);
-      double W[21], wr[6];
-      load_information(info, e, W);
-      apply_information(W, T.r, wr);
-      if (role == 0) {
-        double rr = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) rr += T.r[k] * wr[k];
-        cost += s * s * rr;
-        if (G.sw_free[e]) cost += (1.0 - s) * (1.0 - s) * kSwitchPrior * kSwitchPrior;
-      }
-      if (fixed) continue;
-      add_JwT(T, role, wr, s * s, g);
-      const int row0[6] = {0, 6, 11, 15, 18, 20};
-#pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        double ec[6] = {0, 0, 0, 0, 0, 0}, jc[6], wc[6], col[6] = {0, 0, 0, 0, 0, 0};
-        ec[c] = 1.0;
-        apply_Jw(T, role, ec, jc);
-        apply_information(W, jc, wc);
-        add_JwT(T, role, wc, s * s, col);
-#pragma unroll
-        for (int r0 = 0; r0 <= c; ++r0) H[row0[r0] + (c - r0)] += col[r0];
-      }
-    }
-    if (fixed) {  // identity block keeps the system SPD; the gradient of a fixed pose is zero
-      const int dg[6] = {0, 6, 11, 15, 18, 20};
-#pragma unroll
-      for (int k = 0; k < 6; ++k) H[dg[k]] = 1.0;
-    }
-#pragma unroll
-    for (int k = 0; k < 21; ++k) hdiag[size_t(k) * G.n_poses + i] = H[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) grad[size_t(6) * i + k] = g[k];
+// ONE TEXT, TWO KERNELS, and for this kernel the text is a macro, not a template body under wrappers like the products
+// below: behind one more level of inlining (a whole-kernel body, or only the loop's interior as a helper) the register
+// allocator gives the weighted kernel 256 / 252 VGPRs instead of 234 and another instruction stream.  Stamped here, the
+// weighted kernel has the instructions it had, byte for byte.
+#define NOS_PGO_LINEARIZE_WEIGHTED_KERNEL(NAME, ROBUST) \
+  __global__ __launch_bounds__(256) void NAME(PgoView G, const double* __restrict__ info, double* __restrict__ hdiag,   \
+                                              double* __restrict__ grad, double* __restrict__ cost_partials) {          \
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;                                                                  \
+    double cost = 0.0;                                                                                                  \
+    if (i < G.n_poses) {                                                                                                \
+      double H[21], g[6];                                                                                               \
+      _Pragma("unroll") for (int k = 0; k < 21; ++k) H[k] = 0.0;                                                        \
+      _Pragma("unroll") for (int k = 0; k < 6; ++k) g[k] = 0.0;                                                         \
+      const bool fixed = G.fixed[i] != 0;                                                                               \
+      for (uint32_t a = G.adj_off[i]; a < G.adj_off[i + 1]; ++a) {                                                      \
+        const uint32_t e = G.adj[a] >> 1;                                                                               \
+        const int role = int(G.adj[a] & 1u);                                                                            \
+        const uint32_t j = G.adj_nbr[a];                                                                                \
+        WeightedEdgeTerms T;                                                                                            \
+        const double s = weighted_edge_terms(G, e, role == 0 ? i : j, role == 0 ? j : i, T);                            \
+        double W[21], wr[6];                                                                                            \
+        double w = 1.0; /* ROBUST: rho'(q), folded into the s^2 the sums below are scaled by */                         \
+        if constexpr (ROBUST) w = load_information_weight(info, e, W);                                                  \
+        else load_information(info, e, W);                                                                              \
+        apply_information(W, T.r, wr);                                                                                  \
+        if (role == 0) {                                                                                                \
+          double rr = 0.0;                                                                                              \
+          if constexpr (ROBUST) {                                                                                       \
+            rr = info[size_t(24) * e + 22]; /* rho(q) */                                                                \
+          } else {                                                                                                      \
+            _Pragma("unroll") for (int k = 0; k < 6; ++k) rr += T.r[k] * wr[k];                                         \
+          }                                                                                                             \
+          cost += s * s * rr;                                                                                           \
+          if (G.sw_free[e]) cost += (1.0 - s) * (1.0 - s) * kSwitchPrior * kSwitchPrior;                                \
+        }                                                                                                               \
+        if (fixed) continue;                                                                                            \
+        add_JwT(T, role, wr, ROBUST ? s * s * w : s * s, g);                                                            \
+        const int row0[6] = {0, 6, 11, 15, 18, 20};                                                                     \
+        _Pragma("unroll") for (int c = 0; c < 6; ++c) {                                                                 \
+          double ec[6] = {0, 0, 0, 0, 0, 0}, jc[6], wc[6], col[6] = {0, 0, 0, 0, 0, 0};                                 \
+          ec[c] = 1.0;                                                                                                  \
+          apply_Jw(T, role, ec, jc);                                                                                    \
+          apply_information(W, jc, wc);                                                                                 \
+          add_JwT(T, role, wc, ROBUST ? s * s * w : s * s, col);                                                        \
+          _Pragma("unroll") for (int r0 = 0; r0 <= c; ++r0) H[row0[r0] + (c - r0)] += col[r0];                          \
+        }                                                                                                               \
+      }                                                                                                                 \
+      if (fixed) { /* identity block keeps the system SPD; the gradient of a fixed pose is zero */                      \
+        const int dg[6] = {0, 6, 11, 15, 18, 20};                                                                       \
+        _Pragma("unroll") for (int k = 0; k < 6; ++k) H[dg[k]] = 1.0;                                                   \
+      }                                                                                                                 \
+      _Pragma("unroll") for (int k = 0; k < 21; ++k) hdiag[size_t(k) * G.n_poses + i] = H[k];                           \
+      _Pragma("unroll") for (int k = 0; k < 6; ++k) grad[size_t(6) * i + k] = g[k];                                     \
+    }                                                                                                                   \
+    __shared__ double lds[4];                                                                                           \
+    const double bs = pgo_block_sum256(cost, lds); /* the fixed order of pgo_linearize_kernel's block sum */            \
+    if (threadIdx.x == 0) cost_partials[blockIdx.x] = bs;                                                               \
   }
-  __shared__ double lds[4];
-  const double bs = pgo_block_sum256(cost, lds);  // the fixed order of pgo_linearize_kernel's block sum
-  if (threadIdx.x == 0) cost_partials[blockIdx.x] = bs;
-}
+NOS_PGO_LINEARIZE_WEIGHTED_KERNEL(pgo_linearize_weighted_kernel, false)
+NOS_PGO_LINEARIZE_WEIGHTED_KERNEL(pgo_linearize_robust_kernel, true)
+#undef NOS_PGO_LINEARIZE_WEIGHTED_KERNEL
 
 // pgo_switch_linearize_kernel with information: gradient s r~^T Omega' r~ - c^2 (1 - s), curvature r~^T Omega' r~ + c^2.
 __global__ __launch_bounds__(256) void pgo_switch_linearize_weighted_kernel(PgoView G, const double* __restrict__ info,
@@ -1330,7 +1399,26 @@ __global__ __launch_bounds__(256) void pgo_switch_linearize_weighted_kernel(PgoV
   h_s[e] = rr + kSwitchPrior * kSwitchPrior;
 }
 
+// … under a robust loss: rho(q) in the place of r~^T Omega' r~, gradient s rho - c^2 (1 - s), curvature rho + c^2.  The
+// weights kernel has left rho in the record, so this sibling shares nothing with the one above but its guard: it reads
+// s and rho and derives no residual (no template body here: there is no common text to share).
+__global__ __launch_bounds__(256) void pgo_switch_linearize_robust_kernel(PgoView G, const double* __restrict__ info,
+                                                                          double* __restrict__ g_s, double* __restrict__ h_s) {
+  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= G.n_edges) return;
+  if (!G.sw_free[e]) {
+    g_s[e] = 0.0;
+    h_s[e] = 1.0;
+    return;
+  }
+  const double s = G.edge[size_t(8) * e + 7], rho = info[size_t(24) * e + 22];
+  g_s[e] = s * rho - kSwitchPrior * kSwitchPrior * (1.0 - s);
+  h_s[e] = rho + kSwitchPrior * kSwitchPrior;
+}
+
 // pgo_matvec_pose_row with information (mask_agg as there: the operator the coarse level is probed with).
+// ROBUST: out += (s w) J~^T Omega' v — one multiply per adjacency slot.
+template <bool ROBUST>
 __device__ __forceinline__ double pgo_matvec_pose_row_weighted(const PgoView& G, const double* __restrict__ info,
                                                                const double* __restrict__ hdiag, double lambda,
                                                                const double* __restrict__ x, const double* __restrict__ xs,
@@ -1359,7 +1447,11 @@ __device__ __forceinline__ double pgo_matvec_pose_row_weighted(const PgoView& G,
     WeightedEdgeTerms T;
     const double s = weighted_edge_terms(G, e, role == 0 ? i : j, role == 0 ? j : i, T);
     double W[21];
-    load_information(info, e, W);
+    double sw = s;  // s (w)
+    if constexpr (ROBUST)
+      sw = s * load_information_weight(info, e, W);
+    else
+      load_information(info, e, W);
     double xj[6], v[6], vj[6], wv[6];
     bool jfixed = G.fixed[j] != 0;
     if (mask_agg != 0) {
@@ -1374,7 +1466,7 @@ __device__ __forceinline__ double pgo_matvec_pose_row_weighted(const PgoView& G,
 #pragma unroll
     for (int k = 0; k < 6; ++k) v[k] = s * (v[k] + vj[k]) + T.r[k] * xse;
     apply_information(W, v, wv);
-    add_JwT(T, role, wv, s, out);
+    add_JwT(T, role, wv, sw, out);
   }
   const int dg[6] = {0, 6, 11, 15, 18, 20};
 #pragma unroll
@@ -1386,7 +1478,8 @@ __device__ __forceinline__ double pgo_matvec_pose_row_weighted(const PgoView& G,
   return xy;
 }
 
-// pgo_matvec_switch_row with information.
+// pgo_matvec_switch_row with information.  ROBUST: w (Omega' r~) . s (J~_r x_r + J~_q x_q), w folded into s.
+template <bool ROBUST>
 __device__ __forceinline__ double pgo_matvec_switch_row_weighted(const PgoView& G, const double* __restrict__ info,
                                                                  const double* __restrict__ h_s, double lambda,
                                                                  const double* __restrict__ x, const double* __restrict__ xs,
@@ -1400,7 +1493,11 @@ __device__ __forceinline__ double pgo_matvec_switch_row_weighted(const PgoView& 
     WeightedEdgeTerms T;
     const double s = weighted_edge_terms(G, e, ir, iq, T);
     double W[21], wr[6], xr[6], xq[6], vr[6], vq[6];
-    load_information(info, e, W);
+    double sw = s;  // s (w)
+    if constexpr (ROBUST)
+      sw = s * load_information_weight(info, e, W);
+    else
+      load_information(info, e, W);
     apply_information(W, T.r, wr);
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
@@ -1411,7 +1508,7 @@ __device__ __forceinline__ double pgo_matvec_switch_row_weighted(const PgoView& 
     apply_Jw(T, 1, xq, vq);
     double acc = 0.0;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) acc += wr[k] * (s * (vr[k] + vq[k]));
+    for (int k = 0; k < 6; ++k) acc += wr[k] * (sw * (vr[k] + vq[k]));
     out = acc + h_s[e] * (1.0 + lambda) * xs[e];
   }
   ys[e] = out;
@@ -1419,29 +1516,46 @@ __device__ __forceinline__ double pgo_matvec_switch_row_weighted(const PgoView& 
 }
 
 // pgo_matvec_pose_kernel with information (the probing products of the coarse level).
+template <bool ROBUST>
+__device__ __forceinline__ void pgo_matvec_pose_weighted_body(PgoView G, const double* info,
+                                                              const double* hdiag, double lambda,
+                                                              const double* x, const double* xs,
+                                                              double* y, double* dot_partials,
+                                                              uint32_t mask_agg) {
+  const double xy =
+      pgo_matvec_pose_row_weighted<ROBUST>(G, info, hdiag, lambda, x, xs, y, mask_agg, blockIdx.x * 256 + threadIdx.x);
+  __shared__ double lds[4];
+  const double bs = pgo_block_sum256(xy, lds);
+  if (threadIdx.x == 0) dot_partials[blockIdx.x] = bs;
+}
 __global__ __launch_bounds__(256) void pgo_matvec_pose_weighted_kernel(PgoView G, const double* __restrict__ info,
                                                                        const double* __restrict__ hdiag, double lambda,
                                                                        const double* __restrict__ x,
                                                                        const double* __restrict__ xs, double* __restrict__ y,
                                                                        double* __restrict__ dot_partials, uint32_t mask_agg) {
-  const double xy = pgo_matvec_pose_row_weighted(G, info, hdiag, lambda, x, xs, y, mask_agg, blockIdx.x * 256 + threadIdx.x);
-  __shared__ double lds[4];
-  const double bs = pgo_block_sum256(xy, lds);
-  if (threadIdx.x == 0) dot_partials[blockIdx.x] = bs;
+  pgo_matvec_pose_weighted_body<false>(G, info, hdiag, lambda, x, xs, y, dot_partials, mask_agg);
+}
+__global__ __launch_bounds__(256) void pgo_matvec_pose_robust_kernel(PgoView G, const double* __restrict__ info,
+                                                                     const double* __restrict__ hdiag, double lambda,
+                                                                     const double* __restrict__ x,
+                                                                     const double* __restrict__ xs, double* __restrict__ y,
+                                                                     double* __restrict__ dot_partials, uint32_t mask_agg) {
+  pgo_matvec_pose_weighted_body<true>(G, info, hdiag, lambda, x, xs, y, dot_partials, mask_agg);
 }
 
 // pgo_matvec_cg_kernel with information: the product of one PCG iteration with its in-launch tail (p.Ap, alpha).
-__global__ __launch_bounds__(256) void pgo_matvec_cg_weighted_kernel(PgoView G, const double* __restrict__ info,
-                                                                     const double* __restrict__ hdiag,
-                                                                     const double* __restrict__ h_s, double lambda,
-                                                                     const double* __restrict__ x, double* __restrict__ y,
-                                                                     uint32_t pose_blocks, PgoTail tail) {
+template <bool ROBUST>
+__device__ __forceinline__ void pgo_matvec_cg_weighted_body(PgoView G, const double* info,
+                                                            const double* hdiag, const double* h_s,
+                                                            double lambda, const double* x, double* y,
+                                                            uint32_t pose_blocks, PgoTail tail) {
   const size_t N6 = size_t(6) * G.n_poses;
   double xy;
   if (blockIdx.x < pose_blocks)
-    xy = pgo_matvec_pose_row_weighted(G, info, hdiag, lambda, x, x + N6, y, 0u, blockIdx.x * 256 + threadIdx.x);
+    xy = pgo_matvec_pose_row_weighted<ROBUST>(G, info, hdiag, lambda, x, x + N6, y, 0u, blockIdx.x * 256 + threadIdx.x);
   else
-    xy = pgo_matvec_switch_row_weighted(G, info, h_s, lambda, x, x + N6, y + N6, (blockIdx.x - pose_blocks) * 256 + threadIdx.x);
+    xy = pgo_matvec_switch_row_weighted<ROBUST>(G, info, h_s, lambda, x, x + N6, y + N6,
+                                                (blockIdx.x - pose_blocks) * 256 + threadIdx.x);
   __shared__ double lds[1024];
   __shared__ unsigned int last_flag;
   const double bs = pgo_block_sum256(xy, lds);
@@ -1456,6 +1570,20 @@ __global__ __launch_bounds__(256) void pgo_matvec_cg_weighted_kernel(PgoView G, 
     tail.scalars[0] = total[0];
     pgo_cg_alpha(tail.scalars);
   }
+}
+__global__ __launch_bounds__(256) void pgo_matvec_cg_weighted_kernel(PgoView G, const double* __restrict__ info,
+                                                                     const double* __restrict__ hdiag,
+                                                                     const double* __restrict__ h_s, double lambda,
+                                                                     const double* __restrict__ x, double* __restrict__ y,
+                                                                     uint32_t pose_blocks, PgoTail tail) {
+  pgo_matvec_cg_weighted_body<false>(G, info, hdiag, h_s, lambda, x, y, pose_blocks, tail);
+}
+__global__ __launch_bounds__(256) void pgo_matvec_cg_robust_kernel(PgoView G, const double* __restrict__ info,
+                                                                   const double* __restrict__ hdiag,
+                                                                   const double* __restrict__ h_s, double lambda,
+                                                                   const double* __restrict__ x, double* __restrict__ y,
+                                                                   uint32_t pose_blocks, PgoTail tail) {
+  pgo_matvec_cg_weighted_body<true>(G, info, hdiag, h_s, lambda, x, y, pose_blocks, tail);
 }
 
 }  // namespace nos

@@ -45,9 +45,13 @@ class PoseGraph:
     """Device-resident pose graph (nos_pose_graph).  poses [n,7] = px py pz qw qx qy qz, meas [m,7] likewise.
     information: [m, 6, 6] or [m, 21] (upper triangle row-major) — one information matrix per constraint over the error
     (dt, dtheta) of its measurement, t_true = t_m + dt, R_true = R_m Exp(dtheta) (nos_pgo_create_weighted in
-    include/nos.h states the rule); None: every constraint weighs |r|^2 (nos_pgo_create)."""
+    include/nos.h states the rule); None: every constraint weighs |r|^2 (nos_pgo_create).
+    loss: None | ("huber", delta) | ("exponential", c1, c2) — a robust loss on q = r~^T Omega' r~ (set_loss; the rule is
+    stated at nos_pgo_set_loss in include/nos.h); robust: [m] flags of the constraints it applies to, None = all.  A loss
+    lives on graphs with information: with information=None every constraint takes the identity."""
 
-    def __init__(self, ctx, poses, ref, qry, meas, switch_init=None, switch_free=None, fixed=None, information=None):
+    def __init__(self, ctx, poses, ref, qry, meas, switch_init=None, switch_free=None, fixed=None, information=None,
+                 loss=None, robust=None):
         self._ctx = ctx
         self._lib = ctx._lib
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
@@ -60,6 +64,8 @@ class PoseGraph:
         swf = None if switch_free is None else np.ascontiguousarray(switch_free, dtype=np.uint8).tobytes()
         fx = None if fixed is None else np.ascontiguousarray(fixed, dtype=np.uint8).tobytes()
         h = ctypes.c_void_p()
+        if information is None and loss is not None and self.n_edges > 0:
+            information = np.broadcast_to(np.eye(6), (self.n_edges, 6, 6))
         if information is None:
             check(self._lib.nos_pgo_create(ctx.handle, self.n_poses, _dp(poses), self.n_edges, ref.ctypes.data_as(ip),
                                            qry.ctypes.data_as(ip), _dp(meas), None if sw is None else _dp(sw), swf, fx,
@@ -72,6 +78,30 @@ class PoseGraph:
                   "nos_pgo_create_weighted")
         self._h = h
         ctx._adopt(self)
+        if loss is not None:
+            self.set_loss(loss, robust)
+
+    def set_loss(self, loss, robust=None):
+        """The robust loss from the NEXT linearize() on (nos_pgo_set_loss): None | ("huber", delta) |
+        ("exponential", c1, c2); robust: [m] flags of the constraints it applies to (usually the loop closures), None = all.
+        Products and solves before the next linearize() keep the weights of the last one, so an annealed schedule is a loop
+        of set_loss / linearize / solve / retract."""
+        from .api import make_loss
+        l = make_loss(loss)
+        flags = None
+        if robust is not None:
+            flags = np.ascontiguousarray(robust, dtype=np.uint8).reshape(-1)
+            if flags.size != self.n_edges:
+                raise ValueError("robust must hold one flag per constraint (%d), got %d" % (self.n_edges, flags.size))
+            flags = flags.tobytes() if flags.size else b"\0"
+        check(self._lib.nos_pgo_set_loss(self._h, ctypes.byref(l), flags), "nos_pgo_set_loss")
+
+    def edge_weights(self):
+        """[m]: the weight w = rho'(q) every constraint had at the last linearize() — 1.0 where no loss applies, near 0 for
+        a constraint the loss has rejected."""
+        out = np.ones(max(self.n_edges, 1))
+        check(self._lib.nos_pgo_get_vector(self._h, 3, _dp(out)), "nos_pgo_get_vector")
+        return out[:self.n_edges]
 
     @property
     def n_unknowns(self):
@@ -171,7 +201,8 @@ class PoseGraph:
 
 class PoseGraphOptimizerHip:
     """Python view of the C++ drop-in class (csrc/host/nos_pgo_solver.hpp) with the reference's surface:
-    SetPose(index, pose7) / SetConstraint(ref, qry, rel_pose7, is_loop) / SetPoseConstant(index) / Solve(options).
+    SetPose(index, pose7) / SetConstraint(ref, qry, rel_pose7, is_loop) / SetPoseConstant(index) / SetLossFunction(loss) /
+    Solve(options).
     pose7 = px py pz qw qx qy qz.  After a successful Solve the registered pose arrays hold the optimum."""
 
     def __init__(self, pcg_max_iterations=2000, pcg_tolerance=1e-10):
@@ -182,6 +213,12 @@ class PoseGraphOptimizerHip:
         self.pcg_tolerance = pcg_tolerance
         self.report = None
         self.switch_parameters = None
+        self._loss = None
+
+    def SetLossFunction(self, loss):
+        """loss: None | ("exponential", c1, c2) | ("huber", threshold), applied to every constraint.  Any other tuple stands
+        for a LossFunction subclass the library has no device form of: Solve then returns False."""
+        self._loss = loss
 
     def SetPose(self, pose_index, pose7):
         self._poses[int(pose_index)] = pose7  # kept by reference, overwritten on success
@@ -214,8 +251,20 @@ class PoseGraphOptimizerHip:
                 ctypes.c_double(options.parameter_tolerance), ctypes.c_int(self.pcg_max_iterations),
                 ctypes.c_double(self.pcg_tolerance))
         has = np.array([c[4] is not None for c in self._constraints], dtype=np.uint8)
+        info = None
         if has.any():
             info = np.ascontiguousarray(np.stack([np.zeros(36) if c[4] is None else c[4] for c in self._constraints]))
+        if self._loss is not None:
+            from .api import make_loss
+            try:
+                l = make_loss(self._loss)
+                kind, a, b = l.kind, l.a, l.b
+            except ValueError:
+                kind, a, b = -1, 0.0, 0.0
+            ok = host_lib().nos_host_pgo_solve_robust(*head, None if info is None else _dp(info), has.tobytes() if m else b"\0",
+                                                      ctypes.c_int(kind), ctypes.c_double(a), ctypes.c_double(b), _dp(sw),
+                                                      _dp(rep))
+        elif info is not None:
             ok = host_lib().nos_host_pgo_solve_weighted(*head, _dp(info), has.tobytes(), _dp(sw), _dp(rep))
         else:
             ok = host_lib().nos_host_pgo_solve(*head, _dp(sw), _dp(rep))
