@@ -465,9 +465,18 @@ int nos_map_stats_destroy(nos_map_stats* stats);
  * batches alone: batch of first appearance, then ascending integer cell coordinates.  One insert into an empty store
  * gives the statistics of nos_ndt_map_build bit for bit; sums are merged per voxel as store + batch, so results after
  * several inserts agree with a one-shot build to rounding (exactly when the sums are exact).
- * A batch that holds a non-finite coordinate (NOS_ERR_INVALID_ARGUMENT) or a point outside the addressable grid
- * (NOS_ERR_UNSUPPORTED) is rejected as a whole and leaves the store unchanged, like every rejected call here (a rejected
- * call writes nothing, *n_touched included).  n_points == 0 is a no-op.  *n_touched (optional) = voxels the batch fell into. */
+ * A batch that holds a non-finite coordinate (NOS_ERR_INVALID_ARGUMENT), a point outside the addressable grid or
+ * points that would take the voxel they fall into past 2^32 - 1 points (both NOS_ERR_UNSUPPORTED) is rejected as a whole
+ * and leaves the store unchanged, like every rejected call here (a rejected call writes nothing, *n_touched included).
+ * n_points == 0 is a no-op.  *n_touched (optional) = voxels the batch fell into.
+ * The count limit, for nos_voxel_map_insert, _insert_scan, _merge and _import(NOS_IMPORT_ADD) alike: a
+ * call that lands a voxel exactly on 2^32 - 1 points is accepted; one that would take ANY destination voxel past it
+ * returns NOS_ERR_UNSUPPORTED, and nos_voxel_map_export (cells, counts, sums, stamps, epoch), nos_voxel_map_stats and
+ * nos_voxel_map_info are bit for bit what they were; the store stays usable.  The message names a point of the batch
+ * that falls into such a voxel — its original index: nos_scan_order's for a cell-sorted scan, else its position —, for a
+ * merge a source voxel id, for an add a voxel of the state.  For insert, insert_scan and merge the limit is found on the
+ * device after room for the batch was reserved, so capacity, bytes and generation of nos_voxel_map_memory may have
+ * grown by the rejected call; results never depend on them.  The check adds no launch and no host wait. */
 typedef struct nos_voxel_map nos_voxel_map;
 int nos_voxel_map_create(nos_ctx* ctx, double voxel_resolution, double search_radius_sq, int flags,
                          size_t capacity_hint, nos_voxel_map** out);
@@ -541,7 +550,9 @@ int nos_voxel_map_match_indexed(nos_voxel_map* map, nos_scan* scan, const double
  *     inclusive.
  *   NOS_PRUNE_AGE: kept iff epoch - stamp <= max_age, where epoch counts the inserts that returned NOS_OK with at least
  *     one point (a rejected insert does not advance it) and a voxel's stamp is the epoch of the last insert that touched
- *     it.  max_age = 0 keeps only what the last insert touched.  Stamps are 32 bits wide: ages are exact below 2^32 inserts.
+ *     it.  max_age = 0 keeps only what the last insert touched.  Stamps are the low 32 bits of the 64-bit epoch and the
+ *     age is formed modulo 2^32: ages are exact, across epoch 2^32 too, as long as no live voxel is 2^32 or more inserts
+ *     old; a max_age of 2^32 - 1 or more keeps every such voxel.
  *   With both bits set a voxel must pass both tests.
  * Voxel ids stay a function of the sequence of calls alone: a prune renumbers the survivors by their rank among the
  * survivors (their relative order is kept); a cell that was removed and is seen again is a new voxel, appended by the
@@ -692,8 +703,11 @@ int nos_voxel_map_memory(const nos_voxel_map* map, size_t* capacity, size_t* byt
  *   NOS_ERR_INVALID_ARGUMENT  dst, src, R or t NULL, dst == src, different contexts, a non-finite entry of R or t (or
  *                             finite entries so large that a source voxel's moments overflow);
  *   NOS_ERR_HIP               either store was left undefined by an earlier failure;
- *   NOS_ERR_UNSUPPORTED       a destination cell outside +-2^20 per axis, or source voxels landing in one cell with more
- *                             than 2^32 - 1 points together: the message names the source voxel id, dst is bit for bit as before. */
+ *   NOS_ERR_UNSUPPORTED       a destination cell outside +-2^20 per axis, or source voxels that would take the voxel of
+ *                             dst they land in past 2^32 - 1 points — together with what that voxel already holds (the
+ *                             count limit above) or among themselves: the message names a source voxel id, dst is bit for
+ *                             bit as before (the limit against dst's own count is found after room was reserved: dst's
+ *                             capacity, bytes and generation may have grown). */
 int nos_voxel_map_merge(nos_voxel_map* dst, const nos_voxel_map* src, const double R[9], const double t[3], size_t* n_touched);
 /* One store matched against another: distribution-to-distribution NDT (Stoyanov et al. 2012).  Every valid
  * voxel of `source` is warped by q = R mean_s + t (the matcher's warp) and matched to its (up to) max_neighbors nearest
@@ -1029,14 +1043,19 @@ int nos_debug_lm_step(nos_ctx* ctx, int dof, const double* sums, const double se
  * flooring, sqrt-information — computed ON THE HOST by the function the kernels call (no GPU call, no context).
  * sums[9] = sx sy sz | mxx mxy mxz myy myz mzz of d = p - cell * voxel_resolution over the voxel's `count` points;
  * params[3] = min_points | min largest eigenvalue | eigenvalue floor ratio (5, 0.01, 0.01 in the build);
- * flags: 0 or NOS_MAP_PROPER_SQRT_INFORMATION.  An invalid voxel: sqrt_information identity, *valid = 0 (and mean 0 below min_points). */
+ * flags: 0 or NOS_MAP_PROPER_SQRT_INFORMATION.  An invalid voxel: sqrt_information identity, *valid = 0 (and mean 0 below min_points).
+ * count is used as the unsigned 32-bit number it is, up to 2^32 - 1.  Against 50 digits at 2^32 - 1 points (exact lattice
+ * sums, cells 0 and +-(2^20 - 1)): validity equal, mean 0 ulp, floored eigenvalues 1.1e-15, information
+ * matrix 1.5e-13 relative. */
 int nos_debug_voxel_finish(uint32_t count, const double sums[9], const int64_t cell[3], double voxel_resolution,
                            const double params[3], int flags, double mean[3], double sqrt_information[9], unsigned char* valid);
 
 /* Test hook: the moment transform of nos_voxel_map_merge computed ON THE HOST by the function its kernel calls (no GPU
  * call, no context).  count >= 1 and sums[9] about the corner of `cell` in a grid of edge src_resolution (as
  * nos_debug_voxel_finish takes them) -> cell_out, the destination cell in a grid of edge dst_resolution, and sums_out[9]
- * about that cell's corner.  NOS_ERR_UNSUPPORTED when the destination cell is not representable in 64 bits. */
+ * about that cell's corner.  NOS_ERR_UNSUPPORTED when the destination cell is not representable in 64 bits.
+ * Against 50 digits at 2^32 - 1 points: bit for bit under the identity and a whole-cell translation; under
+ * a general pose the mean the finish forms is off by 0.47 ulp at most and the scatter by 0.0006 x 128 x 2^-52 n L^2. */
 int nos_debug_voxel_moments(uint32_t count, const double sums[9], const int64_t cell[3], double src_resolution,
                             const double R[9], const double t[3], double dst_resolution,
                             int64_t cell_out[3], double sums_out[9]);

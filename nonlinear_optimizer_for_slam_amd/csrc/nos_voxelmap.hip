@@ -141,9 +141,13 @@ int store_reserve(nos_voxel_map* vm, size_t need) {
 // The back half of an insert and of a merge, ONE copy: U runs (keys ascending and unique, their counts, their nine sums
 // about the corner of the key's cell) go into the store — room for them, lookup, rank of the misses, voxel_merge_kernel
 // (count += n, acc += seg, the finish, stamp = epoch + 1), the closing wait and the bookkeeping.  Nothing of the store is
-// written before the merge kernel; `buf` is the caller's arena, `points` what the runs hold together.
+// written before the merge kernel; `buf` is the caller's arena, `points` what the runs hold together.  A run that would
+// take its voxel past 2^32 − 1 points is flagged by the lookup, the merge kernel then writes nothing, and the closing
+// wait brings the flag with the words it reads anyway: the call is rejected with the store as it was (its capacity
+// aside), naming `member` (e.g. "point") number names.member_idx[...] of that run.
 int store_merge_runs(nos_voxel_map* vm, DeviceBuffers& buf, const uint64_t* run_key, const uint32_t* run_count,
-                     const double* seg_acc, uint32_t U, unsigned long long points, const char* what, size_t* n_touched) {
+                     const double* seg_acc, uint32_t U, unsigned long long points, const nos::VoxelRunNames& names,
+                     const char* member, const char* what, size_t* n_touched) {
   hipStream_t st = vm->ctx->slots[0].stream;
   unsigned int h_info[nos::kInfoWords] = {};
   uint32_t *run_slot = nullptr, *miss = nullptr, *rank = nullptr;
@@ -158,7 +162,8 @@ int store_merge_runs(nos_voxel_map* vm, DeviceBuffers& buf, const uint64_t* run_
   if (e != hipSuccess) return hip_fail(e, what);
   const nos::MapBuildParams prm{5, 0.01, 0.01, (vm->flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0, vm->voxel_resolution};
   const dim3 ugrid(unsigned((size_t(U) + 255) / 256));
-  hipLaunchKernelGGL(nos::voxel_lookup_kernel, ugrid, dim3(256), 0, st, vm->view, run_key, U, run_slot, miss, vm->d_info);
+  hipLaunchKernelGGL(nos::voxel_lookup_kernel, ugrid, dim3(256), 0, st, vm->view, run_key, run_count, names, U, run_slot, miss,
+                     vm->d_info);
   e = hipGetLastError();
   if (e == hipSuccess) e = prim_run(rank_misses, t_rank);
   if (e != hipSuccess) return hip_fail(e, what);  // still nothing written
@@ -172,6 +177,8 @@ int store_merge_runs(nos_voxel_map* vm, DeviceBuffers& buf, const uint64_t* run_
     if (e != hipSuccess) return hip_fail(e, what);
     return fail(NOS_ERR_HIP, "%s failed: a table probe found no free entry", what);
   }
+  if (h_info[nos::kInfoFarPoint] != 0)  // the merge kernel wrote nothing: the store is as it was
+    return fail(NOS_ERR_UNSUPPORTED, "%s %u takes its destination voxel past 2^32 - 1 points", member, h_info[nos::kInfoFarPoint] - 1u);
   vm->n_voxels += h_info[nos::kInfoNew];
   vm->view.n_voxels = vm->n_voxels;
   vm->n_valid = size_t(int(h_info[nos::kInfoValid]));
@@ -182,9 +189,9 @@ int store_merge_runs(nos_voxel_map* vm, DeviceBuffers& buf, const uint64_t* run_
 }
 
 // One insert.  host_xyz != nullptr: [n][3] in the map frame; otherwise d_planes = 3 planes of n doubles in a local frame,
-// warped by `pose` on the device.
-int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const double* d_planes, const nos::PosePod& pose,
-                 size_t* n_touched) {
+// warped by `pose` on the device, `order` the scan's original indices when it was sorted by cell (else nullptr).
+int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const double* d_planes, const uint32_t* order,
+                 const nos::PosePod& pose, size_t* n_touched) {
   if (vm->broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
   if (n >= 0xFFFFFFFFull) return fail(NOS_ERR_UNSUPPORTED, "too many points for one insert");
   if (n == 0) {
@@ -237,7 +244,8 @@ int store_insert(nos_voxel_map* vm, size_t n, const double* host_xyz, const doub
   if (e != hipSuccess) return hip_fail(e, "voxel store insert (segments)");
   e = launch_voxel_sums(rec, g.idx_sorted, g.offsets, g.counts, U, 1.0 / vm->voxel_resolution, vm->voxel_resolution, seg_acc, st);
   if (e != hipSuccess) return hip_fail(e, "voxel store insert (sums)");
-  return store_merge_runs(vm, buf, g.uniq, g.counts, seg_acc, U, n, "voxel store insert", n_touched);
+  return store_merge_runs(vm, buf, g.uniq, g.counts, seg_acc, U, n, nos::VoxelRunNames{g.idx_sorted, g.offsets, order}, "point",
+                          "voxel store insert", n_touched);
 }
 
 // One merge of `src` into `dst` under `pose`: the source's slots become moment records about destination
@@ -288,9 +296,10 @@ int store_merge(nos_voxel_map* dst, const nos_voxel_map* src, const nos::PosePod
     return fail(NOS_ERR_INVALID_ARGUMENT, "source voxel %u has non-finite moments under this pose", h_info[nos::kInfoBadPoint] - 1u);
   if (h_info[nos::kInfoFarPoint] != 0)
     return fail(NOS_ERR_UNSUPPORTED,
-                "source voxel %u lands outside the addressable grid (+-2^20 cells per axis) or takes its destination voxel past "
-                "2^32 - 1 points", h_info[nos::kInfoFarPoint] - 1u);
-  return store_merge_runs(dst, buf, g.uniq, seg_count, seg_acc, U, src->n_points, "voxel store merge", n_touched);
+                "source voxel %u lands outside the addressable grid (+-2^20 cells per axis), or the source voxels of its "
+                "destination cell hold more than 2^32 - 1 points together", h_info[nos::kInfoFarPoint] - 1u);
+  return store_merge_runs(dst, buf, g.uniq, seg_count, seg_acc, U, src->n_points, nos::VoxelRunNames{g.idx_sorted, g.offsets, nullptr},
+                          "source voxel", "voxel store merge", n_touched);
 }
 
 // The keep flags of a prune or of a carve and everything behind them, ONE copy.  plan: arena memory
@@ -792,7 +801,8 @@ int store_add(nos_voxel_map* vm, size_t n, const std::vector<uint64_t>& keys, co
     return fail(NOS_ERR_UNSUPPORTED, "voxel %u of the state takes its destination voxel past 2^32 - 1 points", h_info[nos::kInfoFarPoint] - 1u);
   if (h_info[nos::kInfoProbeError] != 0) return fail(NOS_ERR_HIP, "voxel store add failed: a table probe found no free entry");
   // without a repeated cell the sorted keys ARE the runs' keys (U == n)
-  return store_merge_runs(vm, buf, g.keys_sorted, run_count, run_acc, uint32_t(n), points, "voxel store add", n_touched);
+  return store_merge_runs(vm, buf, g.keys_sorted, run_count, run_acc, uint32_t(n), points,
+                          nos::VoxelRunNames{g.idx_sorted, nullptr, nullptr}, "voxel", "voxel store add", n_touched);
 }
 
 // The store as whatever matches against it is handed it: the view the live matcher reads (nothing of it is written), the
@@ -935,14 +945,14 @@ int nos_voxel_map_insert(nos_voxel_map* vm, size_t n_points, const double* point
   if (!vm) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map is NULL");
   if (!points_xyz && n_points > 0) return fail(NOS_ERR_INVALID_ARGUMENT, "points is NULL");
   const nos::PosePod identity{{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}};
-  return store_insert(vm, n_points, points_xyz, nullptr, identity, n_touched);
+  return store_insert(vm, n_points, points_xyz, nullptr, nullptr, identity, n_touched);
 }
 
 int nos_voxel_map_insert_scan(nos_voxel_map* vm, nos_scan* scan, const double R[9], const double t[3], size_t* n_touched) {
   nosd::CtxGuard guard_(vm ? vm->ctx : nullptr);  // one solve / accumulate / create at a time per context
   if (!vm || !scan || !R || !t) return fail(NOS_ERR_INVALID_ARGUMENT, "NULL argument");
   if (vm->ctx != scan->ctx) return fail(NOS_ERR_INVALID_ARGUMENT, "voxel map and scan belong to different contexts");
-  return store_insert(vm, scan->n, nullptr, scan->d_planes, make_pose(R, t), n_touched);
+  return store_insert(vm, scan->n, nullptr, scan->d_planes, scan->d_order, make_pose(R, t), n_touched);
 }
 
 int nos_voxel_map_merge(nos_voxel_map* dst, const nos_voxel_map* src, const double R[9], const double t[3], size_t* n_touched) {

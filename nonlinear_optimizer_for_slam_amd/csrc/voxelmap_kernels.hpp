@@ -38,7 +38,8 @@ constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 // words of the store's device-side info block
 enum VoxelInfoWord {
   kInfoBadPoint = 0,    // 1 + index of a point with a non-finite coordinate (atomicMax; 0 = none)
-  kInfoFarPoint = 1,    // 1 + index of a point whose cell lies outside +-2^20 (atomicMax; 0 = none)
+  kInfoFarPoint = 1,    // 1 + index of a point whose cell lies outside +-2^20 (atomicMax; 0 = none); behind the wait that
+                        // reads that, 1 + a member of a run that takes its voxel past 2^32 - 1 points (voxel_lookup_kernel)
   kInfoProbeError = 2,  // a probe loop ran through the whole table (cannot happen at load factor <= 1/2)
   kInfoNew = 3,         // voxels the last merge created
   kInfoValid = 4,       // valid voxels in the store (kept across inserts; int)
@@ -138,9 +139,20 @@ __device__ __forceinline__ void voxel_table_insert(const VoxelStoreView& s, uint
   atomicOr(error, 1u);
 }
 
+// Who a run is named by when it would take its voxel past 2^32 − 1 points: member_idx[first[u]] (first == nullptr: run u
+// has one member, at position u) is a member of run u — a point of the batch, a voxel of the source or of the state —
+// and `order`, when not nullptr, maps it to the caller's numbering (a cell-sorted scan's original indices).
+struct VoxelRunNames {
+  const uint32_t* member_idx;
+  const uint32_t* first;
+  const uint32_t* order;
+};
+
 // Step 4a.  One lane per touched voxel u (run u of the sorted batch): the store's slot for its key, or kNoSlot and
-// miss[u] = 1.  The table is read-only here.
+// miss[u] = 1.  A run that would take the voxel it found past 2^32 − 1 points raises kInfoFarPoint with 1 + the name of
+// one of its members (atomicMax; the host has read and found the word 0 before this launch).  The table is read-only here.
 __global__ __launch_bounds__(256) void voxel_lookup_kernel(VoxelStoreView s, const uint64_t* __restrict__ run_key,
+                                                           const uint32_t* __restrict__ run_count, VoxelRunNames names,
                                                            uint32_t n_runs, uint32_t* __restrict__ run_slot,
                                                            uint32_t* __restrict__ miss, unsigned int* __restrict__ info) {
   const uint32_t u = blockIdx.x * 256 + threadIdx.x;
@@ -148,6 +160,11 @@ __global__ __launch_bounds__(256) void voxel_lookup_kernel(VoxelStoreView s, con
   const uint32_t slot = voxel_table_find(s, run_key[u], &info[kInfoProbeError]);
   run_slot[u] = slot;
   miss[u] = slot == kNoSlot ? 1u : 0u;
+  if (slot != kNoSlot && (unsigned long long)s.count[slot] + run_count[u] > 0xFFFFFFFFull) {
+    uint32_t who = names.member_idx[names.first ? names.first[u] : u];
+    if (names.order) who = names.order[who];
+    atomicMax(&info[kInfoFarPoint], who + 1u);
+  }
 }
 
 // Step 4b.  One lane per touched voxel: a miss takes slot n_voxels + rank (rank = exclusive scan of `miss`, i.e. its
@@ -164,6 +181,9 @@ __global__ __launch_bounds__(256) void voxel_merge_kernel(VoxelStoreView s, cons
                                                           MapBuildParams prm, uint32_t epoch,
                                                           unsigned int* __restrict__ info) {
   const uint32_t u = blockIdx.x * 256 + threadIdx.x;
+  // the lookup found a run that takes its voxel past 2^32 − 1 points: the whole call is rejected, nothing is written.
+  // The word is final here (the lookup is an earlier launch on this stream) and no lane of this kernel writes it.
+  if (info[kInfoFarPoint] != 0) return;
   int delta = 0;
   if (u < n_runs) {
     const uint64_t key = run_key[u];

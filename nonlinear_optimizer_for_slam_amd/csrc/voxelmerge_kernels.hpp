@@ -60,7 +60,9 @@ __global__ __launch_bounds__(256) void voxel_moments_kernel(VoxelStoreView src, 
 // Step 3.  One lane per run u of the sorted keys (*n_runs of them, known on the device only: the launch covers the most
 // there can be): seg_acc[u][9] and seg_count[u], the operands of voxel_merge_kernel, = the run's records and counts added
 // in ascending source slot, left to right, with plain adds; a run of one member is copied as it is.  The count is summed
-// in 64 bits: a total above 2^32 − 1 raises kInfoFarPoint with 1 + the source slot that crossed it.
+// in 64 bits: a total above 2^32 − 1 raises kInfoFarPoint with 1 + the source slot that crossed it.  Only the SOURCE
+// voxels of one cell are added here; what the destination voxel already holds is added to the run's count by
+// voxel_lookup_kernel, which raises the same word when run + destination pass 2^32 − 1.
 __global__ __launch_bounds__(256) void voxel_moment_sums_kernel(const double* __restrict__ mom /* [n][9] */,
                                                                 const uint32_t* __restrict__ mom_count,
                                                                 const uint32_t* __restrict__ sorted_idx,

@@ -13,6 +13,8 @@ store's merge, prune and compaction.
     insert_scan   an insert of points Rᵀ-rows + t (exact for an axis rotation and lattice points)
     merge         the source model's live points, grouped by source cell, moved by the pose and inserted as ONE batch; every
                   source voxel must land whole in one destination cell (asserted: the exactness condition of nos.h)
+    add           the exported state of another model of the same grid: a merge under the identity
+    Rejected      raised by any of the four, with nothing changed, when a voxel would pass 2^32 − 1 points
     prune         box and / or age; survivors keep their order, renumbered by rank
     carve         voxel_carve_inputs.counts on the cells in slot order, voxel_carve_inputs.removed, then the prune's removal;
                   epoch and stamps untouched
@@ -25,6 +27,16 @@ from tests import voxel_carve_inputs as ci
 
 KEYS = ("cells", "counts", "valid", "means", "sqrt_infos")
 LIM = 1 << 20
+COUNT_MAX = 0xFFFFFFFF  # the points a voxel holds at most
+
+
+class Rejected(Exception):
+    """An insert, a merge or an add would take a voxel past COUNT_MAX points: the call is rejected as a whole and the
+    model is as it was.  rows: the positions, in the batch, of the points that fall into such voxels."""
+
+    def __init__(self, rows):
+        Exception.__init__(self, "%d points fall into voxels that would pass 2^32 - 1 points" % len(rows))
+        self.rows = rows
 
 
 def _same_bits(a, b, keys=KEYS):
@@ -112,12 +124,16 @@ class Model:
     def insert(self, pts, stamp=True):
         if pts.shape[0] == 0:
             return 0
-        self.epoch += 1
         cells = _cells_of(pts, self.res)
         keys = _pack(cells)
-        self.history.append((self.epoch, pts, keys))
         order = np.argsort(keys, kind="stable")
         uniq, first, n = np.unique(keys[order], return_index=True, return_counts=True)
+        # the rule of nos.h: a call that would take a voxel past 2^32 - 1 points is rejected as a whole, nothing changes
+        over = [int(k) for k, c in zip(uniq, n) if int(k) in self.slot and int(self.counts[self.slot[int(k)]]) + int(c) > COUNT_MAX]
+        if over:
+            raise Rejected(np.nonzero(np.isin(keys, over))[0])
+        self.epoch += 1
+        self.history.append((self.epoch, pts, keys))
         seg = np.add.reduceat(_terms(pts[order]), first, axis=0)
         new = self._new_cells(uniq, cells[order][first], keys)
         V = self.cells.shape[0]
@@ -163,6 +179,12 @@ class Model:
     def merge(self, src, R=None, t=None):
         """→ destination voxels touched; an empty source is a no-op that leaves the epoch alone"""
         return self.insert(self.merge_batch(src, np.eye(3) if R is None else R, np.zeros(3) if t is None else t))
+
+    def add(self, other):
+        """VoxelMap.add of other's exported state: on exact inputs an insert of its live points as one batch, which is
+        what a merge under the identity is → voxels touched"""
+        assert other.res == self.res
+        return self.merge(other)
 
     # ---------------------------------------------------------------------------------------------- what removes
 
