@@ -1,5 +1,5 @@
 // group_host.hpp — host side of grouping by key, as match_host.hpp is for matching: what the map build and
-// the scan sort (nos_mapbuild.hip), the voxel store (nos_voxelmap.hip), the matcher's tables (nos_match.hip), the indexed
+// the scan sort (nos_mapbuild.hip), the voxel store (voxel_store_host.hpp), the matcher's tables (nos_match.hip), the indexed
 // dataset (nos_indexed.hip) and the scan filter (nos_scanfilter.hip) share.  No kernel lives here.
 #pragma once
 

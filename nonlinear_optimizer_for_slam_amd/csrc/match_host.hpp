@@ -31,7 +31,7 @@ struct SnapshotSource {
   }
 };
 
-// The live voxel store (nos_voxelmap.hip's live_store); its kernels end with the probe-error word.
+// The live voxel store (voxel_query_host.hpp's live_store); its kernels end with the probe-error word.
 struct StoreSource : LiveStore {
   static constexpr const char* kWhat = "matching against the voxel store";
   static constexpr bool kTallyLaunches = true, kRecordLastKernel = true;
@@ -55,7 +55,7 @@ inline int check_match_call(const nos_ctx* map_ctx, const nos_scan* scan, const 
 
 // What a match runs over, one thread per item.  Items have n(), kForm (what a message of the flat match calls the route)
 // and lead(f): f(the kernel's arguments between the view and the item count).  A scan's points are the items of every
-// match but the map-to-map one, whose items are a second store's voxels (nos_voxelmap.hip's StoreVoxels).
+// match but the map-to-map one, whose items are a second store's voxels (voxel_query_host.hpp's StoreVoxels).
 struct ScanPoints {
   const nos_scan* scan;
   static constexpr const char* kForm = "";

@@ -281,8 +281,13 @@ struct nos_scan {
   double* d_planes = nullptr;  // [3][n]
   uint32_t* d_order = nullptr; // after nos_scan_sort_by_cell: original index of the point stored at each position
 };
+// tests/test_scan_products_own_their_arrays.py reads n, d_planes and d_order out of a handle: four words in this order
+static_assert(std::is_standard_layout<nos_scan>::value && sizeof(nos_scan) == 4 * sizeof(void*) && sizeof(size_t) == sizeof(void*) &&
+                  offsetof(nos_scan, n) == sizeof(void*) && offsetof(nos_scan, d_planes) == 2 * sizeof(void*) &&
+                  offsetof(nos_scan, d_order) == 3 * sizeof(void*),
+              "nos_scan's layout is read by a test");
 
-// per-voxel numbers of a map build (nos_mapbuild.hip) or of a voxel store (nos_voxelmap.hip), on the host
+// per-voxel numbers of a map build (nos_mapbuild.hip) or of a voxel store (voxel_store_host.hpp; nos_voxel_map_stats in nos_voxelmap.hip), on the host
 struct nos_map_stats {
   std::vector<double> means;            // [V][3] voxel order = ascending packed (ix, iy, iz); reference-exact mode: first seen
   std::vector<double> sqrt_infos;       // [V][9]
@@ -305,6 +310,39 @@ hipError_t upload(T** dptr, const std::vector<T>& host) {
   if (e == hipSuccess && !host.empty()) e = hipMemcpy(*dptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
   return e;
 }
+
+// A scan under construction and its two device arrays, ONE copy of what nos_scan_create, the filter, the deskew and the
+// ray cast each need: alloc sizes them (planes, then order — hipMalloc, not the arena: the handle outlives the call);
+// release hands the finished handle to the caller; whatever was not released is freed when this goes out of scope, and a
+// failed allocation's sticky error goes with it, so that it does not surface as the next call's launch error.
+struct NewScan {
+  nos_scan* scan;
+  explicit NewScan(nos_ctx* ctx) : scan(new (std::nothrow) nos_scan()) {
+    if (scan) scan->ctx = ctx;
+  }
+  NewScan(const NewScan&) = delete;
+  NewScan& operator=(const NewScan&) = delete;
+  ~NewScan() {
+    if (!scan) return;
+    (void)hipGetLastError();
+    if (scan->d_planes) (void)hipFree(scan->d_planes);
+    if (scan->d_order) (void)hipFree(scan->d_order);
+    delete scan;
+  }
+  explicit operator bool() const { return scan != nullptr; }
+  // n points; n == 0: the empty form — a 24-byte planes block, so that d_planes is never NULL, and no order array
+  hipError_t alloc(size_t n, bool with_order) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&scan->d_planes), std::max<size_t>(n, 1) * 3 * sizeof(double));
+    if (e == hipSuccess && with_order && n > 0) e = hipMalloc(reinterpret_cast<void**>(&scan->d_order), n * sizeof(uint32_t));
+    if (e == hipSuccess) scan->n = n;
+    return e;
+  }
+  nos_scan* release() {
+    nos_scan* s = scan;
+    scan = nullptr;
+    return s;
+  }
+};
 
 // Scratch buffers of one call, freed when it returns.  Without a slot: one hipMalloc / hipFree per buffer (round 1).  With a
 // slot (round 4): an ARENA — buffers are carved out of a few large slabs that come from the slot's buffer pool and go back
@@ -487,9 +525,9 @@ int map_create_device(nos_ctx* ctx, size_t n_voxels, const double* d_means, cons
 hipError_t launch_voxel_sums(const double* d_records, const uint32_t* sorted_idx, const uint32_t* seg_offset,
                              const uint32_t* seg_count, uint32_t n_voxels, double inv_res, double res, double* acc_out,
                              hipStream_t stream);
-// The live voxel store as whatever matches against it is handed it — the matcher of nos_voxelmap.hip (which owns struct
-// nos_voxel_map; its match source, match_host.hpp, derives from this) and the batched registration of
-// nos_voxelregister.hip.
+// The live voxel store as whatever matches against it is handed it — the matcher of nos_voxelmap.hip (struct
+// nos_voxel_map is voxel_store_host.hpp's, live_store voxel_query_host.hpp's; its match source, match_host.hpp, derives
+// from this) and the batched registration of nos_voxelregister.hip.
 struct LiveStore {
   nos_ctx* ctx;
   nos::VoxelMatchView view;
@@ -498,6 +536,10 @@ struct LiveStore {
   double span;                  // cells the search ball spans per axis: 2 r / resolution + 2
   bool broken;                  // an earlier failure left the store undefined
 };
+// What every call that reads a store's content rejects: `broken` = a merge reported a probe error (nos_voxel_map::broken).
+inline int check_usable(bool broken) {
+  return broken ? fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure") : NOS_OK;
+}
 // What a lone match and a registration reject of the store itself, in this order.  The live matcher visits at most
 // kVoxelMatchMaxSpan cells per axis.
 inline int check_live_store(const LiveStore& s) {
@@ -505,8 +547,7 @@ inline int check_live_store(const LiveStore& s) {
     return fail(NOS_ERR_UNSUPPORTED,
                 "the search ball spans more than %d voxel cells per axis (2 r / resolution + 2 = %g): match against a snapshot",
                 nos::kVoxelMatchMaxSpan, s.span);
-  if (s.broken) return fail(NOS_ERR_HIP, "the voxel store was left undefined by an earlier failure");
-  return NOS_OK;
+  return check_usable(s.broken);
 }
 // What a batched registration and a score batch reject of their scans: every scan there, and of the map's context.
 inline int check_scans(const nos_ctx* ctx, nos_scan* const* scans, int n) {

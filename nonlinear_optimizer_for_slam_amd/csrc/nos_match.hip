@@ -327,17 +327,14 @@ int nos_scan_create(nos_ctx* ctx, size_t n_points, const double* points_xyz, nos
   *out_scan = nullptr;
   if (ctx->slots.size() != 1) return fail(NOS_ERR_UNSUPPORTED, "the matcher needs a single-device context");
   if (!points_xyz && n_points > 0) return fail(NOS_ERR_INVALID_ARGUMENT, "points is NULL");
-  nos_scan* scan = new (std::nothrow) nos_scan();
+  NewScan scan(ctx);
   if (!scan) return fail(NOS_ERR_OUT_OF_MEMORY, "host allocation failed");
-  scan->ctx = ctx;
-  scan->n = n_points;
   DeviceSlot& slot = ctx->slots[0];
   // [n][3] records (std::vector<Vec3>) → 3 planes, through the same record-unpack kernel as datasets
   hipError_t e = hipSetDevice(slot.device);
   void* staging = nullptr;
-  const size_t bytes = std::max<size_t>(n_points, 1) * 3 * sizeof(double);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&scan->d_planes), bytes);
-  if (e == hipSuccess) e = hipMalloc(&staging, bytes);
+  if (e == hipSuccess) e = scan.alloc(n_points, false);
+  if (e == hipSuccess) e = hipMalloc(&staging, std::max<size_t>(n_points, 1) * 3 * sizeof(double));
   int rc = NOS_OK;
   if (e == hipSuccess && n_points > 0) {
     e = hipMemcpyAsync(staging, points_xyz, n_points * 3 * sizeof(double), hipMemcpyHostToDevice, slot.stream);
@@ -353,16 +350,13 @@ int nos_scan_create(nos_ctx* ctx, size_t n_points, const double* points_xyz, nos
     fo.off[1] = 8;
     fo.off[2] = 16;
     if (e == hipSuccess)
-      rc = unpack_records(NOS_F64, static_cast<unsigned char*>(staging), 24, fo, 3, 0, n_points, L, scan->d_planes, slot.stream);
+      rc = unpack_records(NOS_F64, static_cast<unsigned char*>(staging), 24, fo, 3, 0, n_points, L, scan.scan->d_planes, slot.stream);
     if (e == hipSuccess && rc == NOS_OK) e = hipStreamSynchronize(slot.stream);
   }
   if (staging) (void)hipFree(staging);
-  if (e != hipSuccess || rc != NOS_OK) {
-    nos_scan_destroy(scan);
-    if (rc != NOS_OK) return rc;
-    return hip_fail(e, "scan upload");
-  }
-  *out_scan = scan;
+  if (rc != NOS_OK) return rc;
+  if (e != hipSuccess) return hip_fail(e, "scan upload");
+  *out_scan = scan.release();
   return NOS_OK;
 }
 

@@ -5,7 +5,6 @@
 #include "scan_deskew_kernels.hpp"
 
 #include <cmath>
-#include <memory>
 
 using namespace nosd;
 
@@ -39,26 +38,18 @@ int nos_scan_deskew(nos_scan* scan, const double* times, size_t n_times, double 
   P.kkv[1] = P.k[2] * P.kv[0] - P.k[0] * P.kv[2];
   P.kkv[2] = P.k[0] * P.kv[1] - P.k[1] * P.kv[0];
   P.s_ref = reference_time;
-  std::unique_ptr<nos_scan> out(new (std::nothrow) nos_scan());
+  NewScan out(ctx);
   if (!out) return fail(NOS_ERR_OUT_OF_MEMORY, "host allocation failed");
-  out->ctx = ctx;
   DeviceSlot& slot = ctx->slots[0];
   hipStream_t st = slot.stream;
   hipError_t e = hipSetDevice(slot.device);
-  if (e != hipSuccess) return fail(NOS_ERR_HIP, "scan deskew failed: %s", hipGetErrorString(e));
-  if (n == 0) {  // an empty scan deskews to an empty scan (nos_scan_create's form of one)
-    e = hipMalloc(reinterpret_cast<void**>(&out->d_planes), 3 * sizeof(double));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "scan deskew failed: %s", hipGetErrorString(e));
-    }
+  if (e == hipSuccess && n == 0) e = out.alloc(0, false);  // an empty scan deskews to an empty scan
+  if (e != hipSuccess) return hip_fail(e, "scan deskew");
+  if (n == 0) {
     *out_scan = out.release();
     return NOS_OK;
   }
   unsigned int h_info[nos::kDeskewWords] = {0, 0};
-  double* out_planes = nullptr;
-  uint32_t* out_order = nullptr;
-  int rc = NOS_OK;
   {
     DeviceBuffers buf(&slot);  // arena (pooled slabs) for the time stamps and the info words; goes back when this block ends
     buf.reserve(n_times * sizeof(double) + 512);
@@ -66,37 +57,25 @@ int nos_scan_deskew(nos_scan* scan, const double* times, size_t n_times, double 
     unsigned int* info = nullptr;
     e = buf.alloc(&d_times, n_times);
     if (e == hipSuccess) e = buf.alloc(&info, size_t(nos::kDeskewWords));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&out_planes), n * 3 * sizeof(double));
-    if (e == hipSuccess && scan->d_order != nullptr) e = hipMalloc(reinterpret_cast<void**>(&out_order), n * sizeof(uint32_t));
+    if (e == hipSuccess) e = out.alloc(n, scan->d_order != nullptr);  // the order array goes along when the source has one
     if (e == hipSuccess && n_times > 0) e = hipMemcpyAsync(d_times, times, n_times * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(info, 0, sizeof h_info, st);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(nos::scan_deskew_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, scan->d_planes, scan->d_order,
-                         uint32_t(n), d_times, uint64_t(n_times), P, out_planes, info);
+                         uint32_t(n), d_times, uint64_t(n_times), P, out.scan->d_planes, info);
       e = hipGetLastError();
     }
-    if (e == hipSuccess && out_order != nullptr)
-      e = hipMemcpyAsync(out_order, scan->d_order, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && scan->d_order != nullptr)
+      e = hipMemcpyAsync(out.scan->d_order, scan->d_order, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(h_info, info, sizeof h_info, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);  // the one wait
-    if (e == hipSuccess && h_info[nos::kDeskewNoTime] != 0)
-      rc = fail(NOS_ERR_INVALID_ARGUMENT, "the point at position %u has no time stamp: its original index is >= n_times = %zu",
+  }
+  if (e != hipSuccess) return hip_fail(e, "scan deskew");
+  if (h_info[nos::kDeskewNoTime] != 0)
+    return fail(NOS_ERR_INVALID_ARGUMENT, "the point at position %u has no time stamp: its original index is >= n_times = %zu",
                 h_info[nos::kDeskewNoTime] - 1u, n_times);
-    else if (e == hipSuccess && h_info[nos::kDeskewBadTime] != 0)
-      rc = fail(NOS_ERR_INVALID_ARGUMENT, "the time stamp of the point at position %u is not finite", h_info[nos::kDeskewBadTime] - 1u);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();  // a failed allocation must not surface as the next call's launch error
-    rc = fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "scan deskew failed: %s", hipGetErrorString(e));
-  }
-  if (rc != NOS_OK) {
-    if (out_planes) (void)hipFree(out_planes);
-    if (out_order) (void)hipFree(out_order);
-    return rc;
-  }
-  out->n = n;
-  out->d_planes = out_planes;
-  out->d_order = out_order;
+  if (h_info[nos::kDeskewBadTime] != 0)
+    return fail(NOS_ERR_INVALID_ARGUMENT, "the time stamp of the point at position %u is not finite", h_info[nos::kDeskewBadTime] - 1u);
   *out_scan = out.release();
   return NOS_OK;
 }

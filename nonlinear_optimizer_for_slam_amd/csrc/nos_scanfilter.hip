@@ -17,19 +17,14 @@ int nos_scan_filter(nos_scan* scan, double voxel_size, nos_scan** out_scan) {
   const size_t n = scan->n;
   if (n >= 0xFFFFFFFFull) return fail(NOS_ERR_UNSUPPORTED, "too many points");
   const double inv_res = 1.0 / voxel_size;  // once, in double: the factor voxel_key_kernel multiplies by
-  std::unique_ptr<nos_scan> out(new (std::nothrow) nos_scan());
+  NewScan out(ctx);
   if (!out) return fail(NOS_ERR_OUT_OF_MEMORY, "host allocation failed");
-  out->ctx = ctx;
   DeviceSlot& slot = ctx->slots[0];
   hipStream_t st = slot.stream;
   hipError_t e = hipSetDevice(slot.device);
-  if (e != hipSuccess) return fail(NOS_ERR_HIP, "scan filter failed: %s", hipGetErrorString(e));
-  if (n == 0) {  // an empty scan filters to an empty scan (nos_scan_create's form of one)
-    e = hipMalloc(reinterpret_cast<void**>(&out->d_planes), 3 * sizeof(double));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "scan filter failed: %s", hipGetErrorString(e));
-    }
+  if (e == hipSuccess && n == 0) e = out.alloc(0, false);  // an empty scan filters to an empty scan
+  if (e != hipSuccess) return hip_fail(e, "scan filter");
+  if (n == 0) {
     *out_scan = out.release();
     return NOS_OK;
   }
@@ -37,8 +32,6 @@ int nos_scan_filter(nos_scan* scan, double voxel_size, nos_scan** out_scan) {
   while (table_size < 2 * n) table_size <<= 1;  // load factor <= 1/2 even when every point has a cell of its own
   uint32_t n_kept = 0;
   unsigned int h_info[nos::kFilterWords] = {0, 0, 0, 0};
-  double* out_planes = nullptr;
-  uint32_t* out_order = nullptr;
   {
     DeviceBuffers buf(&slot);  // arena (pooled slabs) for the temporaries; goes back when this block ends
     // table: 8 B key + 4 B first per entry; per point: 4 B entry + 4 B kept position; select temporaries behind them
@@ -77,24 +70,15 @@ int nos_scan_filter(nos_scan* scan, double voxel_size, nos_scan** out_scan) {
       return fail(NOS_ERR_UNSUPPORTED, "point %u lies outside the addressable grid", h_info[nos::kFilterFarPoint] - 1u);
     if (e == hipSuccess && (h_info[nos::kFilterProbeError] != 0 || n_kept == 0 || n_kept > n))
       return fail(NOS_ERR_HIP, "scan filter: inconsistent table (kept %u of %zu)", n_kept, n);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&out_planes), size_t(n_kept) * 3 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&out_order), size_t(n_kept) * sizeof(uint32_t));
+    if (e == hipSuccess) e = out.alloc(n_kept, true);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(nos::scan_filter_gather_kernel, dim3((n_kept + 255) / 256), dim3(256), 0, st, scan->d_planes, uint32_t(n),
-                         scan->d_order, kept, n_kept, out_planes, out_order);
+                         scan->d_order, kept, n_kept, out.scan->d_planes, out.scan->d_order);
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);  // the gather has read `kept` before the arena takes it back
   }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();  // a failed allocation must not surface as the next call's launch error
-    if (out_planes) (void)hipFree(out_planes);
-    if (out_order) (void)hipFree(out_order);
-    return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "scan filter failed: %s", hipGetErrorString(e));
-  }
-  out->n = n_kept;
-  out->d_planes = out_planes;
-  out->d_order = out_order;
+  if (e != hipSuccess) return hip_fail(e, "scan filter");
   *out_scan = out.release();
   return NOS_OK;
 }

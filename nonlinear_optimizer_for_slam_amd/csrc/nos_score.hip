@@ -1,5 +1,5 @@
 // nos_score.hip — nos_ndt_score_batch (C ABI of include/nos.h) and the host path of nos_voxel_map_score_batch (whose
-// entry point is in nos_voxelmap.hip, which owns the store).
+// entry point is in nos_voxelmap.hip; the store, struct nos_voxel_map, is voxel_store_host.hpp's, which only that unit includes).
 //
 // B (scan, pose) problems scored against one map — a snapshot (nos_ndt_map) or the LIVE voxel store — by
 // nos::score_batch_kernel (score_kernels.hpp): matches, matched points and the cost Σ ρ per problem, nothing written in

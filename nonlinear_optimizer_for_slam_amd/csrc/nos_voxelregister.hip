@@ -1,5 +1,6 @@
 // nos_voxelregister.hip — nos_voxel_map_register6_batch / nos_voxel_map_register3_batch (C ABI of include/nos.h; the entry
-// points themselves are in nos_voxelmap.hip, which owns the store).
+// points themselves are in nos_voxelmap.hip; the store, struct nos_voxel_map, is voxel_store_host.hpp's, which only that unit
+// includes).
 //
 // nos_ndt*_register_batch (nos_register.hip) against the LIVE voxel store: B registrations in ONE launch, one workgroup
 // each (nos::register_live_kernel, assemble_register_live.hpp), every round matched through the table the inserts
