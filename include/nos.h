@@ -1194,6 +1194,13 @@ int nos_pgo_time_sweep(nos_pose_graph* pg, int which, double lambda, int repeats
  * the names in lower case without the prefix, e.g. "lm_cluster"; "ingest": 0 auto, 1 pack, 2 unpack;
  * "debug_cluster_abort": test hook, makes the next one-launch solve give up and fall back).  Nothing on the solve /
  * accumulate path reads the environment.
+ *   "debug_alloc_fill" / "debug_alloc_filled"  test hooks (option only).  debug_alloc_fill: 0 (default) off; -1 = every
+ *                 device block handed out from now on — a buffer of the pool, parked or fresh, over its whole capacity;
+ *                 every allocation made for an object or a call; the pinned staging blocks allocated on first use — is
+ *                 filled with the word 0x00000000 first; 1 … 0x7FFFFFFF = with that 32-bit word.  The context's own
+ *                 workspaces exist before the option can be set and are not filled.  No result may depend on the word.
+ *                 debug_alloc_filled counts the blocks filled (saturating); setting it to 0 resets it, no other value is
+ *                 accepted.
  *   "lm_cluster"  1 (default) the device-resident loop runs in ONE launch wherever it can: correspondences resident on chip
  *                 up to the register + LDS capacity, streamed from HBM every iteration beyond it; 4 = one launch only for
  *                 resident data (one launch per iteration above), 5 = as 1 with the all-reduce's first stage always through

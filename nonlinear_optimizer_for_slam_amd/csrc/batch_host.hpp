@@ -40,6 +40,7 @@ class BatchTrip {
       slot_.batch_pinned = nullptr;
       slot_.batch_pinned_bytes = 0;
       NOS_HIP_CHECK(hipHostMalloc(&slot_.batch_pinned, pinned_total, hipHostMallocDefault));
+      NOS_HIP_CHECK(debug_fill(slot_, slot_.batch_pinned, pinned_total, /*host=*/true));
       slot_.batch_pinned_bytes = pinned_total;
     }
     void* dev = nullptr;

@@ -55,6 +55,49 @@ void pool_drain(DeviceSlot& slot) {
   slot.pool_bytes = 0;
 }
 
+// Settings::debug_alloc_fill.  The word goes out with hipMemsetD32Async on the slot's stream and the stream is waited for:
+// the ingestion copy streams are non-blocking streams of their own, so the caller must get a finished block.  A tail of
+// fewer than four bytes gets the word's low bytes.  The counter is the context's, not the slot's, and plain: every
+// allocation is made by the thread that holds the context's lock (CtxGuard) — the ingestion's worker threads pack host
+// memory and allocate nothing.
+hipError_t debug_fill(DeviceSlot& slot, void* ptr, size_t bytes, bool host) {
+  Settings& st = *slot.settings;
+  if (st.debug_alloc_fill == 0) return hipSuccess;  // off: this branch and nothing else
+  const uint32_t word = st.debug_alloc_fill < 0 ? 0u : uint32_t(st.debug_alloc_fill);
+  char* tail = static_cast<char*>(ptr) + (bytes & ~size_t(3));
+  if (host) {
+    for (size_t i = 0; i < bytes / 4; ++i) memcpy(static_cast<char*>(ptr) + 4 * i, &word, 4);
+    memcpy(tail, &word, bytes & 3);
+  } else {
+    hipError_t e = bytes >= 4 ? hipMemsetD32Async(ptr, int(word), bytes / 4, slot.stream) : hipSuccess;
+    if (e == hipSuccess && (bytes & 3) != 0) e = hipMemcpyAsync(tail, &word, bytes & 3, hipMemcpyHostToDevice, slot.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(slot.stream);
+    if (e != hipSuccess) return e;
+  }
+  if (st.debug_alloc_filled < INT_MAX) ++st.debug_alloc_filled;
+  return hipSuccess;
+}
+
+hipError_t device_alloc(DeviceSlot& slot, void** ptr, size_t bytes) {
+  *ptr = nullptr;
+  hipError_t e = hipMalloc(ptr, bytes);
+  if (e == hipSuccess && (e = debug_fill(slot, *ptr, bytes)) != hipSuccess) {
+    (void)hipFree(*ptr);
+    *ptr = nullptr;
+  }
+  return e;
+}
+
+namespace {
+// what pool_alloc hands out, parked or fresh, filled over its whole capacity while Settings::debug_alloc_fill is on
+int pool_filled(DeviceSlot& slot, void* ptr, size_t capacity) {
+  const hipError_t e = debug_fill(slot, ptr, capacity);
+  if (e == hipSuccess) return NOS_OK;
+  pool_release(slot, ptr, capacity);
+  return hip_fail(e, "filling a device block (debug_alloc_fill)");
+}
+}  // namespace
+
 int pool_alloc(DeviceSlot& slot, size_t bytes, void** ptr, size_t* capacity) {
   if (bytes == 0) bytes = 8;
   int best = -1;
@@ -67,7 +110,7 @@ int pool_alloc(DeviceSlot& slot, size_t bytes, void** ptr, size_t* capacity) {
     *capacity = slot.pool[best].bytes;
     slot.pool_bytes -= slot.pool[best].bytes;
     slot.pool.erase(slot.pool.begin() + best);
-    return NOS_OK;
+    return pool_filled(slot, *ptr, *capacity);
   }
   hipError_t e = hipMalloc(ptr, bytes);
   if (e == hipErrorOutOfMemory && !slot.pool.empty()) {  // give the parked buffers back and try once more
@@ -78,7 +121,7 @@ int pool_alloc(DeviceSlot& slot, size_t bytes, void** ptr, size_t* capacity) {
     return fail(e == hipErrorOutOfMemory ? NOS_ERR_OUT_OF_MEMORY : NOS_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", bytes,
                 hipGetErrorString(e));
   *capacity = bytes;
-  return NOS_OK;
+  return pool_filled(slot, *ptr, *capacity);
 }
 
 void pool_release(DeviceSlot& slot, void* ptr, size_t capacity) {
@@ -132,6 +175,8 @@ const OptionEntry kOptions[] = {
     {"map_fma_mask", &nosd::Settings::map_fma_mask, 0, (1 << 26) - 1},
     {"map_eigen_version", &nosd::Settings::map_eigen_version, 33, 34},
     {"debug_cluster_abort", &nosd::Settings::debug_cluster_abort, 0, 2},
+    {"debug_alloc_fill", &nosd::Settings::debug_alloc_fill, -1, INT_MAX},
+    {"debug_alloc_filled", &nosd::Settings::debug_alloc_filled, 0, 0},  // a counter: read it, or reset it to 0
     {"lm_cluster_max_blocks", &nosd::Settings::lm_cluster_max_blocks, 1, 256},
     {"stream_lds_chunks", &nosd::Settings::stream_lds_chunks, 0, 3},
     {"stream_reg_rounds", &nosd::Settings::stream_reg_rounds, 0, nos::kStreamRegRoundsMax},
@@ -206,6 +251,7 @@ int nos_ctx_create(const int* device_ids, int n_devices, nos_ctx** out_ctx) {
     DeviceSlot& s = ctx->slots[i];
     s.device = device_ids[i];
     s.pool_enabled = ctx->settings.pool != 0;
+    s.settings = &ctx->settings;
     hipDeviceProp_t prop;
     e = hipSetDevice(s.device);
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, s.device);

@@ -155,7 +155,7 @@ int create_from_host_planes(nos_ctx* ctx, int kind, size_t n, const double* cons
     hipError_t e = hipSetDevice(slot.device);
     void* staging = nullptr;
     const size_t plane_bytes = cnt * sizeof(double);
-    if (e == hipSuccess && cnt > 0) e = hipMalloc(&staging, plane_bytes * ds->n_fields);
+    if (e == hipSuccess && cnt > 0) e = device_alloc(slot, &staging, plane_bytes * ds->n_fields);
     nos::PlanePtrs src{};
     for (int f = 0; f < ds->n_fields && e == hipSuccess && cnt > 0; ++f) {
       char* d = static_cast<char*>(staging) + plane_bytes * f;
@@ -320,7 +320,10 @@ int ingest_host_pack(nos_ctx* ctx, nos_dataset* ds, Shard& sh, const unsigned ch
       slot.pack_pinned[b] = nullptr;
     }
     slot.pack_bytes = 0;
-    for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipHostMalloc(&slot.pack_pinned[b], need, hipHostMallocDefault);
+    for (int b = 0; b < 2 && e == hipSuccess; ++b) {
+      e = hipHostMalloc(&slot.pack_pinned[b], need, hipHostMallocDefault);
+      if (e == hipSuccess) e = debug_fill(slot, slot.pack_pinned[b], need, /*host=*/true);
+    }
     if (e == hipSuccess) slot.pack_bytes = need;
   }
   // Worker threads live for the whole call; per chunk they are released by `go` (chunk number) and report through
@@ -461,7 +464,7 @@ int create_from_records(nos_ctx* ctx, int kind, size_t n, const void* records, s
       }
       slot.stage_bytes = 0;
       const size_t grow = std::max(want_stage, size_t(4) << 20);
-      for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipMalloc(&slot.stage[b], grow);
+      for (int b = 0; b < 2 && e == hipSuccess; ++b) e = device_alloc(slot, &slot.stage[b], grow);
       if (e == hipSuccess) slot.stage_bytes = grow;
     }
     void** stage = slot.stage;

@@ -36,6 +36,7 @@
 namespace nosd {
 
 struct DeviceSlot;
+struct Settings;
 
 // nos_ctx.hip
 // thread-local text of the last failure + status pass-through
@@ -48,6 +49,19 @@ int env_int(const char* name, int dflt);
 int pool_alloc(DeviceSlot& slot, size_t bytes, void** ptr, size_t* capacity);
 void pool_release(DeviceSlot& slot, void* ptr, size_t capacity);
 void pool_drain(DeviceSlot& slot);
+// The ONE hipMalloc of whatever an object or a call allocates on the slot's device after the context was created (the
+// caller has selected the device).  While Settings::debug_alloc_fill is on, the block is filled before this returns.
+hipError_t device_alloc(DeviceSlot& slot, void** ptr, size_t bytes);
+template <typename T>
+inline hipError_t device_alloc(DeviceSlot& slot, T** ptr, size_t bytes) {
+  void* p = nullptr;
+  const hipError_t e = device_alloc(slot, &p, bytes);
+  *ptr = static_cast<T*>(p);
+  return e;
+}
+// Settings::debug_alloc_fill for a block of `bytes` at `ptr`: device memory through the slot's stream, complete on return
+// (the ingestion copy streams do not wait for that stream); pinned host memory (`host`) by memset.  Off: nothing.
+hipError_t debug_fill(DeviceSlot& slot, void* ptr, size_t bytes, bool host = false);
 
 #define NOS_HIP_CHECK(expr)                                                               \
   do {                                                                                    \
@@ -136,6 +150,7 @@ struct DeviceSlot {
   std::vector<PoolEntry> pool;
   size_t pool_bytes = 0;
   bool pool_enabled = true;  // Settings::pool
+  Settings* settings = nullptr;  // the context's (nos_ctx_create): debug_alloc_fill, read by pool_alloc and device_alloc
   const void* last_kernel = nullptr;  // host function of the hot-path kernel launched last on this device (nos_ctx_last_kernel)
   bool cluster_gave_up = false;  // the last one-launch solve on this device timed out waiting for its grid (shared GPU)
   std::chrono::steady_clock::time_point cluster_gave_up_at{};
@@ -185,6 +200,12 @@ struct Settings {
   int map_eigen_version = 34;
   int debug_cluster_abort = 0;  // test hook (no environment name): the next one-launch solve finds `abort` raised; 2 = and the
                                 // give-up is remembered like a real one (the lm_cluster_retry_ms latch)
+  int debug_alloc_fill = 0;     // test hook (no environment name): 0 off; -1 = every block pool_alloc returns (parked or
+                                // fresh, over its whole capacity), every device_alloc block and the lazily allocated pinned
+                                // staging blocks are filled with the word 0x00000000 before they are handed out; 1 …
+                                // 0x7FFFFFFF = with that 32-bit word.  The context's own workspaces (nos_ctx_create) exist
+                                // before the option can be set and are not filled.
+  int debug_alloc_filled = 0;   // test hook: blocks filled so far (saturating); set to 0 to reset, nothing else is accepted
   int lm_cluster_max_blocks = 256;  // NOS_LM_CLUSTER_MAX_BLOCKS  workgroups of the one-launch loop (rehearsals: ranks sharing a GPU)
   int stream_lds_chunks = 3;   // NOS_STREAM_LDS_CHUNKS  streamed one-launch loop: chunks per workgroup kept in LDS after
                                //                        iteration 0 (0 … 3; 0 = everything streamed every iteration)
@@ -303,16 +324,8 @@ namespace nosd {
 constexpr int kSeqSlot = 32;  // index (in doubles) of the sequence word inside the pinned block
 constexpr int kCommErrorSlot = 40;  // index (in doubles) of the mailbox time-out flag (an unsigned int) in that block
 
-template <typename T>
-hipError_t upload(T** dptr, const std::vector<T>& host) {
-  const size_t bytes = std::max<size_t>(host.size(), 1) * sizeof(T);
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(dptr), bytes);
-  if (e == hipSuccess && !host.empty()) e = hipMemcpy(*dptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
-  return e;
-}
-
 // A scan under construction and its two device arrays, ONE copy of what nos_scan_create, the filter, the deskew and the
-// ray cast each need: alloc sizes them (planes, then order — hipMalloc, not the arena: the handle outlives the call);
+// ray cast each need: alloc sizes them (planes, then order — device_alloc, not the arena: the handle outlives the call);
 // release hands the finished handle to the caller; whatever was not released is freed when this goes out of scope, and a
 // failed allocation's sticky error goes with it, so that it does not surface as the next call's launch error.
 struct NewScan {
@@ -332,8 +345,9 @@ struct NewScan {
   explicit operator bool() const { return scan != nullptr; }
   // n points; n == 0: the empty form — a 24-byte planes block, so that d_planes is never NULL, and no order array
   hipError_t alloc(size_t n, bool with_order) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&scan->d_planes), std::max<size_t>(n, 1) * 3 * sizeof(double));
-    if (e == hipSuccess && with_order && n > 0) e = hipMalloc(reinterpret_cast<void**>(&scan->d_order), n * sizeof(uint32_t));
+    DeviceSlot& slot = scan->ctx->slots[0];
+    hipError_t e = device_alloc(slot, &scan->d_planes, std::max<size_t>(n, 1) * 3 * sizeof(double));
+    if (e == hipSuccess && with_order && n > 0) e = device_alloc(slot, &scan->d_order, n * sizeof(uint32_t));
     if (e == hipSuccess) scan->n = n;
     return e;
   }
@@ -344,26 +358,22 @@ struct NewScan {
   }
 };
 
-// Scratch buffers of one call, freed when it returns.  Without a slot: one hipMalloc / hipFree per buffer (round 1).  With a
-// slot (round 4): an ARENA — buffers are carved out of a few large slabs that come from the slot's buffer pool and go back
-// to it, so a map build no longer pays ≈ 20 hipMalloc + hipFree pairs (each hipFree also waits for the device) per call,
-// and repeated builds of similar size pay none.  reserve() sizes the next slab when the caller knows what is coming.
+// Scratch buffers of one call, freed when it returns: an ARENA — buffers are carved out of a few large slabs that come
+// from the slot's buffer pool and go back to it, so a map build pays no hipMalloc + hipFree pair per buffer (each hipFree
+// also waits for the device), and repeated builds of similar size pay none at all.  reserve() sizes the next slab when
+// the caller knows what is coming.
 struct DeviceBuffers {
-  std::vector<void*> ptrs;  // buffers allocated one by one (and rocPRIM temporaries the callers push here)
   struct Slab {
     void* ptr;
     size_t capacity, used;
   };
   std::vector<Slab> slabs;
-  DeviceSlot* slot = nullptr;
+  DeviceSlot* slot;
   size_t next_slab = 0;
-  DeviceBuffers() = default;
   explicit DeviceBuffers(DeviceSlot* s) : slot(s) {}
   DeviceBuffers(const DeviceBuffers&) = delete;
   DeviceBuffers& operator=(const DeviceBuffers&) = delete;
   ~DeviceBuffers() {
-    for (void* p : ptrs)
-      if (p) (void)hipFree(p);
     if (!slabs.empty()) (void)hipStreamSynchronize(slot->stream);  // nothing in flight may still use a slab that goes back
     for (Slab& sl : slabs) pool_release(*slot, sl.ptr, sl.capacity);
   }
@@ -371,11 +381,6 @@ struct DeviceBuffers {
   hipError_t alloc_bytes(void** out, size_t bytes) {
     bytes = (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
     *out = nullptr;
-    if (slot == nullptr) {
-      hipError_t e = hipMalloc(out, bytes);
-      if (e == hipSuccess) ptrs.push_back(*out);
-      return e;
-    }
     if (slabs.empty() || slabs.back().capacity - slabs.back().used < bytes) {
       const size_t grown = slabs.empty() ? size_t(8) << 20 : std::min<size_t>(2 * slabs.back().capacity, size_t(1) << 30);
       const size_t want = std::max(std::max(bytes, next_slab), grown);

@@ -104,8 +104,8 @@ int nos_scan_sort_by_cell(nos_scan* scan, double cell_edge) {
   if (e == hipSuccess) e = buf.alloc(&keys, n);
   if (e == hipSuccess) e = buf.alloc(&keys_sorted, n);
   if (e == hipSuccess) e = buf.alloc(&idx, n);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&order), n * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sorted), n * 3 * sizeof(double));
+  if (e == hipSuccess) e = device_alloc(slot, &order, n * sizeof(uint32_t));
+  if (e == hipSuccess) e = device_alloc(slot, &sorted, n * 3 * sizeof(double));
   CellKeys ck;
   if (e == hipSuccess) e = cell_keys(scan->ctx, buf, st, scan->d_planes, n, 1.0 / cell_edge, keys, idx, &ck);
   if (e == hipSuccess) {

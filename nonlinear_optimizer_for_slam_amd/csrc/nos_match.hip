@@ -149,8 +149,8 @@ int nosd::map_create_device(nos_ctx* ctx, size_t n_voxels, const double* d_means
   unsigned int *flags = nullptr, *box = nullptr;
   hipError_t e = hipSetDevice(slot.device);
   const size_t cap = std::max<size_t>(V, 1);  // of d_orig_id, which the map keeps; the arena's arrays hold at least one too
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&map->d_orig_id), cap * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&map->d_n_matches), sizeof(unsigned long long));
+  if (e == hipSuccess) e = device_alloc(slot, &map->d_orig_id, cap * sizeof(uint32_t));
+  if (e == hipSuccess) e = device_alloc(slot, &map->d_n_matches, sizeof(unsigned long long));
   if (e == hipSuccess) e = g.arrays(buf, st, V, map->d_orig_id);
   if (e == hipSuccess) e = g.temporaries(buf, 64);
   if (e == hipSuccess) e = buf.alloc(&flags, 4);
@@ -222,7 +222,7 @@ int nosd::map_create_device(nos_ctx* ctx, size_t n_voxels, const double* d_means
     const size_t b_start = up(table_size * sizeof(uint32_t)), b_count = up(table_size * sizeof(uint32_t));
     const size_t b_dense = n_dense > 0 ? up((n_dense + 1) * sizeof(uint32_t)) : 0, b_key = up(table_size * sizeof(uint64_t));
     char* base = nullptr;
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&base), b_mean + b_S + b_rec + b_start + b_count + b_dense + b_key);
+    if (e == hipSuccess) e = device_alloc(slot, &base, b_mean + b_S + b_rec + b_start + b_count + b_dense + b_key);
     if (e == hipSuccess) {
       map->d_block = base;
       map->d_mean = reinterpret_cast<double*>(base);
@@ -334,7 +334,7 @@ int nos_scan_create(nos_ctx* ctx, size_t n_points, const double* points_xyz, nos
   hipError_t e = hipSetDevice(slot.device);
   void* staging = nullptr;
   if (e == hipSuccess) e = scan.alloc(n_points, false);
-  if (e == hipSuccess) e = hipMalloc(&staging, std::max<size_t>(n_points, 1) * 3 * sizeof(double));
+  if (e == hipSuccess) e = device_alloc(slot, &staging, std::max<size_t>(n_points, 1) * 3 * sizeof(double));
   int rc = NOS_OK;
   if (e == hipSuccess && n_points > 0) {
     e = hipMemcpyAsync(staging, points_xyz, n_points * 3 * sizeof(double), hipMemcpyHostToDevice, slot.stream);
@@ -410,7 +410,7 @@ int nos_dataset_download(nos_dataset* ds, double* const planes[]) {
     if (cnt == 0) continue;
     NOS_HIP_CHECK(hipSetDevice(slot.device));
     double* tmp = nullptr;
-    NOS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tmp), cnt * size_t(ds->n_fields) * sizeof(double)));
+    NOS_HIP_CHECK(device_alloc(slot, &tmp, cnt * size_t(ds->n_fields) * sizeof(double)));
     const dim3 grid(unsigned((cnt + 255) / 256), unsigned(ds->n_fields));
     if (ds->dtype == NOS_F64)
       hipLaunchKernelGGL((nos::untile_kernel<double>), grid, dim3(256), 0, slot.stream,

@@ -115,7 +115,7 @@ int ensure_room(nos_place_db* db, DeviceSlot& slot) {
   const size_t new_cap = std::max(kPlaceMinCapacity, 2 * db->capacity);
   const size_t sd = slot_doubles(db->P);
   double* grown = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&grown), new_cap * sd * sizeof(double));
+  hipError_t e = device_alloc(slot, &grown, new_cap * sd * sizeof(double));
   if (e != hipSuccess) return hip_status(e, "growing the place database");
   if (db->size > 0) {
     e = hipMemcpyAsync(grown, db->d_slots, db->size * sd * sizeof(double), hipMemcpyDeviceToDevice, slot.stream);
@@ -207,7 +207,7 @@ int nos_place_db_create(nos_ctx* ctx, const nos_place_params* params, size_t res
   if (reserve > 0) {
     DeviceSlot& slot = ctx->slots[0];
     hipError_t e = hipSetDevice(slot.device);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&db->d_slots), reserve * slot_doubles(db->P) * sizeof(double));
+    if (e == hipSuccess) e = device_alloc(slot, &db->d_slots, reserve * slot_doubles(db->P) * sizeof(double));
     if (e != hipSuccess) return hip_status(e, "reserving the place database");
     db->capacity = reserve;
   }

@@ -31,9 +31,9 @@ int nos_voxel_map_create(nos_ctx* ctx, double voxel_resolution, double search_ra
   vm->min_capacity = vm->capacity;
   DeviceSlot& slot = ctx->slots[0];
   hipError_t e = hipSetDevice(slot.device);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&vm->d_info), nos::kInfoWords * sizeof(unsigned int));
+  if (e == hipSuccess) e = device_alloc(slot, &vm->d_info, nos::kInfoWords * sizeof(unsigned int));
   if (e == hipSuccess) e = hipMemsetAsync(vm->d_info, 0, nos::kInfoWords * sizeof(unsigned int), slot.stream);
-  if (e == hipSuccess) e = store_alloc(vm->capacity, slot.stream, &vm->d_block, &vm->block_bytes, &vm->view);
+  if (e == hipSuccess) e = store_alloc(slot, vm->capacity, &vm->d_block, &vm->block_bytes, &vm->view);
   if (e == hipSuccess) e = hipStreamSynchronize(slot.stream);
   if (e != hipSuccess) {
     if (vm->d_info) (void)hipFree(vm->d_info);

@@ -71,7 +71,7 @@ template <class T>
 hipError_t pgo_alloc(nos_pose_graph* pg, T** out, size_t count, bool pinned = false) {
   const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
   void* p = nullptr;
-  const hipError_t e = pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+  const hipError_t e = pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : device_alloc(pg->ctx->slots[0], &p, bytes);
   if (e != hipSuccess) return e;
   pg->owned.push_back({p, pinned});
   *out = static_cast<T*>(p);

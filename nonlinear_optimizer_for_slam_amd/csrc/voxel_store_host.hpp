@@ -69,8 +69,8 @@ inline nos::MapBuildParams finish_params(const nos_voxel_map* vm) {
   return nos::MapBuildParams{5, 0.01, 0.01, (vm->flags & NOS_MAP_PROPER_SQRT_INFORMATION) ? 1 : 0, vm->voxel_resolution};
 }
 
-// Arrays and table for `capacity` slots in one allocation; the table's keys start empty.
-inline hipError_t store_alloc(size_t capacity, hipStream_t st, void** block, size_t* block_bytes, nos::VoxelStoreView* v) {
+// Arrays and table for `capacity` slots in one allocation; the table's keys start empty (queued on the slot's stream).
+inline hipError_t store_alloc(DeviceSlot& slot, size_t capacity, void** block, size_t* block_bytes, nos::VoxelStoreView* v) {
   auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
   const size_t table = 2 * capacity;
   const size_t b_key = up(capacity * sizeof(uint64_t)), b_count = up(capacity * sizeof(uint32_t));
@@ -79,7 +79,7 @@ inline hipError_t store_alloc(size_t capacity, hipStream_t st, void** block, siz
   const size_t b_tkey = up(table * sizeof(unsigned long long)), b_tslot = up(table * sizeof(uint32_t));
   char* base = nullptr;
   const size_t bytes = b_key + b_count + b_acc + b_mean + b_S + b_valid + b_stamp + b_tkey + b_tslot;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), bytes);
+  hipError_t e = device_alloc(slot, &base, bytes);
   if (e != hipSuccess) return e;
   char* p = base;
   v->key = reinterpret_cast<uint64_t*>(p), p += b_key;
@@ -92,7 +92,7 @@ inline hipError_t store_alloc(size_t capacity, hipStream_t st, void** block, siz
   v->table_key = reinterpret_cast<unsigned long long*>(p), p += b_tkey;
   v->table_slot = reinterpret_cast<uint32_t*>(p);
   v->table_mask = uint32_t(table - 1);
-  e = hipMemsetAsync(v->table_key, 0xFF, table * sizeof(unsigned long long), st);
+  e = hipMemsetAsync(v->table_key, 0xFF, table * sizeof(unsigned long long), slot.stream);
   if (e != hipSuccess) {
     (void)hipFree(base);
     return e;
@@ -140,7 +140,7 @@ inline int store_reserve(nos_voxel_map* vm, size_t need) {
   void* block = nullptr;
   size_t block_bytes = 0;
   nos::VoxelStoreView nv{};
-  hipError_t e = store_alloc(capacity, st, &block, &block_bytes, &nv);
+  hipError_t e = store_alloc(slot, capacity, &block, &block_bytes, &nv);
   if (e != hipSuccess) return hip_fail(e, "growing the voxel store");
   const size_t V = vm->n_voxels;
   nv.n_voxels = vm->n_voxels;
@@ -406,7 +406,7 @@ struct KeepPass {
     void* block = nullptr;
     size_t block_bytes = 0;
     nos::VoxelStoreView nv{};
-    hipError_t e = store_alloc(capacity, st, &block, &block_bytes, &nv);
+    hipError_t e = store_alloc(vm->ctx->slots[0], capacity, &block, &block_bytes, &nv);
     if (e != hipSuccess) return hip_fail(e, "voxel store prune (new block)");
     nv.n_voxels = uint32_t(kept);
     unsigned int err = 0;
@@ -566,7 +566,7 @@ inline int store_restore(nos_voxel_map* vm, size_t n, const std::vector<uint64_t
   size_t block_bytes = 0;
   nos::VoxelStoreView nv{};
   hipError_t e = hipSetDevice(slot.device);
-  if (e == hipSuccess) e = store_alloc(capacity, st, &block, &block_bytes, &nv);
+  if (e == hipSuccess) e = store_alloc(slot, capacity, &block, &block_bytes, &nv);
   if (e != hipSuccess) return hip_fail(e, "voxel store restore (new block)");
   nv.n_voxels = uint32_t(n);
   unsigned int h_info[nos::kInfoWords] = {};
